@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- ECP iterations/sec and wall-clock to f_tol = 1e-6 on BASELINE.json's workload.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line (`value`, `ms_per_step` and the configuration; the
+fields of the other measurements are null).  --full adds everything else the line carries, as described below: the cold-start
+loads, the wall-clock to f_tol, the rooflines, the streaming ceiling, the CPU baseline and, with N > 1, the multi_gpu block.
+--dump-outputs DIR writes what the last timed step computed as float64 DIR/<name>.npy (solution.npy, objective.npy,
+ecp_iter.npy; --workload cfg5: solution.npy and objective.npy of every instance of rank 0's block); the inputs are generated
+from --seed, so two builds run with the same arguments can be compared output for output.
 
 A "step" is one pass of the reference's hot loop (src/model.jl:258-308): re-solve the growing LP,
 evaluate every nonlinear row at x*, append one tangent cut per violated row.  The workload at
@@ -20,10 +27,10 @@ are one curve).  How the path is split depends on the workload (--lp-layout auto
   row-sharded  --workload cfg4 (BASELINE.json configs[3], 1e6 exp/log rows): the LP ROW-SHARDED over the ranks
                (RowShardedKatanaModel): every rank keeps its own cuts, A'y costs one RCCL all-reduce of an n-vector per
                PDHG iteration.
-The line then also carries the per-phase split, the measured latency of one all-reduce of an n-vector on the fabric and the
-same workload timed on rank 0's GPU alone in the same run.
+With --full the line then also carries the per-phase split, the measured latency of one all-reduce of an n-vector on the
+fabric and the same workload timed on rank 0's GPU alone in the same run.
 
-Prints ONE JSON line (rank 0).  `value` = ECP iterations / second, whole job.
+Prints ONE JSON line (rank 0).  `value` = ECP iterations / second, whole job.  With --full also:
   roofline     -- the dominant kernel = whichever of k_pdhg_x / k_pdhg_y has the larger total time in the run
                   (algorithmic bytes per launch / mean launch duration from the start/stop hipEvents of
                   hipExtLaunchKernelGGL on the engine's own stream, in a second, identical pass over the same K steps
@@ -32,12 +39,13 @@ Prints ONE JSON line (rank 0).  `value` = ECP iterations / second, whole job.
                   (cfg3_hbm: 2048 instead of 32 entries per NL row, 411 MB per pass), same timing.
   spmv_roofline -- the LP SpMV steps on an HBM-resident cut matrix (cfg4's LP after one un-capped sweep: >= 1.2e7
                   non-zeros, CSR + CSC mirror beyond the Infinity Cache), same timing.
-  --workload cfg5 -- BASELINE.json configs[4] instead: the batch of 512 independent instances in throughput mode, split into one
-                  contiguous block per GPU with no communication; `value` is then instances/s (its own `metric` string).
   stream_ceiling -- torch.sum / copy_ over 1 GiB in the same run: the box's practical read and copy rates next to the 8 TB/s
                   spec figure the fractions are quoted against.
   cpu_baseline -- the CPU oracle (serial restatement of the reference + HiGHS dual simplex, 1 core) on the SAME
                   configuration as `value` (full cfg3: one solve to f_tol, about 100 s of one host core).
+--workload cfg5 -- BASELINE.json configs[4] instead: the batch of 512 independent instances in throughput mode, split into one
+                  contiguous block per GPU with no communication; `value` is then instances/s (its own `metric` string);
+                  --full adds incl_load, the same with the load inside the clock.
 """
 import argparse
 import json
@@ -50,7 +58,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec figure
+DUMP_LIMIT_BYTES = 64 << 20
 PROFILE_ROUND = "r04"      # profiles/<round>_kernel_stats.csv, <round>_traffic.json: the rocprofv3 summaries of THIS command
 
 
@@ -122,6 +131,9 @@ def parse():
     ap.add_argument("--warmup", type=int, default=11)
     ap.add_argument("--workload", default="cfg3", help="cfg3 (BASELINE.json's metric), cfg2, cfg4, cfg5, cfg3_qp ...")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true", help="also the measurements beyond `value` (cold start, wall-clock to f_tol, "
+                                                        "rooflines, CPU baseline, multi_gpu block); the --no-* options trim them")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as float64 DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-cpu-baseline-mt", action="store_true", help="skip the second CPU line (HiGHS default threading)")
     ap.add_argument("--no-roofline", action="store_true")
@@ -142,8 +154,9 @@ def parse():
     return a
 
 
-def run_steps(model, nsteps, solve_log=None):
-    """nsteps hot-loop passes; returns when exactly nsteps have run."""
+def run_steps(model, nsteps, solve_log=None, last=None):
+    """nsteps hot-loop passes; returns when exactly nsteps have run.  last(model), when given, is called at the end of the
+    final pass, before the reset that follows a finished solve: it sees what a caller of that pass receives."""
     done_steps = 0
     t_solve = time.perf_counter()
     if not getattr(model, "_bench_begun", False):
@@ -157,10 +170,22 @@ def run_steps(model, nsteps, solve_log=None):
             if solve_log is not None:
                 solve_log.append(dict(status=status, iters=model.numiters(), obj=model.getobjval(),
                                       wall=time.perf_counter() - t_solve, pdhg=model.stat("pdhg_iters")))
+        if last is not None and done_steps == nsteps:
+            last(model)
+        if finished:
             model.reset()
             model.optimize_begin()
             t_solve = time.perf_counter()
     return done_steps
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one float64 .npy per array (every workload's outputs stay far below the 64 MB limit)"""
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT_BYTES, "outputs beyond %d bytes" % DUMP_LIMIT_BYTES
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def cpu_baseline(args):
@@ -238,7 +263,7 @@ def main_batch(args, ktn, torch, dist, rank, world, local_rank, backend):
         if fb: fb.solve()
     barrier()
     t0 = time.perf_counter()
-    ok, worst = True, 0.0
+    ok, worst, res = True, 0.0, []
     for _ in range(args.steps):
         res = fb.solve() if fb else []
         for r, inst in zip(res, mine):
@@ -246,13 +271,17 @@ def main_batch(args, ktn, torch, dist, rank, world, local_rank, backend):
             worst = max(worst, abs(r["objval"] - inst.opt_obj) / max(1.0, abs(inst.opt_obj)))
     barrier()
     elapsed = time.perf_counter() - t0
-    # the same with the load inside the clock (three passes: fusion + description + ktn_loadproblem + solve)
-    barrier()
-    t1 = time.perf_counter()
-    for _ in range(3):
-        if fb: fb.load(mine).solve()                  # (a serving process keeps its handle: FusedBatch.load)
-    barrier()
-    incl = (time.perf_counter() - t1) / 3
+    if args.dump_outputs and rank == 0 and res:
+        dump_outputs(args.dump_outputs, {"objective": [r["objval"] for r in res], "solution": np.concatenate([r["x"] for r in res])})
+    incl = 0.0
+    if args.full:
+        # the same with the load inside the clock (three passes: fusion + description + ktn_loadproblem + solve)
+        barrier()
+        t1 = time.perf_counter()
+        for _ in range(3):
+            if fb: fb.load(mine).solve()                  # (a serving process keeps its handle: FusedBatch.load)
+        barrier()
+        incl = (time.perf_counter() - t1) / 3
     flags = torch.tensor([elapsed, 0.0 if ok else 1.0, worst, incl, load_s], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
     if dist is not None:
         dist.all_reduce(flags, op=dist.ReduceOp.MAX)
@@ -268,7 +297,8 @@ def main_batch(args, ktn, torch, dist, rank, world, local_rank, backend):
                        "parallelism": "1 GPU" if world == 1 else "%d contiguous blocks of the batch, one per GPU, no communication" % world},
             "status": "Optimal" if bad == 0.0 else "some instance not Optimal", "max_objective_relerr": worst,
             "incl_load": {"instances_per_s": nb / incl, "s_per_batch": incl, "first_load_s": load_s,
-                          "what": "instance fusion + row-program description + ktn_loadproblem + ktn_set_blocks on the same handle + solve, per batch"},
+                          "what": "instance fusion + row-program description + ktn_loadproblem + ktn_set_blocks on the same handle + solve, per batch"}
+                         if args.full else None,
             "roofline": None, "cpu_baseline": None}))
     if dist is not None:
         dist.destroy_process_group()
@@ -313,7 +343,8 @@ def main():
     else:
         # What a user of the reference pays (soltime spans all of optimize!, src/model.jl:227,311, and a JuMP `solve` pays
         # loadproblem! every time, src/model.jl:81-173): a fresh handle, the load and the first solve, COLD -- before any warm-up,
-        # first touch of the device allocator included.  The timed steps below then run from this handle's loaded state.
+        # first touch of the device allocator included.  The timed steps below then run from this handle's loaded state (a
+        # plain run makes this first solve too, so that its timed steps start from the same state as those of --full).
         torch.cuda.synchronize()
         tc0 = time.perf_counter()
         nlp = ktn.SeparableNLP(inst)
@@ -326,28 +357,29 @@ def main():
         cold = {"first_solve_s": tc3 - tc1, "first_load_s": tc2 - tc1, "first_optimize_s": tc3 - tc2, "describe_s": tc1 - tc0,
                 "status": st_first, "ecp_iters": model.numiters(),
                 "what": "fresh ktn_create + ktn_loadproblem + ktn_optimize on a cold process, host buffers in, before any warm-up"}
-        # ... and the same load with the allocator warm (a second problem on a live process): median of 3 on a second handle
-        m2 = ktn.NonlinearModel(ktn.KatanaSolver(log_level=0, device=local_rank))
-        loads = []
-        for _ in range(3):
-            torch.cuda.synchronize()
-            tl = time.perf_counter()
-            m2.loadproblem(inst.n, inst.num_constr, inst.l_var, inst.u_var, inst.l_constr, inst.u_constr, inst.sense, nlp)
-            loads.append(time.perf_counter() - tl)
-        cold["load_s"] = sorted(loads)[1]
-        del m2
-        # ... and what a JuMP user pays per solve (a NEW model, src/model.jl:63-65): a fresh handle in this warm process (~100
-        # device buffers allocated anew; a caching block pool was tried in round 4 and was SLOWER -- 28 against 15 ms -- because
-        # giving a block back needs the device synchronisation hipFree does implicitly, for every buffer)
-        fresh = []
-        for _ in range(3):
-            torch.cuda.synchronize()
-            tl = time.perf_counter()
-            m3 = ktn.NonlinearModel(ktn.KatanaSolver(log_level=0, device=local_rank))
-            m3.loadproblem(inst.n, inst.num_constr, inst.l_var, inst.u_var, inst.l_constr, inst.u_constr, inst.sense, nlp)
-            fresh.append(time.perf_counter() - tl)
-            del m3
-        cold["load_new_handle_s"] = sorted(fresh)[1]
+        if args.full:
+            # ... and the same load with the allocator warm (a second problem on a live process): median of 3 on a second handle
+            m2 = ktn.NonlinearModel(ktn.KatanaSolver(log_level=0, device=local_rank))
+            loads = []
+            for _ in range(3):
+                torch.cuda.synchronize()
+                tl = time.perf_counter()
+                m2.loadproblem(inst.n, inst.num_constr, inst.l_var, inst.u_var, inst.l_constr, inst.u_constr, inst.sense, nlp)
+                loads.append(time.perf_counter() - tl)
+            cold["load_s"] = sorted(loads)[1]
+            del m2
+            # ... and what a JuMP user pays per solve (a NEW model, src/model.jl:63-65): a fresh handle in this warm process (~100
+            # device buffers allocated anew; a caching block pool was tried in round 4 and was SLOWER -- 28 against 15 ms --
+            # because giving a block back needs the device synchronisation hipFree does implicitly, for every buffer)
+            fresh = []
+            for _ in range(3):
+                torch.cuda.synchronize()
+                tl = time.perf_counter()
+                m3 = ktn.NonlinearModel(ktn.KatanaSolver(log_level=0, device=local_rank))
+                m3.loadproblem(inst.n, inst.num_constr, inst.l_var, inst.u_var, inst.l_constr, inst.u_constr, inst.sense, nlp)
+                fresh.append(time.perf_counter() - tl)
+                del m3
+            cold["load_new_handle_s"] = sorted(fresh)[1]
         model.reset()
 
     def barrier():
@@ -355,15 +387,21 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    if multi_path:
+    if multi_path or not args.full:
         cold = None
     run_steps(model, args.warmup)
     barrier()
     solves = []
+    outputs = {}
+
+    def snapshot(m):
+        # rank 0's copy: the LP point x* of the last step is replicated over the ranks under both layouts
+        outputs.update(solution=m.getsolution(), objective=[m.getobjval()], ecp_iter=[m.numiters()])
+
     phase_keys = ("pdhg_iters", "lp_time_s", "sep_time_s", "lp_setup_time_s", "allreduce_calls", "allreduce_bytes")
     ph0 = {k: model.stat(k) for k in phase_keys}
     t0 = time.perf_counter()
-    run_steps(model, args.steps, solves)
+    run_steps(model, args.steps, solves, last=snapshot if args.dump_outputs and rank == 0 else None)
     barrier()
     elapsed = time.perf_counter() - t0
     phases = {k: model.stat(k) - ph0[k] for k in phase_keys}
@@ -372,20 +410,24 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if outputs:
+        dump_outputs(args.dump_outputs, outputs)
 
     # one complete solve from the loaded state: wall-clock to f_tol
-    model.reset()
-    model._bench_begun = False
-    barrier()
-    t1 = time.perf_counter()
-    status = model.optimize()
-    barrier()
-    wall_to_ftol = time.perf_counter() - t1
-    obj = model.getobjval()
-    iters_to_ftol = model.numiters()
+    status = obj = iters_to_ftol = wall_to_ftol = None
+    if args.full:
+        model.reset()
+        model._bench_begun = False
+        barrier()
+        t1 = time.perf_counter()
+        status = model.optimize()
+        barrier()
+        wall_to_ftol = time.perf_counter() - t1
+        obj = model.getobjval()
+        iters_to_ftol = model.numiters()
 
     roofline = None
-    if not multi_path and not args.no_roofline:
+    if args.full and not multi_path and not args.no_roofline:
         # identical second pass with per-launch hipEvent timing on the engine's stream
         prof = ktn.NonlinearModel(ktn.KatanaSolver(log_level=0, device=local_rank, profile=1))
         prof.loadproblem(inst.n, inst.num_constr, inst.l_var, inst.u_var, inst.l_constr, inst.u_constr, inst.sense,
@@ -431,7 +473,7 @@ def main():
     # the separator sweep on the HBM-resident variant of the same workload (k = 2048 entries per
     # NL row, 411 MB per pass); at cfg3's own k = 32 the sweep is a 10 us launch-latency-bound kernel.
     sweep_roofline = None
-    if not multi_path and not args.no_roofline and not args.no_sweep_roofline and args.workload == "cfg3":
+    if args.full and not multi_path and not args.no_roofline and not args.no_sweep_roofline and args.workload == "cfg3":
         hb = ktn.instances.make_config("cfg3_hbm", seed=args.seed, vertex=False)
         sm = ktn.NonlinearModel(ktn.KatanaSolver(log_level=0, device=local_rank, profile=1))
         sm.loadproblem(hb.n, hb.num_constr, hb.l_var, hb.u_var, hb.l_constr, hb.u_constr, hb.sense, ktn.SeparableNLP(hb))
@@ -470,7 +512,7 @@ def main():
     # The box's practical streaming ceilings next to the 8 TB/s spec figure `peak` ("quote the copy-kernel
     # ceiling measured in the same run"): a read-only reduction and a copy over 1 GiB, plain torch kernels
     stream_ceiling = None
-    if not multi_path and not args.no_roofline and rank == 0:
+    if args.full and not multi_path and not args.no_roofline and rank == 0:
         nel = (1 << 30) // 8
         xs_ = torch.ones(nel, dtype=torch.float64, device="cuda")
         ys_ = torch.empty_like(xs_)
@@ -491,7 +533,7 @@ def main():
     # The LP SpMV steps in the HBM regime (tools/spmv_bench.py): cfg4's LP after one un-capped sweep
     spmv_roofline = None
     sweep_short = None
-    if not multi_path and not args.no_roofline and not args.no_spmv_roofline and args.workload == "cfg3":
+    if args.full and not multi_path and not args.no_roofline and not args.no_spmv_roofline and args.workload == "cfg3":
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import spmv_bench
         sinst, sm, nviol = spmv_bench.build(1_000_000, device=local_rank)
@@ -557,13 +599,13 @@ def main():
         del sm, sinst
 
     cpu = None
-    if rank == 0 and not multi_path and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not multi_path and not args.no_cpu_baseline:
         cpu = cpu_baseline(args)
 
     # N > 1: the per-phase split of the timed region, the latency of one all-reduce of an n-vector on this fabric, and the
     # SAME workload on rank 0's GPU alone (what a strong-scaling ratio has to be taken against)
     multi = None
-    if multi_path:
+    if args.full and multi_path:
         t = torch.zeros(inst.n + 1, dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
         for _ in range(5):
             dist.all_reduce(t)
@@ -611,7 +653,7 @@ def main():
                            "rows sharded x%d (linear rows and NL rows by blocks, cuts stay on their rank), x replicated, "
                            "one all-reduce of an n-vector per PDHG iteration (transport: %s)" % (world, model.transport))},
             "wall_to_ftol_s": wall_to_ftol, "ecp_iters_to_ftol": iters_to_ftol, "status": status, "objective": obj,
-            "planted_objective": inst.opt_obj, "objective_relerr": abs(obj - inst.opt_obj) / max(1.0, abs(inst.opt_obj)),
+            "planted_objective": inst.opt_obj, "objective_relerr": abs(obj - inst.opt_obj) / max(1.0, abs(inst.opt_obj)) if args.full else None,
             "pdhg_iters_per_step": pdhg_timed / args.steps, "solves_in_timed_region": len(solves),
             "first_solve_s": cold["first_solve_s"] if cold else None, "load_s": cold["load_s"] if cold else None,
             "load_new_handle_s": cold["load_new_handle_s"] if cold else None, "cold": cold,

@@ -19,9 +19,9 @@ run_pmc() {    # name, counter, args...
   python3 $R/tools/pmc_reduce.py $OUT/${name}_$ctr $ctr > $OUT/${name}_pmc_${ctr}_per_kernel.csv
   rm -rf $OUT/${name}_$ctr
 }
-run_stats bench $R/bench.py --no-cpu-baseline --no-roofline
-run_pmc bench FETCH_SIZE $R/bench.py --no-cpu-baseline --no-roofline --steps 12 --warmup 0
-run_pmc bench WRITE_SIZE $R/bench.py --no-cpu-baseline --no-roofline --steps 12 --warmup 0
+run_stats bench $R/bench.py --full --no-cpu-baseline --no-roofline
+run_pmc bench FETCH_SIZE $R/bench.py --full --no-cpu-baseline --no-roofline --steps 12 --warmup 0
+run_pmc bench WRITE_SIZE $R/bench.py --full --no-cpu-baseline --no-roofline --steps 12 --warmup 0
 run_stats spmv_hbm $R/tools/spmv_bench.py 1000000 30
 run_pmc spmv_hbm FETCH_SIZE $R/tools/spmv_bench.py 1000000 8
 run_pmc spmv_hbm WRITE_SIZE $R/tools/spmv_bench.py 1000000 8
@@ -29,7 +29,7 @@ run_stats sweep_hbm $R/tools/sweep_bench.py cfg3_hbm 20
 run_pmc sweep_hbm FETCH_SIZE $R/tools/sweep_bench.py cfg3_hbm 8
 run_stats sweep_short $R/tools/sweep_viol.py cfg4 8          # the sweep on 1e6 short rows (bench.py sweep_roofline_short_rows) and the materialising precompute!
 cd $R
-python3 bench.py > $OUT/bench_cfg3.json 2> $OUT/bench_cfg3.err
+python3 bench.py --full > $OUT/bench_cfg3.json 2> $OUT/bench_cfg3.err
 python3 tools/spmv_bench.py 1000000 40 2>/dev/null | tail -1 > $OUT/spmv_hbm.json
 python3 tools/sweep_bench.py cfg3_hbm 20 2>/dev/null | tail -1 > $OUT/sweep_hbm.json
 ls -la $OUT
