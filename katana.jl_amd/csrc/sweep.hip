@@ -10,11 +10,19 @@ namespace ktn {
 // ------------------------------------------------------------------------------------
 // loadproblem!  src/model.jl:81-173
 // ------------------------------------------------------------------------------------
+// A tape VAR's Jacobian slot is the FIRST structure entry of its column; a column listed twice keeps 0 in the other
+// entries.  `slot_of` (one entry per column, all -1 on entry and on return) maps a column to that slot, so a row costs
+// O(tape + row) instead of a scan of the row per VAR.
 static void postfix_to_nodes(const int32_t* op, const double* arg, int64_t len, const int32_t* rcols, int64_t rlen,
-                             int64_t jac_base, std::vector<int32_t>& nop, std::vector<int32_t>& na,
-                             std::vector<int32_t>& nb, std::vector<double>& nc) {
+                             int64_t jac_base, std::vector<int64_t>& slot_of, std::vector<int32_t>& nop,
+                             std::vector<int32_t>& na, std::vector<int32_t>& nb, std::vector<double>& nc) {
     std::vector<int32_t> st;
     const int64_t base = (int64_t)nop.size();
+    for (int64_t s = rlen - 1; s >= 0; --s) slot_of[(size_t)rcols[s]] = s;          // backwards: the first slot wins
+    struct Reset {                                                                   // (also when a malformed tape throws)
+        std::vector<int64_t>& m; const int32_t* c; int64_t n;
+        ~Reset() { for (int64_t s = 0; s < n; ++s) m[(size_t)c[s]] = -1; }
+    } reset{slot_of, rcols, rlen};
     for (int64_t t = 0; t < len; ++t) {
         const int o = op[t];
         int32_t a = 0, b = 0;
@@ -22,9 +30,9 @@ static void postfix_to_nodes(const int32_t* op, const double* arg, int64_t len, 
         switch (o) {
             case KTN_OP_CONST: c = arg[t]; break;
             case KTN_OP_VAR: {
-                const int32_t v = (int32_t)arg[t];
-                int64_t slot = -1;
-                for (int64_t s = 0; s < rlen; ++s) if (rcols[s] == v) { slot = s; break; }
+                const double av = arg[t];
+                const int64_t slot = (av > -1.0 && av < (double)slot_of.size()) ? slot_of[(size_t)(int64_t)av] : -1;
+                const int32_t v = (int32_t)av;
                 if (slot < 0) throw Error(KTN_E_INVALID, "tape variable missing from the row's Jacobian structure");
                 a = v;
                 b = (int32_t)(jac_base + slot);
@@ -187,6 +195,10 @@ void Engine::loadproblem(int64_t num_var, int64_t num_constr, const double* l_va
     std::vector<int32_t> nop, na, nb;
     std::vector<double> nc;
     std::vector<int32_t> tape_all;
+    std::vector<int64_t> col_slot;
+    for (int64_t i = 0; i < m_ext; ++i) {
+        if (h_rowkind[i] == KTN_ROW_TAPE) { col_slot.assign((size_t)n0 + 1, -1); break; }
+    }
     for (int64_t i = 0; i < m_ext; ++i) {
         nodeptr[i] = (int64_t)nop.size();
         if (h_rowkind[i] != KTN_ROW_TAPE) continue;
@@ -196,14 +208,14 @@ void Engine::loadproblem(int64_t num_var, int64_t num_constr, const double* l_va
         if (i < m0) {
             KTN_REQUIRE(d->tape_ptr != nullptr, "tape row without tape arrays");
             const int64_t tb = d->tape_ptr[i], te = d->tape_ptr[i + 1];
-            postfix_to_nodes(d->tape_op + tb, d->tape_arg + tb, te - tb, rc, rl, h_rowptr[i], nop, na, nb, nc);
+            postfix_to_nodes(d->tape_op + tb, d->tape_arg + tb, te - tb, rc, rl, h_rowptr[i], col_slot, nop, na, nb, nc);
         } else {
             std::vector<int32_t> op(d->obj_tape_op, d->obj_tape_op + d->obj_tape_len);
             std::vector<double> arg(d->obj_tape_arg, d->obj_tape_arg + d->obj_tape_len);
             if (op.empty()) { op.push_back(KTN_OP_CONST); arg.push_back(0.0); }
             op.push_back(KTN_OP_VAR); arg.push_back((double)n0);
             op.push_back(KTN_OP_SUB); arg.push_back(0.0);
-            postfix_to_nodes(op.data(), arg.data(), (int64_t)op.size(), rc, rl, h_rowptr[i], nop, na, nb, nc);
+            postfix_to_nodes(op.data(), arg.data(), (int64_t)op.size(), rc, rl, h_rowptr[i], col_slot, nop, na, nb, nc);
         }
     }
     nodeptr[m_ext] = (int64_t)nop.size();

@@ -85,3 +85,51 @@ def max_nl_violation(inst, x):
 # reference's tests ask for 1e-3 (or rtol 1e-7 on 202_04).  Status and objective at the
 # suite-wide 1e-6 tolerance are asserted for every KAT; for these ids x is asserted at 3e-3.
 TRAJECTORY_SENSITIVE = {"105_04", "202_04", "501_02_n3", "501_02_n4", "501_02_n9"}
+
+
+def instance_as_expressions(ktn, inst):
+    """(objective, constraints) of a SeparableInstance written as expressions, atom by atom in storage order, folded left
+    to right: LIN p0*x, QUAD p0*(x-p1)^2, EXP p0*exp(p1*x), NEGLOG -p0*log(x+p1); every row ends with + rconst."""
+    def atoms(cols, kinds, p0, p1):
+        e = None
+        for j, k, a, b in zip(cols, kinds, p0, p1):
+            x = ktn.var(int(j))
+            a, b = float(a), float(b)
+            t = [a * x, a * (x - b) ** 2, a * ktn.exp(b * x), (-a) * ktn.log(x + b)][int(k)]
+            e = t if e is None else e + t
+        return e
+    rp = inst.rowptr
+    cons = []
+    for i in range(inst.num_constr):
+        s = slice(rp[i], rp[i + 1])
+        e = atoms(inst.col[s], inst.kind[s], inst.p0[s], inst.p1[s])
+        cons.append(ktn.const(float(inst.rconst[i])) if e is None else e + float(inst.rconst[i]))
+    obj = atoms(inst.obj_col, inst.obj_kind, inst.obj_p0, inst.obj_p1) + float(inst.obj_const)
+    return obj, cons
+
+
+def julia_shaped_nlp(ktn, n, objective, constraints, constr_linear, obj_linear, rng):
+    """Restatement of build_ktn_nlp_desc (katana.jl_amd/julia/KatanaHIP.jl) for s-expression models: every row a TAPE row
+    (linear rows too) with row_linear as declared, n-ary + and * folded left to right, the Jacobian structure taken from a
+    COO list in shuffled order and converted to CSR row by row in COO order, the objective a TAPE even when linear."""
+    from oracle import sexpr
+    L = ktn._lib
+    coo = [(i, j) for i, s in enumerate(constraints) for j in sexpr.variables(s)]
+    coo = [coo[k] for k in rng.permutation(len(coo))]
+    m = len(constraints)
+    counts = np.bincount([i for i, _ in coo], minlength=m) if coo else np.zeros(m, dtype=np.int64)
+    rowptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    fill = rowptr[:-1].copy()
+    col = np.zeros(len(coo), dtype=np.int32)
+    for i, j in coo:
+        col[fill[i]] = j
+        fill[i] += 1
+    tptr, top, targ = [0], [], []
+    for s in constraints:
+        o, a = ktn.from_sexpr(s).tape()
+        top.extend(o.tolist()); targ.extend(a.tolist())
+        tptr.append(len(top))
+    oo, oa = ktn.from_sexpr(objective).tape()
+    return ktn.NLPDescription(n, rowptr, col, np.full(m, L.ROW_TAPE), [1 if f else 0 for f in constr_linear], np.zeros(m),
+                              None, None, None, tptr, top, targ, obj_linear=bool(obj_linear), obj_kind=L.ROW_TAPE,
+                              obj_tape_op=oo, obj_tape_arg=oa)
