@@ -8,13 +8,29 @@ workgroups each and many of them fit on the 256 CUs side by side."""
 import time
 from concurrent.futures import ThreadPoolExecutor
 
-from .nlp import SeparableNLP
+from .nlp import SeparableNLP, Problem, fuse_problems
 from .solver import NonlinearModel
+
+
+def _as_problem(item):
+    """a Problem of a jump_like.Model (Model.problem()), a SeparableInstance (SeparableNLP) or a Problem"""
+    if isinstance(item, Problem):
+        return item
+    if hasattr(item, "problem"):
+        return item.problem()
+    return Problem(item.n, item.num_constr, item.l_var, item.u_var, item.l_constr, item.u_constr, item.sense, SeparableNLP(item))
+
+
+def _all_instances(items):
+    from .instances import SeparableInstance
+    return all(isinstance(i, SeparableInstance) for i in items)
 
 
 def solve_batch(solver, instances, threads=16, describe=SeparableNLP, fused=False, per_instance_lp=False, device_loop=None):
     """Solve every instance; returns (results, wall_seconds).  results[i] = dict(status, objval, iters,
-    numcuts, x) in the order of `instances`.
+    numcuts, x) in the order of `instances`.  The items are SeparableInstances or -- expression-built models, tape rows
+    included -- Problems (katana_jl_amd.Problem: the arguments of loadproblem!) or jump_like.Models; a fused batch of the
+    latter is the block-diagonal union of nlp.fuse_problems, and each instance's objective is reported in its own sense.
 
     fused=True solves the block-diagonal union of the instances as ONE problem (instances.fuse_instances): the
     cutting-plane loop, the sweep and every PDHG launch then serve the whole batch at once, and the stop rule --
@@ -26,15 +42,18 @@ def solve_batch(solver, instances, threads=16, describe=SeparableNLP, fused=Fals
     cutting-plane round still waits for its slowest instance, so the batch takes 0.26 s against 0.22 s -- hence off by default.
     With device_loop (the default for fused batches) the WHOLE cutting-plane loop of every instance runs inside its own
     workgroup (ktn_optimize_blocks, csrc/batch_ecp.hpp): no instance waits for another; 0.10 s for 512 x cfg5.  Batches it does
-    not cover (tape rows, nonlinear objective, free variables) fall back to the host-driven loop inside the call."""
+    not cover (host rows, nonlinear objective, free variables) fall back to the host-driven loop inside the call."""
     if device_loop is None:
         device_loop = fused and not per_instance_lp
     if fused:
         return _solve_fused(solver, instances, per_instance_lp, device_loop)
     def work(inst):
         m = NonlinearModel(solver)
-        m.loadproblem(inst.n, inst.num_constr, inst.l_var, inst.u_var, inst.l_constr, inst.u_constr, inst.sense,
-                      describe(inst))
+        if isinstance(inst, Problem) or hasattr(inst, "problem"):
+            m.loadproblem(*_as_problem(inst))
+        else:
+            m.loadproblem(inst.n, inst.num_constr, inst.l_var, inst.u_var, inst.l_constr, inst.u_constr, inst.sense,
+                          describe(inst))
         status = m.optimize()
         return dict(status=status, objval=m.getobjval(), iters=m.numiters(), numcuts=m.numcuts(), x=m.getsolution(),
                     pdhg_iters=m.stat("pdhg_iters"))
@@ -65,6 +84,14 @@ class FusedBatch:
         import numpy as np
         from .instances import fuse_instances
         self.instances = instances
+        if not _all_instances(instances):                          # Problems / Models, tape rows allowed (nlp.fuse_problems)
+            self.big, self.offs, self._objinfo = fuse_problems([_as_problem(i) for i in instances])
+            self.m.loadproblem(*self.big)
+            if self.per_instance_lp or self.device_loop:
+                self.m.set_blocks(self.offs)
+            self._solved = False
+            return self
+        self._objinfo = None
         self.big, self.offs = fuse_instances(instances)
         big = self.big
         self.m.loadproblem(big.n, big.num_constr, big.l_var, big.u_var, big.l_constr, big.u_constr, big.sense, SeparableNLP(big))
@@ -85,6 +112,18 @@ class FusedBatch:
         self._solved = True
         status = m.optimize_blocks(cut_capacity) if self.device_loop else m.optimize()
         x = m.getsolution()
+        common = dict(status=status, iters=m.numiters(), numcuts=None, pdhg_iters=m.stat("pdhg_iters"),
+                      blk_lp_launches=m.stat("blk_lp_launches"), blk_lp_fallbacks=m.stat("blk_lp_fallbacks"),
+                      blk_pdhg_iters_sum=m.stat("blk_pdhg_iters_sum"), ecp_blocks_launches=m.stat("ecp_blocks_launches"),
+                      ecp_blocks_fallbacks=m.stat("ecp_blocks_fallbacks"), ecp_blocks_pdhg_sum=m.stat("ecp_blocks_pdhg_sum"))
+        if self._objinfo is not None:
+            # each instance's objective in its own sense, from its own LIN coefficients and constant on its slice of x
+            common["ecp_blocks_tape_rows"] = m.stat("ecp_blocks_tape_rows")
+            out = []
+            for k, (cols, coefs, c0) in enumerate(self._objinfo):
+                xk = x[offs[k]:offs[k + 1]]
+                out.append(dict(common, objval=float(np.sum(coefs * xk[cols]) + c0), x=xk))
+            return out
         # per-instance objectives: all atoms of the fused objective at once, then sums by instance
         kind, p0, p1, col = self._obj
         val, _ = atom_value_deriv(kind, p0, p1, x[col])
@@ -93,10 +132,6 @@ class FusedBatch:
         nz = np.flatnonzero(np.diff(optr) > 0)                    # (instances with an empty objective are not reduceat starts)
         if len(nz):
             seg[nz] = np.add.reduceat(val, optr[:-1][nz])
-        common = dict(status=status, iters=m.numiters(), numcuts=None, pdhg_iters=m.stat("pdhg_iters"),
-                      blk_lp_launches=m.stat("blk_lp_launches"), blk_lp_fallbacks=m.stat("blk_lp_fallbacks"),
-                      blk_pdhg_iters_sum=m.stat("blk_pdhg_iters_sum"), ecp_blocks_launches=m.stat("ecp_blocks_launches"),
-                      ecp_blocks_fallbacks=m.stat("ecp_blocks_fallbacks"), ecp_blocks_pdhg_sum=m.stat("ecp_blocks_pdhg_sum"))
         return [dict(common, objval=float(seg[k] + inst.obj_const), x=x[offs[k]:offs[k + 1]]) for k, inst in enumerate(self.instances)]
 
 

@@ -5,7 +5,8 @@
 // tolerance schedule and the stop rule -- so that no instance ever waits for another (with a host-driven round per
 // cutting-plane iteration every round waits for its slowest instance: csrc/batch_lp.hpp).
 //
-// The batch is loaded as one block-diagonal problem (instances.fuse_instances) of SEPARABLE rows with a linear objective;
+// The batch is loaded as one block-diagonal problem (instances.fuse_instances, nlp.fuse_problems) of separable or tape rows
+// with a linear objective;
 // ktn_loadproblem builds the fused LP of the linear rows as usual.  k_ecp_blocks then works on a per-instance ARENA in
 // global memory (the instance's LP in local indices with room for its cuts): CSR rows (unscaled + scaled values), CSC
 // mirror (unscaled + scaled), row bounds, duals, diagonal scalings, scaled problem vectors.  The PDHG iterates live in
@@ -32,6 +33,8 @@ struct EcpBatch {
     const int64_t* lp_rowptr; const int32_t* lp_col; const double* lp_val; const double* lp_lo; const double* lp_hi;   // loaded LP
     const double* c; const double* l; const double* u;                                                                // LP columns (unscaled)
     NlpDev P; const int32_t* nl_rows;                                                                                 // NL rows (global ids)
+    double* jac;                     // Jacobian scratch indexed like the structure (tape rows: written by the eval pass, read by the emit pass)
+    int has_tape;                    // some NL row is a KTN_ROW_TAPE row (0: the sweep is the separable one alone)
     // ---- arenas
     const EcpArena* arena;
     int32_t* rptr; uint16_t* rcol; double* rval; double* rsval; double* lo; double* hi; double* y; double* dr; double* loh; double* hih;
@@ -117,6 +120,13 @@ __device__ __forceinline__ void ecp_spmv(int count, const int32_t* __restrict__ 
         }
         if (fin) out(omine, mine, pf);
     }
+}
+
+// one tape row at the instance's LDS copy of x (xs[col - c0]).  Inlined: as a call (__noinline__) the kernel's scratch grows
+// from 376 to 1 440 bytes per lane (the live state of the PDHG loop is saved around the call), inlined to 504
+// (DESIGN.md section 8).
+static __device__ __forceinline__ double ecp_tape_row(const NlpDev& P, int32_t r, const double* xs, int c0, double* jac) {
+    return tape_row_eval(P, r, [&](int32_t c) { return xs[c - c0]; }, jac);
 }
 
 static __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B) {
@@ -509,13 +519,15 @@ static __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B) {
         __syncthreads();
 
         // ============================================================ separator sweep over the instance's NL rows ======
-        // precompute! + isconstrsat (src/separators.jl:111-120): 16 lanes per row; flags and row lengths into icnt
+        // precompute! + isconstrsat (src/separators.jl:111-120): 16 lanes per separable row, one lane per tape row; flags and
+        // row lengths into icnt
         double mv[1] = {0.0};
         int bad_nf = 0;
         {
             const int lane = tid & 15;
             for (int i = tid / 16; i < m_nl; i += kEcpThreads / 16) {
                 const int32_t gr = B.nl_rows[nl0 + i];
+                if (B.has_tape && B.P.row_kind[gr] == KTN_ROW_TAPE) continue;          // (the device row_kind also holds kRowSepLong)
                 const int64_t beg = B.P.rowptr[gr], end = B.P.rowptr[gr + 1];
                 double g = 0.0;
                 for (int64_t e = beg + lane; e < end; e += 16) {
@@ -532,6 +544,20 @@ static __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B) {
                     const bool sat = (g >= lb - f_eff) && (g <= ub + f_eff);           // NaN -> violated
                     icnt[i] = sat ? 0 : (int)(end - beg);
                     yts[i] = g;                                                         // keep g for the emit pass (m_nl <= mmax)
+                    if (!sat) { double d = fmax(g - ub, lb - g); if (!(d == d)) d = __builtin_inf(); mv[0] = fmax(mv[0], d); }
+                }
+            }
+            // tape rows: the interpreter of k_tape_eval with x from LDS; node values and adjoints in the rows' own slices of
+            // node_val / node_adj, Jacobian entries into B.jac (the instances' node and entry ranges are disjoint)
+            if (B.has_tape) {
+                for (int i = tid; i < m_nl; i += kEcpThreads) {
+                    const int32_t gr = B.nl_rows[nl0 + i];
+                    if (B.P.row_kind[gr] != KTN_ROW_TAPE) continue;
+                    const double g = ecp_tape_row(B.P, gr, xs, (int)c0, B.jac);
+                    const double lb = B.P.lb[gr], ub = B.P.ub[gr];
+                    const bool sat = (g >= lb - f_eff) && (g <= ub + f_eff);           // NaN -> violated
+                    icnt[i] = sat ? 0 : (int)(B.P.rowptr[gr + 1] - B.P.rowptr[gr]);
+                    yts[i] = g;
                     if (!sat) { double d = fmax(g - ub, lb - g); if (!(d == d)) d = __builtin_inf(); mv[0] = fmax(mv[0], d); }
                 }
             }
@@ -588,14 +614,20 @@ static __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B) {
                 const int32_t gr = B.nl_rows[nl0 + i];
                 const int64_t beg = B.P.rowptr[gr], end = B.P.rowptr[gr + 1];
                 const int dst = rptr[rnew];
+                const bool tape = B.has_tape && B.P.row_kind[gr] == KTN_ROW_TAPE;     // its entries are in B.jac already
                 double dot = 0.0, mx = -__builtin_inf();
                 int nf = 0;
                 for (int64_t e = beg + lane; e < end; e += 16) {
                     const int ck = B.P.colk[e];
-                    const double2 pp = B.P.pp[e];
                     const int cl = (ck & kColMask) - (int)c0;
-                    double val, der;
-                    atom_eval((unsigned)ck >> kKindShift, pp.x, pp.y, xs[cl], val, der);
+                    double der;
+                    if (tape) {
+                        der = B.jac[e];
+                    } else {
+                        const double2 pp = B.P.pp[e];
+                        double val;
+                        atom_eval((unsigned)ck >> kKindShift, pp.x, pp.y, xs[cl], val, der);
+                    }
                     dot += xs[cl] * der;
                     mx = nanmax(mx, der);
                     nf |= !isfinite(der);

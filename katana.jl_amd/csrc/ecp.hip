@@ -10,8 +10,9 @@ namespace ktn {
 // Throughput mode, device-side loop (batch_ecp.hpp).  Returns false when the problem does not qualify or an instance
 // could not finish (arena overflow, LP status): the caller then runs the ordinary loop.
 bool Engine::optimize_blocks_device(int cap_mul) {
-    if (n_blocks <= 0 || !obj_linear || sense != KTN_MIN || has_inf_bound || n_tape_nl > 0 || n_host > 0 || prm.vis_data) return false;
-    for (int64_t i = 0; i < m_ext - 1; ++i) if (h_rowkind[(size_t)i] != KTN_ROW_SEP) return false;
+    // (rows: separable or tape, linear or not; k_ecp_blocks evaluates tape rows with the interpreter of k_tape_eval)
+    if (n_blocks <= 0 || !obj_linear || sense != KTN_MIN || has_inf_bound || n_host > 0 || prm.vis_data) return false;
+    for (int64_t i = 0; i < m_ext - 1; ++i) if (h_rowkind[(size_t)i] != KTN_ROW_SEP && h_rowkind[(size_t)i] != KTN_ROW_TAPE) return false;
     const int nb = (int)n_blocks;
     auto block_of_col = [&](int64_t c) { return (int)(std::upper_bound(h_blkcol.begin(), h_blkcol.end(), c) - h_blkcol.begin()) - 1; };
     // linear rows of the loaded LP (in original row order) and NL slots must be grouped by instance, instance after instance
@@ -78,6 +79,7 @@ bool Engine::optimize_blocks_device(int cap_mul) {
     B.lp_rowptr = lp_rowptr.p; B.lp_col = lp_col.p; B.lp_val = lp_val.p; B.lp_lo = lp_lo.p; B.lp_hi = lp_hi.p;
     B.c = lp_c.p; B.l = lp_l.p; B.u = lp_u.p;
     B.P = nlp_view(); B.nl_rows = d_nlrows.p;
+    B.jac = d_jac.p; B.has_tape = n_tape_nl > 0 ? 1 : 0;      // every row owns its entries of the Jacobian buffer
     B.arena = d_ar.p;
     B.rptr = e_rptr.p; B.rcol = e_rcol.p; B.rval = e_rval.p; B.rsval = e_rsval.p; B.lo = e_lo.p; B.hi = e_hi.p; B.y = e_y.p; B.dr = e_dr.p;
     B.loh = e_loh.p; B.hih = e_hih.p;
@@ -120,6 +122,7 @@ bool Engine::optimize_blocks_device(int cap_mul) {
     stats["ecp_blocks_launches"] += 1.0;
     stats["ecp_blocks_pdhg_sum"] += pd;
     stats["ecp_blocks_rows"] = rows;
+    stats["ecp_blocks_tape_rows"] = (double)n_tape_nl;
     if (!ok) { stats["ecp_blocks_fallbacks"] += 1.0; return false; }
     status = KTN_STATUS_OPTIMAL; lp_status = KTN_STATUS_OPTIMAL;
     iter = (int64_t)it_max; numcuts = (int64_t)cuts; objval = obj + c0; allsat = true;

@@ -657,17 +657,15 @@ static __global__ __launch_bounds__(kBlock) void k_depth_reflag(int64_t m_nl, co
     if (flag[s] && keys[s] < thr) { flag[s] = 0; cnt[s] = 0; }
 }
 
-// precompute! for tape rows: one thread per row, forward sweep then reverse sweep over
-// the row's expression DAG.  Derivative conventions follow the oracle (oracle/sexpr.py):
-// log' = 1/v, sqrt' = 0.5/sqrt(v), pow: 2 -> 2v, 1 -> 1, else p v^(p-1).
-static __global__ __launch_bounds__(kBlock) void k_tape_eval(NlpDev P, const int32_t* __restrict__ tape_rows, int64_t n_tape,
-                                                      const double* __restrict__ x, SweepOut O) {
-    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (t >= n_tape) return;
-    const int32_t r = tape_rows[t];
+// precompute! of ONE tape row by one thread: forward sweep then reverse sweep over the row's expression DAG; returns
+// g = value + rconst and writes the row's Jacobian entries into jac (indexed like the structure).  Derivative conventions
+// follow the oracle (oracle/sexpr.py): log' = 1/v, sqrt' = 0.5/sqrt(v), pow: 2 -> 2v, 1 -> 1, else p v^(p-1).
+// XF says how x is read: xat(global column) -- x[col] in k_tape_eval, the workgroup's LDS copy in k_ecp_blocks.
+template <class XF>
+__device__ __forceinline__ double tape_row_eval(const NlpDev& P, int32_t r, XF&& xat, double* jac) {
     const int64_t nb = P.node_ptr[r], ne = P.node_ptr[r + 1];
-    for (int64_t e = P.rowptr[r]; e < P.rowptr[r + 1]; ++e) O.jac[e] = 0.0;
-    if (ne == nb) { O.g[r] = P.rconst[r]; return; }
+    for (int64_t e = P.rowptr[r]; e < P.rowptr[r + 1]; ++e) jac[e] = 0.0;
+    if (ne == nb) return P.rconst[r];
     double* val = P.node_val;
     double* adj = P.node_adj;
     for (int64_t i = nb; i < ne; ++i) {
@@ -677,7 +675,7 @@ static __global__ __launch_bounds__(kBlock) void k_tape_eval(NlpDev P, const int
         double v;
         switch (op) {
             case KTN_OP_CONST: v = P.node_c[i]; break;
-            case KTN_OP_VAR: v = x[P.node_a[i]]; break;
+            case KTN_OP_VAR: v = xat(P.node_a[i]); break;
             case KTN_OP_ADD: v = a + b; break;
             case KTN_OP_SUB: v = a - b; break;
             case KTN_OP_MUL: v = a * b; break;
@@ -698,7 +696,7 @@ static __global__ __launch_bounds__(kBlock) void k_tape_eval(NlpDev P, const int
         const int op = P.node_op[i];
         const double w = adj[i];
         if (op == KTN_OP_CONST) continue;
-        if (op == KTN_OP_VAR) { O.jac[P.node_b[i]] += w; continue; }
+        if (op == KTN_OP_VAR) { jac[P.node_b[i]] += w; continue; }
         const int64_t ia = nb + P.node_a[i];
         const double a = val[ia];
         switch (op) {
@@ -719,7 +717,16 @@ static __global__ __launch_bounds__(kBlock) void k_tape_eval(NlpDev P, const int
             default: adj[ia] += w * (-sin(a)); break;
         }
     }
-    O.g[r] = val[ne - 1] + P.rconst[r];
+    return val[ne - 1] + P.rconst[r];
+}
+
+// precompute! for tape rows: one thread per row
+static __global__ __launch_bounds__(kBlock) void k_tape_eval(NlpDev P, const int32_t* __restrict__ tape_rows, int64_t n_tape,
+                                                      const double* __restrict__ x, SweepOut O) {
+    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (t >= n_tape) return;
+    const int32_t r = tape_rows[t];
+    O.g[r] = tape_row_eval(P, r, [&](int32_t c) { return x[c]; }, O.jac);
 }
 
 // linear_oa_cut constant / round_coefs max / finite check / isconstrsat from a

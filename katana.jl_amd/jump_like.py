@@ -7,7 +7,7 @@ import math
 import numpy as np
 
 from .expr import Expr, var
-from .nlp import ExprNLP
+from .nlp import ExprNLP, Problem
 from .solver import NonlinearModel
 
 
@@ -48,6 +48,12 @@ class Model:
         lin = [c[3] for c in self.cons]
         lin = None if any(v is None for v in lin) else lin
         return ExprNLP(n, self.obj, [c[0] for c in self.cons], lin, self.obj_linear)
+
+    def problem(self):
+        """the arguments of loadproblem! for this model (a Problem), without solving it"""
+        return Problem(len(self.lb), len(self.cons), np.asarray(self.lb, dtype=np.float64), np.asarray(self.ub, dtype=np.float64),
+                       np.asarray([c[1] for c in self.cons], dtype=np.float64),
+                       np.asarray([c[2] for c in self.cons], dtype=np.float64), self.sense, self.build())
 
     def solve(self):
         d = self.build()

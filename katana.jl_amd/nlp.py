@@ -4,11 +4,16 @@ loadproblem! (src/model.jl:86).  An NLPDescription owns the numpy arrays behind 
 its evaluator (jac_structure, isconstrlinear, isobjlinear); values and derivatives are
 computed on the device only."""
 import ctypes as C
+from collections import namedtuple
 
 import numpy as np
 
 from . import _lib as L
 from .expr import Expr
+
+
+# the arguments of loadproblem! (src/model.jl:81-86): NonlinearModel.loadproblem(*problem)
+Problem = namedtuple("Problem", "num_var num_constr l_var u_var l_constr u_constr sense d")
 
 
 def _ptr(a, ctype):
@@ -197,3 +202,107 @@ class CallbackNLP(NLPDescription):
         d.eval_obj = C.cast(self._obj_cb, C.c_void_p)
         d.eval_user = None
         return d
+
+
+def tape_affine(ops, args):
+    """(coef dict, constant) of a postfix tape that is affine, else None: one pass that carries affine forms through
+    CONST, VAR, ADD, SUB, NEG, and MUL or DIV with one constant side.  The values are those of Expr.affine() of the tape's
+    source expression (a + s*b: a[k] + s*b[k] where both hold k, 0.0 + s*b[k] where only b does)."""
+    st = []
+    for o, c in zip(np.asarray(ops).tolist(), np.asarray(args).tolist()):
+        if o == L.OP_CONST:
+            st.append(({}, float(c)))
+        elif o == L.OP_VAR:
+            st.append(({int(c): 1.0}, 0.0))
+        elif o == L.OP_NEG:
+            co, k = st.pop()
+            st.append(({j: -v for j, v in co.items()}, -k))
+        elif o in (L.OP_ADD, L.OP_SUB, L.OP_MUL, L.OP_DIV):
+            (cb, kb), (ca, ka) = st.pop(), st.pop()
+            if o in (L.OP_ADD, L.OP_SUB):
+                s = 1.0 if o == L.OP_ADD else -1.0
+                co = dict(ca)
+                for j, v in cb.items():
+                    co[j] = co.get(j, 0.0) + s * v
+                st.append((co, ka + s * kb))
+            elif o == L.OP_MUL and not ca:
+                st.append(({j: ka * v for j, v in cb.items()}, ka * kb))
+            elif o == L.OP_MUL and not cb:
+                st.append(({j: kb * v for j, v in ca.items()}, ka * kb))
+            elif o == L.OP_DIV and not cb:
+                st.append(({j: v / kb for j, v in ca.items()}, ka / kb))
+            else:
+                return None
+        else:
+            return None
+    if not st:
+        return {}, 0.0
+    assert len(st) == 1, "malformed tape"
+    return st[0]
+
+
+def _linear_objective(d, k):
+    """(cols, coefs, constant) of problem k's objective, which must be declared linear and be linear"""
+    if isinstance(d, CallbackNLP) or d.obj_kind == L.ROW_HOST:
+        raise ValueError("problem %d: host-evaluated rows or objective (CallbackNLP) cannot be fused" % k)
+    if not d.obj_linear:
+        raise ValueError("problem %d: nonlinear objective; a fused batch needs linear objectives" % k)
+    if d.obj_kind == L.ROW_SEP:
+        if len(d.obj_atom_kind) and np.any(d.obj_atom_kind != L.ATOM_LIN):
+            raise ValueError("problem %d: objective declared linear has nonlinear atoms" % k)
+        return d.obj_col.astype(np.int64), d.obj_p0.copy(), d.obj_const
+    aff = tape_affine(d.obj_tape_op, d.obj_tape_arg)
+    if aff is None:
+        raise ValueError("problem %d: objective declared linear is not affine (CONST, VAR, +, -, neg, * or / by a constant)" % k)
+    co, c0 = aff
+    js = sorted(co)
+    return np.asarray(js, dtype=np.int64), np.asarray([co[j] for j in js], dtype=np.float64), c0 + d.obj_const
+
+
+def fuse_problems(problems):
+    """Block-diagonal union of independent problems (Problem tuples of NLPDescriptions, any mix of separable and tape rows):
+    rows instance after instance, columns shifted by each instance's column offset, tapes copied with their VAR arguments
+    shifted.  Every objective must be linear; it enters the fused :Min objective as LIN atoms (negated for a :Max instance).
+    Returns (Problem, col_offsets[len + 1], objinfo) with objinfo[k] = (cols, coefs, constant) of instance k's objective in
+    ITS own sense and local columns: objval_k = coefs . x_k[cols] + constant."""
+    problems = list(problems)
+    if not problems:
+        raise ValueError("fuse_problems: no problems")
+    ds = []
+    for k, p in enumerate(problems):
+        d = p.d
+        if isinstance(d, CallbackNLP) or np.any(d.row_kind == L.ROW_HOST) or d.obj_kind == L.ROW_HOST:
+            raise ValueError("problem %d: host-evaluated rows or objective (CallbackNLP) cannot be fused" % k)
+        if p.sense not in ("Min", "Max"):
+            raise ValueError("problem %d: sense must be 'Min' or 'Max'" % k)
+        if d.num_var != int(p.num_var) or d.num_constr != int(p.num_constr):
+            raise ValueError("problem %d: num_var / num_constr do not match the description" % k)
+        ds.append(d)
+    offs = np.concatenate([[0], np.cumsum([d.num_var for d in ds])]).astype(np.int64)
+    eoff = np.concatenate([[0], np.cumsum([len(d.col) for d in ds])]).astype(np.int64)
+    toff = np.concatenate([[0], np.cumsum([len(d.tape_op) for d in ds])]).astype(np.int64)
+    rowptr = np.concatenate([[0]] + [d.rowptr[1:] + e for d, e in zip(ds, eoff)]).astype(np.int64)
+    tape_ptr = np.concatenate([[0]] + [d.tape_ptr[1:] + t for d, t in zip(ds, toff)]).astype(np.int64)
+    col = np.concatenate([d.col + np.int32(o) for d, o in zip(ds, offs)]).astype(np.int32)
+    targs = []
+    for d, o in zip(ds, offs):
+        a = d.tape_arg.copy()
+        isvar = d.tape_op == L.OP_VAR
+        a[isvar] = a[isvar] + float(o)                                  # every other argument bit for bit
+        targs.append(a)
+    info, ocol, op0, oconst = [], [], [], 0.0
+    for k, (p, d, o) in enumerate(zip(problems, ds, offs)):
+        cols, coefs, c0 = _linear_objective(d, k)
+        info.append((cols, coefs, float(c0)))
+        sgn = -1.0 if p.sense == "Max" else 1.0
+        ocol.append(cols + o); op0.append(sgn * coefs); oconst += sgn * c0
+    cat = np.concatenate
+    fused = NLPDescription(
+        int(offs[-1]), rowptr, col, cat([d.row_kind for d in ds]), cat([d.row_linear for d in ds]), cat([d.rconst for d in ds]),
+        cat([d.atom_kind for d in ds]), cat([d.p0 for d in ds]), cat([d.p1 for d in ds]),
+        tape_ptr, cat([d.tape_op for d in ds]), cat(targs),
+        obj_linear=True, obj_kind=L.ROW_SEP, obj_col=cat(ocol).astype(np.int32), obj_atom_kind=np.zeros(int(sum(len(c) for c in ocol))),
+        obj_p0=cat(op0), obj_p1=np.zeros(int(sum(len(c) for c in ocol))), obj_const=oconst)
+    f64 = lambda attr: cat([np.asarray(getattr(p, attr), dtype=np.float64).reshape(-1) for p in problems])
+    big = Problem(fused.num_var, fused.num_constr, f64("l_var"), f64("u_var"), f64("l_constr"), f64("u_constr"), "Min", fused)
+    return big, offs, info
