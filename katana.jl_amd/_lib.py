@@ -11,6 +11,7 @@ STATUS_NONE, STATUS_OPTIMAL, STATUS_UNBOUNDED, STATUS_INFEASIBLE, STATUS_USERLIM
 MIN, MAX = 0, 1
 ROW_SEP, ROW_TAPE, ROW_HOST = 0, 1, 2
 ATOM_LIN, ATOM_QUAD, ATOM_EXP, ATOM_NEGLOG = 0, 1, 2, 3
+CUT_KELLEY, CUT_SUPPORTING = 0, 1          # ktn_params.cut_algo
 (OP_CONST, OP_VAR, OP_ADD, OP_SUB, OP_MUL, OP_DIV, OP_NEG, OP_POWC, OP_EXP, OP_LOG, OP_SQRT, OP_SIN,
  OP_COS) = range(13)
 
@@ -26,7 +27,8 @@ class KtnParams(C.Structure):
                 ("lp_dual_inherit", c_i32), ("profile", c_i32), ("purge_age", c_i32), ("purge_margin", c_f64),
                 ("purge_min_frac", c_f64), ("purge_min_rows", c_i64), ("lp_dense_after", c_i32), ("cut_cap_factor", c_f64), ("cut_cap_min", c_i64), ("lp_stag_factor", c_f64),
                 ("lp_ruiz_warm", c_i32), ("lp_tiled_nnz", c_i64), ("lp_near_check", c_i32), ("dedupe_eps", c_f64), ("polish_factor", c_f64), ("polish_max_var", c_i32), ("polish_max_iter", c_i32),
-                ("epi_shift", c_i32), ("obj_cert_tol", c_f64), ("lp_mid_max_var", c_i32)]
+                ("epi_shift", c_i32), ("obj_cert_tol", c_f64), ("lp_mid_max_var", c_i32),
+                ("cut_algo", c_i32), ("esh_root_iters", c_i32), ("esh_root_tol", c_f64), ("esh_interior_iters", c_i32)]
 
 
 class KtnNlpDesc(C.Structure):
@@ -72,6 +74,8 @@ PROTOTYPES = {
     "ktn_numiters": (c_i64, [C.c_void_p]),
     "ktn_numcuts": (c_i64, [C.c_void_p]),
     "ktn_setwarmstart": (c_i32, [C.c_void_p, P(c_f64), c_i64]),
+    "ktn_set_interior_point": (c_i32, [C.c_void_p, P(c_f64), c_i64]),
+    "ktn_get_interior_point": (c_i32, [C.c_void_p, P(c_f64), c_i64, P(c_i32)]),
     "ktn_sep_precompute": (c_i32, [C.c_void_p, P(c_f64), c_i64]),
     "ktn_sep_num_constr": (c_i64, [C.c_void_p]),
     "ktn_sep_jac_nnz": (c_i64, [C.c_void_p]),
@@ -103,6 +107,7 @@ PROTOTYPES = {
     "ktn_set_cut_exchange": (c_i32, [C.c_void_p, C.c_void_p, C.c_void_p, c_i64]),
     "ktn_dist_release_ipc": (c_i32, [C.c_void_p]),
     "ktn_last_sweep_slots": (c_i32, [C.c_void_p, P(c_i64), c_i64, P(c_i64)]),
+    "ktn_last_sweep_lambdas": (c_i32, [C.c_void_p, P(c_f64), c_i64, P(c_i64)]),
     "ktn_lp_append_rows_nl": (c_i32, [C.c_void_p, c_i64, P(c_i64), P(c_i32), P(c_f64), P(c_f64), P(c_f64), P(c_i64)]),
     "ktn_set_blocks": (c_i32, [C.c_void_p, c_i64, P(c_i64)]),
     "ktn_optimize_blocks": (c_i32, [C.c_void_p, c_i32]),

@@ -49,6 +49,7 @@ void ktn_default_params(ktn_params* p) {
     p->epi_shift = 1;
     p->obj_cert_tol = 1e-6;
     p->lp_mid_max_var = 512;
+    p->cut_algo = KTN_CUT_KELLEY; p->esh_root_iters = 20; p->esh_root_tol = 0.1; p->esh_interior_iters = 50;
 }
 
 int ktn_create(const ktn_params* p, ktn_handle* out) {
@@ -123,6 +124,39 @@ int ktn_setwarmstart(ktn_handle h, const double* x, int64_t n) {   // src/model.
     return (h && h->eng) ? KTN_OK : KTN_E_INVALID;
 }
 
+// ---- supporting-hyperplane cuts: the interior point
+int ktn_set_interior_point(ktn_handle h, const double* x, int64_t n) {
+    KTN_TRY(h, {
+        Engine* e = h->eng;
+        KTN_REQUIRE(e->loaded, "ktn_set_interior_point: after loadproblem");
+        if (!x) {
+            e->xint_given = false;
+            e->h_xint.clear();
+        } else {
+            KTN_REQUIRE(n == e->n0, "ktn_set_interior_point: n must be the problem's num_var");
+            e->h_xint.assign(x, x + n);
+            e->xint_given = true;
+        }
+        e->esh_ready = false;
+        e->xint_found = 0;
+        return KTN_OK;
+    })
+}
+int ktn_get_interior_point(ktn_handle h, double* x_out, int64_t n, int32_t* found) {
+    KTN_TRY(h, {
+        Engine* e = h->eng;
+        KTN_REQUIRE(e->loaded && found, "ktn_get_interior_point: after loadproblem, found != NULL");
+        if (e->prm.cut_algo == KTN_CUT_SUPPORTING && !e->esh_ready) e->esh_prepare();
+        const bool have = e->prm.cut_algo == KTN_CUT_SUPPORTING ? e->xint_found != 0 : e->xint_given;
+        *found = have ? 1 : 0;
+        if (have && x_out) {
+            KTN_REQUIRE(n >= e->n0, "ktn_get_interior_point: buffer too small");
+            std::memcpy(x_out, e->h_xint.data(), (size_t)e->n0 * sizeof(double));
+        }
+        return KTN_OK;
+    })
+}
+
 // ---- separator API
 int ktn_sep_precompute(ktn_handle h, const double* xstar, int64_t n) {
     KTN_TRY(h, {
@@ -183,10 +217,15 @@ int ktn_sep_gencut(ktn_handle h, int64_t i, int32_t* cols, double* coefs, int64_
         KTN_REQUIRE(e->have_precompute && i >= 0 && i < e->m_ext && nnz, "gencut: bad row or no precompute!");
         const int64_t beg = e->h_rowptr[i], len = e->h_rowptr[i + 1] - beg;
         KTN_REQUIRE(*nnz >= len, "gencut: output capacity too small");
+        // (cut_algo = KTN_CUT_SUPPORTING: the row's cut moves to its boundary point on the segment from x_int, as the reference's
+        //  gencut calls sep.algo; the state of the precompute is restored afterwards)
+        const bool moved = e->prm.cut_algo == KTN_CUT_SUPPORTING && e->esh_gencut_row(i, coefs, constant);
         std::memcpy(cols, e->h_col.data() + beg, (size_t)len * sizeof(int32_t));
-        if (len) KTN_HIP(hipMemcpyAsync(coefs, e->d_jac.p + beg, (size_t)len * 8, hipMemcpyDeviceToHost, e->stream));
-        KTN_HIP(hipMemcpyAsync(constant, e->d_bconst.p + i, 8, hipMemcpyDeviceToHost, e->stream));
-        e->sync();
+        if (!moved) {
+            if (len) KTN_HIP(hipMemcpyAsync(coefs, e->d_jac.p + beg, (size_t)len * 8, hipMemcpyDeviceToHost, e->stream));
+            KTN_HIP(hipMemcpyAsync(constant, e->d_bconst.p + i, 8, hipMemcpyDeviceToHost, e->stream));
+            e->sync();
+        }
         *nnz = len;
         return KTN_OK;
     })
@@ -385,11 +424,25 @@ int ktn_last_sweep_slots(ktn_handle h, int64_t* slots, int64_t cap, int64_t* cou
         return KTN_OK;
     })
 }
+int ktn_last_sweep_lambdas(ktn_handle h, double* lam, int64_t cap, int64_t* count) {
+    KTN_TRY(h, {
+        Engine* e = h->eng;
+        KTN_REQUIRE(e->loaded && count, "last_sweep_lambdas: bad arguments");
+        *count = e->last_sweep_cuts;
+        if (lam && e->last_sweep_cuts > 0) {
+            KTN_REQUIRE(cap >= e->last_sweep_cuts, "last_sweep_lambdas: buffer too small");
+            e->esh_last_lambdas(lam);
+        }
+        return KTN_OK;
+    })
+}
 int ktn_set_cut_exchange(ktn_handle h, ktn_exchange_cb cb, void* user, int64_t first_nl_id) {
     KTN_TRY(h, {
         Engine* e = h->eng;
         KTN_REQUIRE(e->loaded && first_nl_id >= 0, "ktn_set_cut_exchange: after loadproblem");
         KTN_REQUIRE(cb == nullptr || e->glists, "ktn_set_cut_exchange: enable the global cut lists first (ktn_lp_enable_global_lists)");
+        if (cb != nullptr && e->prm.cut_algo == KTN_CUT_SUPPORTING)
+            throw ktn::Error(KTN_E_UNSUPPORTED, "ktn_set_cut_exchange: not available with cut_algo = KTN_CUT_SUPPORTING");
         e->exch_cb = cb; e->exch_user = user; e->exch_lo = first_nl_id;
         return KTN_OK;
     })
@@ -432,6 +485,8 @@ int ktn_optimize_blocks(ktn_handle h, int32_t cut_capacity) {
     KTN_TRY(h, {
         Engine* e = h->eng;
         KTN_REQUIRE(e->loaded && e->n_blocks > 0, "ktn_optimize_blocks: after ktn_loadproblem and ktn_set_blocks");
+        if (e->prm.cut_algo == KTN_CUT_SUPPORTING)
+            throw ktn::Error(KTN_E_UNSUPPORTED, "ktn_optimize_blocks: not available with cut_algo = KTN_CUT_SUPPORTING");
         if (e->M != e->M_base || e->iter != 0) e->reset();
         if (e->optimize_blocks_device(cut_capacity > 0 ? cut_capacity : 12)) return e->status;
         // an instance did not finish on the device (or the problem does not qualify): the ordinary loop, from the loaded state

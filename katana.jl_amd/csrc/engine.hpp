@@ -355,6 +355,8 @@ struct Engine {
 
     explicit Engine(const ktn_params& p) : prm(p) {
         dev.from_env();
+        if (prm.cut_algo != KTN_CUT_KELLEY && prm.cut_algo != KTN_CUT_SUPPORTING)
+            throw Error(KTN_E_INVALID, "cut_algo must be KTN_CUT_KELLEY (0) or KTN_CUT_SUPPORTING (1)");
         int ndev = 0;
         if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
             throw Error(KTN_E_NODEVICE, "no HIP device visible: the Katana HIP engine has no CPU path");
@@ -382,6 +384,7 @@ struct Engine {
         d_anynf.resize(4, stream);
     }
     ~Engine() {
+        delete child;
         if (dist.comm) (void)ncclCommDestroy(dist.comm);
         ipc_release();
         for (auto e : ev_pool) (void)hipEventDestroy(e);
@@ -508,6 +511,44 @@ struct Engine {
     DBuf<uint16_t> d_sbck, d_sbrow;
     DBuf<double2> d_sbpp;
     DBuf<int64_t> d_sbseg;
+
+    // ================================================================ supporting hyperplanes (esh.hip) ===
+    // cut_algo == KTN_CUT_SUPPORTING: every selected violated row that participates is cut at the point
+    // x_int + lambda_i (x* - x_int) where it reaches its bound.  Participating: separable or tape program, exactly one finite side,
+    // not the epigraph row (h_esh_side: +1 upper side, -1 lower side, 0 not participating), and g_i(x_int) at least 10 f_tol
+    // inside its bound (d_esh_sig: the side, or 0).
+    std::vector<int8_t> h_esh_side;
+    DBuf<int8_t> d_esh_sig;
+    DBuf<double> d_xint, d_lam;
+    DBuf<int32_t> d_tape_nlslots;              // NL slot of each tape NL row (d_taperows_nl)
+    DBuf<unsigned long long> d_esh_cnt;         // [0] rows cut at x_b, [1] Newton / bisection passes
+    std::vector<double> h_xint;                 // the point in use (n0 entries)
+    bool xint_given = false, esh_ready = false;
+    int xint_found = 0;
+    int64_t esh_n_part = 0;
+    // the auxiliary min-max problem (variables (x, s), min s, participating rows g_i(x) -+ s against their bound), built at load
+    struct EshAux {
+        int64_t n = 0, m = 0;
+        std::vector<double> lv, uv, lc, uc, rconst, p0, p1, targ, op0, op1;
+        std::vector<int64_t> rowptr, tptr;
+        std::vector<int32_t> col, top, ocol;
+        std::vector<uint8_t> kind, lin, akind, okind;
+        bool has_tape = false;
+    } aux;
+    Engine* child = nullptr;
+    void esh_build_aux(const double* l_var, const double* u_var, const double* l_constr, const double* u_constr, const ktn_nlp_desc* d);
+    void esh_prepare();                         // find (or take) x_int and evaluate the rows there, once per loaded problem
+    void esh_find_interior();
+    // root search of the selected violated rows (after the deepest-cut selection, before k_compact) and the cut emission
+    bool esh_on = false;                        // this sweep's search ran (its cuts go through k_emit_esh)
+    int64_t esh_last_rows = 0;
+    void esh_search(const double* d_x, double f_tol);
+    void esh_emit(const double* d_x, int64_t V);
+    // ktn_sep_gencut for one row at the point of the last precompute
+    DBuf<int32_t> d_esh_one;
+    DBuf<int64_t> d_esh_slot;
+    bool esh_gencut_row(int64_t i, double* coefs, double* constant);
+    void esh_last_lambdas(double* out);
 
     // ================================================================ LP ============
     void rebuild_csc();

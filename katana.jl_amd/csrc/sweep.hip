@@ -241,6 +241,7 @@ void Engine::loadproblem(int64_t num_var, int64_t num_constr, const double* l_va
         if (dist.rank == 0) h_nlrows.push_back((int32_t)m0);      // row-sharded: the epigraph row belongs to rank 0
     }
     m_nl = (int64_t)h_nlrows.size();
+    esh_build_aux(l_var, u_var, l_constr, u_constr, d);         // (esh.hip; cut_algo = KTN_CUT_SUPPORTING only)
     has_inf_bound = false;
     for (int64_t j = 0; j < n_lp; ++j)
         if (!std::isfinite(lv[j]) || !std::isfinite(uv[j])) has_inf_bound = true;
@@ -681,6 +682,7 @@ void Engine::sweep(const double* d_x, double f_tol, int64_t* nviol_out, double* 
     last_sweep_cuts = 0;
     stats["sweeps"] += 1.0;
     if (m_nl == 0) return;
+    if (prm.cut_algo == KTN_CUT_SUPPORTING && !esh_ready) esh_prepare();
     NlpDev P = nlp_view();
     SweepOut O = sweep_view();
     KTN_HIP(hipMemsetAsync(d_scal.p, 0, sizeof(double), stream));
@@ -794,6 +796,7 @@ hipExtLaunchKernelGGL((k_sep_eval_blk<G, BC, BS, U>), dim3((unsigned)(num_cus * 
         return;
     }
     if (V > 0) {
+        if (prm.cut_algo == KTN_CUT_SUPPORTING) esh_search(d_x, f_tol);     // (esh.hip: moves the selected rows' cuts to x_b)
         lp_rowptr.resize((size_t)(M + V + 1), stream);
         lp_lo.resize((size_t)(M + V), stream);
         lp_hi.resize((size_t)(M + V), stream);
@@ -807,8 +810,9 @@ hipExtLaunchKernelGGL((k_sep_eval_blk<G, BC, BS, U>), dim3((unsigned)(num_cus * 
         LpRows L = lp_view();
         LAUNCH_1(k_compact, m_nl, stream, P, d_nlrows.p, m_nl, d_flag.p, d_rank.p, d_cntscan.p, d_bconst.p, M, NNZ, L,
                  d_violslots.p, d_lastcut.p, d_cutprev.p, (int)(prm.lp_dual_inherit && !glists));
-        LAUNCH_G(grp_sweep, k_emit, V, stream, P, d_nlrows.p, d_violslots.p, V, d_x, d_jac.p, d_maxc.p,
-                 prm.cut_coef_rng, 1, M, L);
+        if (prm.cut_algo == KTN_CUT_SUPPORTING) esh_emit(d_x, V);
+        else LAUNCH_G(grp_sweep, k_emit, V, stream, P, d_nlrows.p, d_violslots.p, V, d_x, d_jac.p, d_maxc.p,
+                      prm.cut_coef_rng, 1, M, L);
         check_launch();
         M += V;
         NNZ += nnzV;

@@ -20,7 +20,7 @@ using JuMP
 import ..KatanaSolver, ..AbstractKatanaSeparator, ..EpigraphNLPEvaluator          # src/solver.jl:6, src/separators.jl:8, src/nlpeval.jl:6
 import ..initialize!, ..precompute!, ..gencut, ..isconstrsat                      # the separator API, src/separators.jl:23-53
 
-export KatanaHipSeparator
+export KatanaHipSeparator, supporting_hyperplane_cut
 
 const LIB = get(ENV, "KATANA_HIP_LIB", joinpath(dirname(@__FILE__), "..", "libkatana_hip.so"))
 
@@ -39,6 +39,7 @@ const KTN_OP_SQRT  = Int32(10)
 const KTN_OP_SIN   = Int32(11)
 const KTN_OP_COS   = Int32(12)
 const KTN_ROW_SEP, KTN_ROW_TAPE, KTN_ROW_HOST = UInt8(0), UInt8(1), UInt8(2)
+const KTN_CUT_KELLEY, KTN_CUT_SUPPORTING = Int32(0), Int32(1)                     # ktn_params.cut_algo
 const STATUS = [:None, :Optimal, :Unbounded, :Infeasible, :UserLimit, :Error]     # KTN_STATUS_* + 1
 
 # :call heads of a MathProgBase expression graph the device tape interpreter evaluates
@@ -56,6 +57,7 @@ struct KtnParams
     lp_dense_after::Int32; cut_cap_factor::Cdouble; cut_cap_min::Int64; lp_stag_factor::Cdouble
     lp_ruiz_warm::Int32; lp_tiled_nnz::Int64; lp_near_check::Int32; dedupe_eps::Cdouble; polish_factor::Cdouble; polish_max_var::Int32; polish_max_iter::Int32
     epi_shift::Int32; obj_cert_tol::Cdouble; lp_mid_max_var::Int32
+    cut_algo::Int32; esh_root_iters::Int32; esh_root_tol::Cdouble; esh_interior_iters::Int32
 end
 
 struct KtnNlpDesc
@@ -284,6 +286,17 @@ function check(m::KatanaHipModel, code)
     code
 end
 
+# The cut generator of the reference's KatanaFirstOrderSeparator(algo) slot (src/separators.jl:73-76) that selects supporting
+# hyperplanes (cut_algo = KTN_CUT_SUPPORTING): KatanaSolver(lp, separator = KatanaFirstOrderSeparator(supporting_hyperplane_cut)).
+# The engine's device search serves it; the reference's own host loop cannot call it.
+supporting_hyperplane_cut(sep, a, b, i) = error("supporting_hyperplane_cut is served by the HIP engine (KatanaHipModel)")
+
+# cut_algo of a KatanaSolver: the `algo` of its separator, when that is a KatanaFirstOrderSeparator
+function cut_algo_of(s)
+    sep = s.model_params.separator
+    (isdefined(sep, :algo) && sep.algo === supporting_hyperplane_cut) ? KTN_CUT_SUPPORTING : KTN_CUT_KELLEY
+end
+
 # `s` is the reference's KatanaSolver (src/solver.jl:6-10): lp_solver is ignored (the LP runs on the GPU),
 # features and model_params are honoured (src/model.jl:46-58)
 function KatanaHipModel(s)
@@ -300,7 +313,8 @@ function KatanaHipModel(s)
                     d.lp_gap_floor, d.lp_gap_cap, d.lp_dual_inherit, d.profile, d.purge_age, d.purge_margin,
                     d.purge_min_frac, d.purge_min_rows, d.lp_dense_after, d.cut_cap_factor, d.cut_cap_min,
                     d.lp_stag_factor, d.lp_ruiz_warm, d.lp_tiled_nnz, d.lp_near_check, d.dedupe_eps, d.polish_factor, d.polish_max_var, d.polish_max_iter,
-                    d.epi_shift, d.obj_cert_tol, d.lp_mid_max_var)
+                    d.epi_shift, d.obj_cert_tol, d.lp_mid_max_var,
+                    cut_algo_of(s), d.esh_root_iters, d.esh_root_tol, d.esh_interior_iters)
     h = Ref{Ptr{Void}}(C_NULL)
     code = ccall((:ktn_create, LIB), Cint, (Ref{KtnParams}, Ref{Ptr{Void}}), Ref(prm), h)
     code == 0 || error("ktn_create failed ($code): no MI355X visible? the engine has no CPU path")

@@ -11,6 +11,17 @@ from . import _lib as L
 STATUS_SYMBOLS = {L.STATUS_NONE: "None", L.STATUS_OPTIMAL: "Optimal", L.STATUS_UNBOUNDED: "Unbounded",
                   L.STATUS_INFEASIBLE: "Infeasible", L.STATUS_USERLIMIT: "UserLimit", L.STATUS_ERROR: "Error"}
 _SUPPORTED_FEATURES = ("VisData",)   # src/solver.jl:31-32
+# the cut generator of KatanaFirstOrderSeparator(algo) (src/separators.jl:73-76): ktn_params.cut_algo
+CUT_ALGOS = {"kelley": L.CUT_KELLEY, "linear_oa_cut": L.CUT_KELLEY,
+             "supporting_hyperplane": L.CUT_SUPPORTING, "supporting_hyperplane_cut": L.CUT_SUPPORTING}
+
+
+def _cut_algo_code(cut_algo):
+    if isinstance(cut_algo, str):
+        if cut_algo not in CUT_ALGOS:
+            raise ValueError("unknown cut_algo %r (one of %s)" % (cut_algo, ", ".join(sorted(CUT_ALGOS))))
+        return CUT_ALGOS[cut_algo]
+    return int(cut_algo)
 
 
 def _f64(a):
@@ -27,10 +38,13 @@ class KatanaSolver:
 
     `lp_solver` is accepted for call-site compatibility (`KatanaSolver(GLPKSolverLP(), ...)`,
     test/runtests.jl:24) and ignored: the LP is solved on the GPU.  Extra keywords `lp_*`,
-    `device`, `profile` reach the GPU LP (ktn_params)."""
+    `device`, `profile` reach the GPU LP (ktn_params).
+
+    `cut_algo` picks the separator's cut generator: "kelley" (the reference's linear_oa_cut, the default) or
+    "supporting_hyperplane" (cut at the boundary point between an interior point and x*), or the ktn_params code."""
 
     def __init__(self, lp_solver=None, separator=None, features=(), f_tol=1e-6, cut_coef_rng=1e9, log_level=10,
-                 iter_cap=10000, obj_eps=-1.0, **gpu_options):
+                 iter_cap=10000, obj_eps=-1.0, cut_algo="kelley", **gpu_options):
         self.lp_solver = lp_solver
         self.features = list(features)
         for f in self.features:
@@ -40,6 +54,7 @@ class KatanaSolver:
         self.model_params = dict(f_tol=float(f_tol), cut_coef_rng=float(cut_coef_rng), log_level=int(log_level),
                                  iter_cap=int(iter_cap), obj_eps=float(obj_eps))
         self.gpu_options = dict(gpu_options)
+        self.gpu_options["cut_algo"] = _cut_algo_code(cut_algo)
 
 
 def NonlinearModel(s):
@@ -73,6 +88,7 @@ class KatanaNonlinearModel:
         self._desc = None
         self.num_var = 0
         self.num_constr = 0
+        self._n0 = 0
 
     def __del__(self):
         try:
@@ -94,6 +110,7 @@ class KatanaNonlinearModel:
                                                    _p(u_constr), sense_code, C.byref(cd)))
         self.num_var = int(self._lib.ktn_get_num_var(self._h))
         self.num_constr = int(self._lib.ktn_sep_num_constr(self._h))
+        self._n0 = int(num_var)
 
     # ---- MathProgBase.optimize!  src/model.jl:219-319 ---------------------------------------
     def optimize(self):
@@ -138,6 +155,23 @@ class KatanaNonlinearModel:
         x = _f64(x)
         self._lib.ktn_setwarmstart(self._h, _p(x), len(x))
         return np.zeros(len(x))
+
+    # ---- supporting-hyperplane cuts: the interior point (ktn_set_interior_point / ktn_get_interior_point) ----
+    def set_interior_point(self, x):
+        """hand the engine an interior point x_int (the problem's own num_var entries); None clears it"""
+        if x is None:
+            L.check(self._h, self._lib.ktn_set_interior_point(self._h, C.POINTER(C.c_double)(), 0))
+            return
+        x = _f64(x)
+        L.check(self._h, self._lib.ktn_set_interior_point(self._h, _p(x), len(x)))
+
+    def interior_point(self):
+        """the interior point in use (found by the engine or the caller's), or None when there is none"""
+        n = self._n0
+        x = np.zeros(max(n, 1))
+        found = C.c_int32(0)
+        L.check(self._h, self._lib.ktn_get_interior_point(self._h, _p(x), len(x), C.byref(found)))
+        return x[:n].copy() if found.value else None
 
     def set_blocks(self, col_offsets):
         """throughput mode: the loaded problem is block-diagonal with these column offsets (ktn_set_blocks)"""
@@ -256,6 +290,16 @@ class KatanaNonlinearModel:
         out = np.zeros(max(int(n.value), 1), dtype=np.int64)
         if n.value:
             L.check(self._h, self._lib.ktn_last_sweep_slots(self._h, _p(out, C.c_int64), len(out), C.byref(n)))
+        return out[:int(n.value)]
+
+    def last_sweep_lambdas(self):
+        """lambda of each cut the last sweep appended (order of last_sweep_slots): the cut was taken at
+        x_int + lambda (x* - x_int); 1 = Kelley's cut at x*"""
+        n = C.c_int64(0)
+        L.check(self._h, self._lib.ktn_last_sweep_lambdas(self._h, C.POINTER(C.c_double)(), 0, C.byref(n)))
+        out = np.ones(max(int(n.value), 1))
+        if n.value:
+            L.check(self._h, self._lib.ktn_last_sweep_lambdas(self._h, _p(out), len(out), C.byref(n)))
         return out[:int(n.value)]
 
     def lp_pdhg_raw(self, x0, y0, eta, omega, iters):
