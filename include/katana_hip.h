@@ -337,6 +337,14 @@ int ktn_get_lp_sol(ktn_handle h, int64_t k, double* x_out, int64_t n);
 
 /* ---- statistics (not in the reference: measurement hooks) ----
  * names: "lp_time_s" "sep_time_s" "pdhg_iters" "lp_solves" "lp_restarts" "sweeps"
+ * which form of the separable evaluation the loaded problem takes (written by ktn_loadproblem, read-only):
+ *        "sweep_group"          lanes per row G of the row kernels (8, 16, 32, 64)
+ *        "sweep_rows_per_group" rows per lane group R of the sweep's row kernel (1, 2, 4); 0 when the sweep is
+ *                               column-blocked or batch-blocked
+ *        "sweep_blocked"        1 when the sweep is the column-blocked one (long sorted rows)
+ *        "sweep_batched"        1 when the sweep is the batch-blocked one (many short rows)
+ *        "precompute_multirow"  1 when precompute! runs four rows per lane group
+ *        "sep_long_rows"        rows beyond 8 192 entries, evaluated one workgroup per row
  * with params.profile = 1, per hot kernel K in {kx, ky, sweep_eval}:
  *        "K_time_s" "K_launches" "K_bytes"  from the start/stop hipEvents of hipExtLaunchKernelGGL
  *        on the engine's own stream (dispatch begin/end, as rocprofv3 --kernel-trace reports) */

@@ -130,6 +130,8 @@ struct Engine {
     int64_t m_nl = 0, n_tape_nl = 0;
     int64_t m_nl_global = 0;       // NL rows over all ranks of a row-sharded LP (== m_nl otherwise): decisions that steer collectives use it
     int grp_sweep = 32;
+    int sweep_rows_per_group = 1;  // R of k_sep_sweep (1: k_sep_eval); fixed at load from m_nl, G and the CU count
+    bool pre_multirow = false;     // precompute_all runs k_sep_sweep<G, 4, true>; fixed at load from m_ext, G and the CU count
 
     // ---- device NLP ----
     DBuf<int64_t> d_rowptr, d_nodeptr;

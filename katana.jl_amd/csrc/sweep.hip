@@ -438,6 +438,19 @@ void Engine::loadproblem(int64_t num_var, int64_t num_constr, const double* l_va
         }
         stats["sweep_batched"] = sb_on ? 1.0 : 0.0;
     }
+    // Which form of the row kernel the sweep and precompute! take depends on the shape alone: many short rows get several rows
+    // per lane group (k_sep_sweep) once one row per group would make several times the resident wavefronts
+    {
+        const int64_t resident = (int64_t)num_cus * 32;
+        const int64_t waves_nl = m_nl * grp_sweep / 64, waves_ext = m_ext * grp_sweep / 64;
+        sweep_rows_per_group = dev.sweep_rows > 0 ? (dev.sweep_rows >= 4 ? 4 : dev.sweep_rows >= 2 ? 2 : 1)
+                                                  : (waves_nl >= 16 * resident ? 4 : waves_nl >= 8 * resident ? 2 : 1);
+        pre_multirow = waves_ext >= 16 * resident;
+        stats["sweep_group"] = (double)grp_sweep;
+        stats["sweep_rows_per_group"] = (blk_on || sb_on) ? 0.0 : (double)sweep_rows_per_group;
+        stats["sweep_blocked"] = blk_on ? 1.0 : 0.0;
+        stats["precompute_multirow"] = pre_multirow ? 1.0 : 0.0;
+    }
     // algorithmic bytes of one evaluation pass over the NL rows (DESIGN.md "sweep bytes")
     sweep_bytes = (double)nnz_nl * (4 + 16) + 8.0 * (m_nl + 1) + 8.0 * n_lp + 8.0 * 4 * m_nl + 16.0 * m_nl;
     const size_t mm = (size_t)std::max<int64_t>(m_ext, 1);
@@ -648,9 +661,8 @@ void Engine::precompute_all(const double* d_x) {
     NlpDev P = nlp_view();
     SweepOut O = sweep_view();
     // many short rows: the R-rows-per-lane-group form of the sweep with the Jacobian store (same sums, same bits); the
-    // selection is the sweep's: once one row per group would make several times the resident wavefronts
-    const int64_t waves1 = m_ext * grp_sweep / 64, resident = (int64_t)num_cus * 32;
-    if (waves1 >= 16 * resident) {
+    // selection is the sweep's, made once in loadproblem (pre_multirow)
+    if (pre_multirow) {
 #define KTN_PRE_LAUNCH(G) hipLaunchKernelGGL((k_sep_sweep<G, 4, true>), dim3(ceil_div(ceil_div(m_ext, (int64_t)4) * G, kBlock)), dim3(kBlock), 0, stream, P, d_allrows.p, m_ext, d_x, 0.0, O)
         switch (grp_sweep) {
             case 8: KTN_PRE_LAUNCH(8); break;
@@ -708,10 +720,9 @@ hipExtLaunchKernelGGL((k_sep_eval_blk<G, BC, BS, U>), dim3((unsigned)(num_cus * 
                               d_part.p, f_tol, O);
     } else {
         // many short rows: several rows per lane group (k_sep_sweep) once one row per group would make more wavefronts
-        // than the chip holds several times over; small sweeps keep one row per group and all the parallelism
-        const int rows_env = dev.sweep_rows;
-        const int64_t waves1 = m_nl * grp_sweep / 64, resident = (int64_t)num_cus * 32;
-        const int R = rows_env > 0 ? rows_env : (waves1 >= 16 * resident ? 4 : waves1 >= 8 * resident ? 2 : 1);
+        // than the chip holds several times over; small sweeps keep one row per group and all the parallelism (the
+        // choice is made once in loadproblem)
+        const int R = sweep_rows_per_group;
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (prm.profile) {
             const size_t ea = ev_get(), eb = ev_get();
