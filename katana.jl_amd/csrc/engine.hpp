@@ -67,6 +67,8 @@ struct DevParams {
     int blk_cfg = -1;              // KTN_BLK_CFG          tuning variant of the column-blocked sweep
     int sweep_blocked = -1;        // KTN_SWEEP_BLOCKED    0 = row kernel instead of the column-blocked sweep
     int sweep_batched = -1;        // KTN_SWEEP_BATCHED    0 = row kernel instead of the batch-blocked sweep for many short rows, 1 = always
+    int tape_classed = -1;         // KTN_TAPE_CLASSED     tape rows by shape class (k_tape_classed): -1 = classes of >= 64 rows, 0 = interpreter for
+                                   //                      every tape row, 1 = every class of >= 2 rows
     int tiled_wg = 2;              // KTN_TILED_WG         workgroups per CU of k_spmv_tiled
     int ecp_power = 20;            // KTN_ECP_POWER        power passes of the device-side batch loop
     int grp_rows = 0, grp_cols = 0;// KTN_GRP_ROWS / COLS  lanes per LP row / column (0 = by average length)
@@ -93,7 +95,7 @@ struct DevParams {
         no_setup_reuse = flag("KTN_NO_SETUP_REUSE"); debug_lp = flag("KTN_DEBUG_LP"); no_packed = flag("KTN_NO_PACKED");
         force_collective = flag("KTN_FORCE_COLLECTIVE");
         sweep_rows = geti("KTN_SWEEP_ROWS", sweep_rows); blk_cfg = geti("KTN_BLK_CFG", blk_cfg); sweep_blocked = geti("KTN_SWEEP_BLOCKED", sweep_blocked);
-        sweep_batched = geti("KTN_SWEEP_BATCHED", sweep_batched);
+        sweep_batched = geti("KTN_SWEEP_BATCHED", sweep_batched); tape_classed = geti("KTN_TAPE_CLASSED", tape_classed);
         tiled_wg = geti("KTN_TILED_WG", tiled_wg); ecp_power = geti("KTN_ECP_POWER", ecp_power);
         grp_rows = geti("KTN_GRP_ROWS", grp_rows); grp_cols = geti("KTN_GRP_COLS", grp_cols); tiled = geti("KTN_TILED", tiled);
         smax_reuse = getd("KTN_SMAX_REUSE", smax_reuse); power_passes = geti("KTN_POWER_PASSES", power_passes);
@@ -161,6 +163,21 @@ struct Engine {
     DBuf<SepPartial> d_part;
     DBuf<double> d_rconst, d_lb, d_ub, d_nodec, d_nodeval, d_nodeadj;
     DBuf<int32_t> d_nlrows, d_allrows, d_taperows_all, d_taperows_nl;
+    // tape rows by shape class (tape_classes.hpp; built by build_tape_classes at load).  A class holds NL rows only or none: the
+    // sweep launches the classes of NL rows, precompute_all all of them; d_tapeint_*: the rows left to k_tape_eval
+    int64_t tc_rows = 0, tc_rows_nl = 0;
+    struct TcLaunch { int64_t wave0, nwaves; size_t lds; bool nl; };      // one launch: the classes of one size bucket, NL rows or not
+    std::vector<TcLaunch> tc_launches;
+    bool tc_lds_set = false;
+    void launch_tape_classed(bool nl_only, const int32_t* mslot, const double* d_x, double f_tol);
+    double tape_bytes = 0.0;                   // algorithmic bytes of one evaluation of the NL tape rows
+    DBuf<int32_t> d_tapeint_all, d_tapeint_nl, d_tc_wavecls, d_tc_wavefirst, d_tc_op, d_tc_a, d_tc_b, d_tc_scol, d_tc_mrow, d_tc_mslot;
+    DBuf<double> d_tc_c, d_tc_cst;
+    DBuf<TapeClassMeta> d_tc_meta;
+    DBuf<uint8_t> d_tc_rowflag;                // [m_ext] 1: the row is evaluated by k_tape_classed (k_gj_stats skips it)
+    void build_tape_classes(const std::vector<int64_t>& nodeptr, const std::vector<int32_t>& nop, const std::vector<int32_t>& na,
+                            const std::vector<int32_t>& nb, const std::vector<double>& nc, const std::vector<int32_t>& tape_all);
+    TapeClassDev tape_class_view();
     // sweep state
     DBuf<double> d_g, d_jac, d_bconst, d_maxc, d_xs, d_ray, d_scal;
     DBuf<int32_t> d_nonfin, d_violslots, d_anynf;
@@ -457,7 +474,7 @@ struct Engine {
     // profile mode: the timed launches go through hipExtLaunchKernelGGL, whose start/stop events
     // carry the dispatch's own begin/end timestamps (what rocprofv3 --kernel-trace reports)
     void ev_flush() {   // stream must be synchronised
-        static const char* names[4] = {"kx", "ky", "sweep_eval", "allreduce"};
+        static const char* names[5] = {"kx", "ky", "sweep_eval", "allreduce", "tape_eval"};
         for (auto& r : ev_recs) {
             float ms = 0.f;
             if (hipEventElapsedTime(&ms, ev_pool[r.a], ev_pool[r.b]) == hipSuccess) {

@@ -657,9 +657,55 @@ static __global__ __launch_bounds__(kBlock) void k_depth_reflag(int64_t m_nl, co
     if (flag[s] && keys[s] < thr) { flag[s] = 0; cnt[s] = 0; }
 }
 
-// precompute! of ONE tape row by one thread: forward sweep then reverse sweep over the row's expression DAG; returns
-// g = value + rconst and writes the row's Jacobian entries into jac (indexed like the structure).  Derivative conventions
+// Arithmetic of ONE node of a tape row's expression DAG, shared by the row interpreter (tape_row_eval) and the shape-class
+// kernel (tape_classes.hpp k_tape_classed): both compile this text, so a value or a partial rounds the same in either.
+// Forward value of a node with operands (op >= KTN_OP_ADD); a, b: the operands' values, pc(): the POWC exponent.
+template <class PC>
+__device__ __forceinline__ double tape_node_forward(int op, double a, double b, PC&& pc) {
+    double v;
+    switch (op) {
+        case KTN_OP_ADD: v = a + b; break;
+        case KTN_OP_SUB: v = a - b; break;
+        case KTN_OP_MUL: v = a * b; break;
+        case KTN_OP_DIV: v = a / b; break;
+        case KTN_OP_NEG: v = -a; break;
+        case KTN_OP_POWC: v = pow(a, pc()); break;
+        case KTN_OP_EXP: v = exp(a); break;
+        case KTN_OP_LOG: v = log(a); break;
+        case KTN_OP_SQRT: v = sqrt(a); break;
+        case KTN_OP_SIN: v = sin(a); break;
+        default: v = cos(a); break;
+    }
+    return v;
+}
+// Reverse step of node i (op >= KTN_OP_ADD) with adjoint w: adds its contributions to the adjoints of its operands ia (and
+// ibf(), asked for by the binary ops only).  val(k): value of node k; adj(k): reference to the adjoint of node k; pc(): the
+// POWC exponent.  Derivative conventions
 // follow the oracle (oracle/sexpr.py): log' = 1/v, sqrt' = 0.5/sqrt(v), pow: 2 -> 2v, 1 -> 1, else p v^(p-1).
+template <class IDX, class IB, class VAL, class ADJ, class PC>
+__device__ __forceinline__ void tape_node_reverse(int op, double w, IDX i, IDX ia, IB&& ibf, VAL&& val, ADJ&& adj, PC&& pc) {
+    const double a = val(ia);
+    switch (op) {
+        case KTN_OP_ADD: adj(ia) += w; adj(ibf()) += w; break;
+        case KTN_OP_SUB: adj(ia) += w; adj(ibf()) -= w; break;
+        case KTN_OP_MUL: { const IDX ib = ibf(); const double b = val(ib);
+                           adj(ia) += w * b; adj(ib) += w * a; } break;
+        case KTN_OP_DIV: { const IDX ib = ibf(); const double b = val(ib);
+                           adj(ia) += w * (1.0 / b); adj(ib) += w * (-(val(i) / b)); } break;
+        case KTN_OP_NEG: adj(ia) -= w; break;
+        case KTN_OP_POWC: { const double p = pc();
+                            const double d = (p == 2.0) ? 2.0 * a : (p == 1.0 ? 1.0 : p * pow(a, p - 1.0));
+                            adj(ia) += w * d; } break;
+        case KTN_OP_EXP: adj(ia) += w * val(i); break;
+        case KTN_OP_LOG: adj(ia) += w * (1.0 / a); break;
+        case KTN_OP_SQRT: adj(ia) += w * (0.5 / val(i)); break;
+        case KTN_OP_SIN: adj(ia) += w * cos(a); break;
+        default: adj(ia) += w * (-sin(a)); break;
+    }
+}
+
+// precompute! of ONE tape row by one thread: forward sweep then reverse sweep over the row's expression DAG; returns
+// g = value + rconst and writes the row's Jacobian entries into jac (indexed like the structure).
 // XF says how x is read: xat(global column) -- x[col] in k_tape_eval, the workgroup's LDS copy in k_ecp_blocks.
 template <class XF>
 __device__ __forceinline__ double tape_row_eval(const NlpDev& P, int32_t r, XF&& xat, double* jac) {
@@ -673,21 +719,9 @@ __device__ __forceinline__ double tape_row_eval(const NlpDev& P, int32_t r, XF&&
         const double a = (op >= KTN_OP_ADD) ? val[nb + P.node_a[i]] : 0.0;
         const double b = (op >= KTN_OP_ADD && op <= KTN_OP_DIV) ? val[nb + P.node_b[i]] : 0.0;
         double v;
-        switch (op) {
-            case KTN_OP_CONST: v = P.node_c[i]; break;
-            case KTN_OP_VAR: v = xat(P.node_a[i]); break;
-            case KTN_OP_ADD: v = a + b; break;
-            case KTN_OP_SUB: v = a - b; break;
-            case KTN_OP_MUL: v = a * b; break;
-            case KTN_OP_DIV: v = a / b; break;
-            case KTN_OP_NEG: v = -a; break;
-            case KTN_OP_POWC: v = pow(a, P.node_c[i]); break;
-            case KTN_OP_EXP: v = exp(a); break;
-            case KTN_OP_LOG: v = log(a); break;
-            case KTN_OP_SQRT: v = sqrt(a); break;
-            case KTN_OP_SIN: v = sin(a); break;
-            default: v = cos(a); break;
-        }
+        if (op == KTN_OP_CONST) v = P.node_c[i];
+        else if (op == KTN_OP_VAR) v = xat(P.node_a[i]);
+        else v = tape_node_forward(op, a, b, [&]() { return P.node_c[i]; });
         val[i] = v;
         adj[i] = 0.0;
     }
@@ -697,25 +731,8 @@ __device__ __forceinline__ double tape_row_eval(const NlpDev& P, int32_t r, XF&&
         const double w = adj[i];
         if (op == KTN_OP_CONST) continue;
         if (op == KTN_OP_VAR) { jac[P.node_b[i]] += w; continue; }
-        const int64_t ia = nb + P.node_a[i];
-        const double a = val[ia];
-        switch (op) {
-            case KTN_OP_ADD: adj[ia] += w; adj[nb + P.node_b[i]] += w; break;
-            case KTN_OP_SUB: adj[ia] += w; adj[nb + P.node_b[i]] -= w; break;
-            case KTN_OP_MUL: { const int64_t ib = nb + P.node_b[i]; const double b = val[ib];
-                               adj[ia] += w * b; adj[ib] += w * a; } break;
-            case KTN_OP_DIV: { const int64_t ib = nb + P.node_b[i]; const double b = val[ib];
-                               adj[ia] += w * (1.0 / b); adj[ib] += w * (-(val[i] / b)); } break;
-            case KTN_OP_NEG: adj[ia] -= w; break;
-            case KTN_OP_POWC: { const double p = P.node_c[i];
-                                const double d = (p == 2.0) ? 2.0 * a : (p == 1.0 ? 1.0 : p * pow(a, p - 1.0));
-                                adj[ia] += w * d; } break;
-            case KTN_OP_EXP: adj[ia] += w * val[i]; break;
-            case KTN_OP_LOG: adj[ia] += w * (1.0 / a); break;
-            case KTN_OP_SQRT: adj[ia] += w * (0.5 / val[i]); break;
-            case KTN_OP_SIN: adj[ia] += w * cos(a); break;
-            default: adj[ia] += w * (-sin(a)); break;
-        }
+        tape_node_reverse(op, w, i, nb + P.node_a[i], [&]() { return nb + P.node_b[i]; }, [&](int64_t k) { return val[k]; },
+                          [&](int64_t k) -> double& { return adj[k]; }, [&]() { return P.node_c[i]; });
     }
     return val[ne - 1] + P.rconst[r];
 }
@@ -731,14 +748,16 @@ static __global__ __launch_bounds__(kBlock) void k_tape_eval(NlpDev P, const int
 
 // linear_oa_cut constant / round_coefs max / finite check / isconstrsat from a
 // materialised Jacobian row (tape rows; also the host-evaluator fallback of section 8b).
-// One thread per row, entries in storage order == the reference's left-to-right order.
+// One thread per row, entries in storage order == the reference's left-to-right order.  `classed` (may be null): per-row flag of
+// the tape rows that k_tape_classed evaluates, statistics included.
 static __global__ __launch_bounds__(kBlock) void k_gj_stats(NlpDev P, const int32_t* __restrict__ nl_rows, int64_t m_nl,
                                                      const double* __restrict__ x, double f_tol, int kind_filter,
-                                                     SweepOut O) {
+                                                     const uint8_t* __restrict__ classed, SweepOut O) {
     const int64_t gid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (gid >= m_nl) return;
     const int32_t r = nl_rows[gid];
     if (kind_filter >= 0 && (P.row_kind[r] == KTN_ROW_SEP || P.row_kind[r] == 3)) return;     // tape rows and host-evaluated rows (3 = kRowSepLong: k_sep_eval_long's)
+    if (classed && classed[r]) return;                                                        // k_tape_classed has done this row's part
     const int64_t beg = P.rowptr[r], end = P.rowptr[r + 1];
     const double g = O.g[r];
     double b = g, mx = -__builtin_inf();

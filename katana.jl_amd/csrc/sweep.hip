@@ -1,7 +1,11 @@
 // sweep.hip -- loadproblem! (src/model.jl:81-173) and the separator sweep (src/separators.jl:85-135, src/model.jl:272-283)  (struct Engine: engine.hpp)
+#include <cstring>
+#include <unordered_map>
+
 #include "engine.hpp"
 #include "launch.hpp"
 #include "kernels.hpp"
+#include "tape_classes.hpp"
 #include "batch_lp.hpp"
 #include "batch_ecp.hpp"
 
@@ -81,6 +85,203 @@ void Engine::host_eval(const double* d_x) {
     LAUNCH_1(k_host_scatter, n_host, stream, P, d_hostrows.p, n_host, d_gh.p, d_jh.p, O);
     check_launch();
     stats["host_evals"] += 1.0;
+}
+
+// ------------------------------------------------------------------------------------
+// Shape classes of the tape rows (tape_classes.hpp).  Two rows share a shape when their node lists agree in length, opcodes,
+// operand indices, POWC exponents and the VARs' Jacobian slots relative to rowptr, when their structures are equally long,
+// and when both or neither are NL rows (so a class is swept as a whole or not at all).  CONST values, columns, rconst and
+// bounds may differ.  The node lists are hashed (O(total nodes)); a row is compared with the first row of its hash's
+// classes only, so many distinct shapes cost nothing quadratic.  Members keep ascending row order.
+// ------------------------------------------------------------------------------------
+void Engine::build_tape_classes(const std::vector<int64_t>& nodeptr, const std::vector<int32_t>& nop, const std::vector<int32_t>& na,
+                                const std::vector<int32_t>& nb, const std::vector<double>& nc, const std::vector<int32_t>& tape_all) {
+    tc_rows = tc_rows_nl = 0;
+    tc_launches.clear();
+    const size_t nt = tape_all.size();
+    if (nt == 0) {                                                   // no tape rows: nothing to class, nothing to upload
+        d_tapeint_all.n = d_tapeint_nl.n = 0;
+        tape_bytes = 0.0;
+        for (const char* k : {"tape_classes", "tape_classed_rows", "tape_interp_rows", "tape_class_max_nodes", "tape_shapes",
+                              "tape_class_lds_bytes", "tape_class_dev_bytes"}) stats[k] = 0.0;
+        return;
+    }
+    std::vector<int32_t> nl_slot((size_t)m_ext, -1);
+    for (size_t si = 0; si < h_nlrows.size(); ++si) nl_slot[(size_t)h_nlrows[si]] = (int32_t)si;
+    // algorithmic bytes of the NL tape rows: 8 per constant, 4 per column, 8 per gathered x*, 8 per Jacobian entry, 48 of
+    // per-row outputs, 8 for row id and slot
+    tape_bytes = 0.0;
+    for (size_t t = 0; t < nt; ++t) {
+        const int64_t r = tape_all[t];
+        if (nl_slot[(size_t)r] < 0) continue;
+        int64_t k = 0;
+        for (int64_t i = nodeptr[(size_t)r]; i < nodeptr[(size_t)r + 1]; ++i) k += nop[(size_t)i] == KTN_OP_CONST ? 1 : 0;
+        const int64_t S = h_rowptr[(size_t)r + 1] - h_rowptr[(size_t)r];
+        tape_bytes += 8.0 * (double)k + (4.0 + 8.0 + 8.0) * (double)S + 48.0 + 8.0;
+    }
+    const int64_t min_rows = dev.tape_classed == 0 ? 0 : (dev.tape_classed > 0 ? 2 : kTapeClassMin);
+    std::vector<int32_t> cls_of(nt, -1), rep, cnt, next_same;        // per class: first member (index into tape_all), size, hash chain
+    if (min_rows > 0 && nt > 0) {
+        auto rel_b = [&](int64_t r, int64_t i) -> int32_t {          // VAR: slot relative to the row; else operand b
+            return nop[(size_t)i] == KTN_OP_VAR ? (int32_t)((int64_t)nb[(size_t)i] - h_rowptr[(size_t)r]) : nb[(size_t)i];
+        };
+        auto same_shape = [&](int64_t r, int64_t q) {
+            const int64_t b0 = nodeptr[(size_t)r], b1 = nodeptr[(size_t)q], n = nodeptr[(size_t)r + 1] - b0;
+            if (n != nodeptr[(size_t)q + 1] - b1) return false;
+            if (h_rowptr[(size_t)r + 1] - h_rowptr[(size_t)r] != h_rowptr[(size_t)q + 1] - h_rowptr[(size_t)q]) return false;
+            if ((nl_slot[(size_t)r] >= 0) != (nl_slot[(size_t)q] >= 0)) return false;
+            for (int64_t i = 0; i < n; ++i) {
+                const int op = nop[(size_t)(b0 + i)];
+                if (op != nop[(size_t)(b1 + i)]) return false;
+                if (op == KTN_OP_CONST) continue;
+                if (rel_b(r, b0 + i) != rel_b(q, b1 + i)) return false;
+                if (op != KTN_OP_VAR && na[(size_t)(b0 + i)] != na[(size_t)(b1 + i)]) return false;
+                if (op == KTN_OP_POWC && std::memcmp(&nc[(size_t)(b0 + i)], &nc[(size_t)(b1 + i)], sizeof(double)) != 0) return false;
+            }
+            return true;
+        };
+        std::unordered_map<uint64_t, int32_t> head;                  // hash -> first class with it
+        for (size_t t = 0; t < nt; ++t) {
+            const int64_t r = tape_all[t];
+            const int64_t b0 = nodeptr[(size_t)r], n = nodeptr[(size_t)r + 1] - b0;
+            uint64_t h = 0x9E3779B97F4A7C15ull ^ (uint64_t)n;
+            auto mix = [&](uint64_t v) { h ^= v + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2); h *= 0xFF51AFD7ED558CCDull; h ^= h >> 33; };
+            mix((uint64_t)(h_rowptr[(size_t)r + 1] - h_rowptr[(size_t)r]));
+            mix(nl_slot[(size_t)r] >= 0 ? 1u : 0u);
+            for (int64_t i = b0; i < b0 + n; ++i) {
+                const int op = nop[(size_t)i];
+                uint64_t w = (uint64_t)(uint32_t)op;
+                if (op != KTN_OP_CONST) w |= (uint64_t)(uint32_t)rel_b(r, i) << 32;
+                mix(w);
+                if (op > KTN_OP_VAR) mix((uint64_t)(uint32_t)na[(size_t)i]);
+                if (op == KTN_OP_POWC) { uint64_t bits; std::memcpy(&bits, &nc[(size_t)i], 8); mix(bits); }
+            }
+            auto it = head.find(h);
+            int32_t c = -1;
+            if (it != head.end()) {
+                int32_t last = -1;
+                for (c = it->second; c >= 0; last = c, c = next_same[(size_t)c])
+                    if (same_shape(r, tape_all[(size_t)rep[(size_t)c]])) break;
+                if (c < 0) { c = (int32_t)rep.size(); rep.push_back((int32_t)t); cnt.push_back(0); next_same.push_back(-1); next_same[(size_t)last] = c; }
+            } else {
+                c = (int32_t)rep.size(); rep.push_back((int32_t)t); cnt.push_back(0); next_same.push_back(-1);
+                head.emplace(h, c);
+            }
+            cls_of[t] = c;
+            ++cnt[(size_t)c];
+        }
+    }
+    // the classed classes: large enough, and the LDS image of a wavefront within its budget; NL classes first, by size bucket
+    const size_t ncls_all = rep.size();
+    std::vector<int32_t> dense(ncls_all, -1), order;
+    int64_t max_nodes = 0;
+    for (int pass = 0; pass < 8; ++pass)
+        for (size_t c = 0; c < ncls_all; ++c) {
+            const int64_t r = tape_all[(size_t)rep[c]];
+            const int64_t n = nodeptr[(size_t)r + 1] - nodeptr[(size_t)r], S = h_rowptr[(size_t)r + 1] - h_rowptr[(size_t)r];
+            if (cnt[c] < min_rows || 2 * n + S > kTapeClassMaxCells) continue;
+            if ((nl_slot[(size_t)r] >= 0) != (pass < 4) || tape_class_bucket(2 * n + S) != (pass & 3)) continue;
+            dense[c] = (int32_t)order.size();
+            order.push_back((int32_t)c);
+        }
+    const size_t ncls = order.size();
+    std::vector<TapeClassMeta> meta(ncls);
+    std::vector<int32_t> p_op, p_a, p_b, wave_cls, wave_first;
+    std::vector<double> p_c;
+    std::vector<uint8_t> rowflag((size_t)m_ext, 0);
+    int64_t mem = 0, ncst = 0, ncol = 0;
+    std::vector<std::vector<int32_t>> cpos(ncls);                    // positions of the CONST nodes of a class
+    int last_bucket = -1;
+    size_t max_lds = 0;
+    for (size_t k = 0; k < ncls; ++k) {
+        const size_t c = (size_t)order[k];
+        const int64_t r = tape_all[(size_t)rep[c]];
+        const int64_t b0 = nodeptr[(size_t)r], n = nodeptr[(size_t)r + 1] - b0, S = h_rowptr[(size_t)r + 1] - h_rowptr[(size_t)r];
+        TapeClassMeta& M = meta[k];
+        M.count = cnt[c]; M.nnodes = (int32_t)n; M.nslots = (int32_t)S; M.prog0 = (int32_t)p_op.size();
+        M.mem0 = mem; M.cst0 = ncst; M.col0 = ncol;
+        for (int64_t i = b0; i < b0 + n; ++i) {
+            const int op = nop[(size_t)i];
+            p_op.push_back(op);
+            if (op == KTN_OP_CONST) { p_a.push_back((int32_t)cpos[k].size()); p_b.push_back(0); cpos[k].push_back((int32_t)(i - b0)); }
+            else if (op == KTN_OP_VAR) { p_a.push_back(0); p_b.push_back((int32_t)((int64_t)nb[(size_t)i] - h_rowptr[(size_t)r])); }
+            else { p_a.push_back(na[(size_t)i]); p_b.push_back(nb[(size_t)i]); }
+            p_c.push_back(op == KTN_OP_POWC ? nc[(size_t)i] : 0.0);
+        }
+        const bool nl = nl_slot[(size_t)r] >= 0;
+        const size_t lds = (size_t)(2 * n + S) * kTapeClassWave * sizeof(double);
+        const int bucket = tape_class_bucket(2 * n + S);
+        if (tc_launches.empty() || tc_launches.back().nl != nl || bucket != last_bucket) tc_launches.push_back({(int64_t)wave_cls.size(), 0, 0, nl});
+        last_bucket = bucket;
+        for (int64_t f = 0; f < M.count; f += kTapeClassWave) { wave_cls.push_back((int32_t)k); wave_first.push_back((int32_t)f); }
+        tc_launches.back().nwaves = (int64_t)wave_cls.size() - tc_launches.back().wave0;
+        tc_launches.back().lds = std::max(tc_launches.back().lds, lds);
+        max_lds = std::max(max_lds, lds);
+        if (nl) tc_rows_nl += M.count;
+        mem += M.count; ncst += (int64_t)cpos[k].size() * M.count; ncol += S * M.count;
+        max_nodes = std::max(max_nodes, n);
+    }
+    tc_rows = mem;
+    // members in ascending row order (tape_all is ascending), operands class-major
+    std::vector<int32_t> mrow((size_t)mem), mslot((size_t)mem), scol((size_t)ncol), fill(ncls, 0), int_all, int_nl;
+    std::vector<double> cst((size_t)ncst);
+    for (size_t t = 0; t < nt; ++t) {
+        const int32_t r = tape_all[t];
+        const int32_t k = cls_of[t] >= 0 ? dense[(size_t)cls_of[t]] : -1;
+        if (k < 0) {
+            int_all.push_back(r);
+            if (nl_slot[(size_t)r] >= 0) int_nl.push_back(r);
+            continue;
+        }
+        const TapeClassMeta& M = meta[(size_t)k];
+        const int64_t j = fill[(size_t)k]++;
+        mrow[(size_t)(M.mem0 + j)] = r;
+        mslot[(size_t)(M.mem0 + j)] = nl_slot[(size_t)r];
+        rowflag[(size_t)r] = 1;
+        const int64_t b0 = nodeptr[(size_t)r], e0 = h_rowptr[(size_t)r];
+        for (size_t q = 0; q < cpos[(size_t)k].size(); ++q) cst[(size_t)(M.cst0 + (int64_t)q * M.count + j)] = nc[(size_t)(b0 + cpos[(size_t)k][q])];
+        for (int64_t sl = 0; sl < M.nslots; ++sl) scol[(size_t)(M.col0 + sl * M.count + j)] = h_col[(size_t)(e0 + sl)];
+    }
+    d_tapeint_all.upload(int_all, stream); d_tapeint_nl.upload(int_nl, stream);
+    d_tc_wavecls.upload(wave_cls, stream); d_tc_wavefirst.upload(wave_first, stream); d_tc_meta.upload(meta, stream);
+    d_tc_op.upload(p_op, stream); d_tc_a.upload(p_a, stream); d_tc_b.upload(p_b, stream); d_tc_c.upload(p_c, stream);
+    d_tc_cst.upload(cst, stream); d_tc_scol.upload(scol, stream); d_tc_mrow.upload(mrow, stream); d_tc_mslot.upload(mslot, stream);
+    d_tc_rowflag.upload(rowflag, stream);
+    sync();
+    stats["tape_classes"] = (double)ncls;
+    stats["tape_classed_rows"] = (double)tc_rows;
+    stats["tape_interp_rows"] = (double)int_all.size();
+    stats["tape_class_max_nodes"] = (double)max_nodes;
+    stats["tape_shapes"] = (double)ncls_all;
+    stats["tape_class_lds_bytes"] = (double)max_lds;
+    stats["tape_class_dev_bytes"] = 8.0 * (double)ncst + 4.0 * (double)ncol + 8.0 * (double)mem + 8.0 * (double)wave_cls.size() +
+                                    20.0 * (double)p_op.size() + (double)(sizeof(TapeClassMeta) * ncls) + (double)m_ext;
+}
+
+// k_tape_classed over the classes of NL rows (the sweep; mslot: NL slots) or over all classes (precompute_all; mslot: rows)
+void Engine::launch_tape_classed(bool nl_only, const int32_t* mslot, const double* d_x, double f_tol) {
+    if (tc_launches.empty()) return;
+    if (!tc_lds_set) {
+        KTN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_tape_classed), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)(kTapeClassMaxCells * kTapeClassWave * sizeof(double))));
+        tc_lds_set = true;
+    }
+    NlpDev P = nlp_view();
+    SweepOut O = sweep_view();
+    for (const TcLaunch& q : tc_launches) {
+        if (nl_only && !q.nl) continue;
+        TapeClassDev T = tape_class_view();
+        T.wave_cls += q.wave0; T.wave_first += q.wave0;
+        hipLaunchKernelGGL(k_tape_classed, dim3((unsigned)q.nwaves), dim3(kTapeClassWave), q.lds, stream, P, T, mslot, d_x, f_tol, O);
+    }
+}
+
+TapeClassDev Engine::tape_class_view() {
+    TapeClassDev T;
+    T.wave_cls = d_tc_wavecls.p; T.wave_first = d_tc_wavefirst.p; T.meta = d_tc_meta.p;
+    T.prog_op = d_tc_op.p; T.prog_a = d_tc_a.p; T.prog_b = d_tc_b.p; T.prog_c = d_tc_c.p;
+    T.cst = d_tc_cst.p; T.scol = d_tc_scol.p; T.mrow = d_tc_mrow.p;
+    return T;
 }
 
 void Engine::loadproblem(int64_t num_var, int64_t num_constr, const double* l_var, const double* u_var,
@@ -297,6 +498,8 @@ void Engine::loadproblem(int64_t num_var, int64_t num_constr, const double* l_va
     for (auto r : h_nlrows) n_host_nl += (h_rowkind[r] == KTN_ROW_HOST) ? 1 : 0;
     d_taperows_nl.upload(tape_nl, stream);
     d_nlrows.upload(h_nlrows, stream);
+    build_tape_classes(nodeptr, nop, na, nb, nc, tape_all);
+    lapl("tape shape classes");
     grp_sweep = pick_group(m_nl ? (double)nnz_nl / (double)m_nl : 4.0);
     if (grp_sweep < 8) grp_sweep = 8;
     lapl("pack + upload NLP");
@@ -676,12 +879,16 @@ void Engine::precompute_all(const double* d_x) {
     }
     if (n_longev > 0)
         hipLaunchKernelGGL(k_sep_eval_long, dim3((unsigned)n_longev), dim3(1024), 0, stream, P, d_longev_rows.p, d_longev_slots.p, d_x, 0.0, 0, O);
-    LAUNCH_1(k_tape_eval, (int64_t)d_taperows_all.n, stream, P, d_taperows_all.p, (int64_t)d_taperows_all.n, d_x, O);
+    LAUNCH_1(k_tape_eval, (int64_t)d_tapeint_all.n, stream, P, d_tapeint_all.p, (int64_t)d_tapeint_all.n, d_x, O);
     if (n_host > 0) host_eval(d_x);
     // cut constants / maxima of tape rows from the materialised Jacobian (flags unused here)
     KTN_HIP(hipMemsetAsync(d_scal.p, 0, sizeof(double), stream));
     KTN_HIP(hipMemsetAsync(d_anynf.p, 0, sizeof(int32_t), stream));
-    LAUNCH_1(k_gj_stats, m_ext, stream, P, d_allrows.p, m_ext, d_x, 0.0, (int)KTN_ROW_TAPE, O);
+    // rows of the classed shapes: value, Jacobian and those constants / maxima in one pass (flags by row, as k_gj_stats' here)
+    launch_tape_classed(false, d_tc_mrow.p, d_x, 0.0);
+    if (tc_rows == 0 || d_tapeint_all.n > 0 || n_host > 0)
+        LAUNCH_1(k_gj_stats, m_ext, stream, P, d_allrows.p, m_ext, d_x, 0.0, (int)KTN_ROW_TAPE,
+                 (const uint8_t*)(tc_rows > 0 ? d_tc_rowflag.p : nullptr), O);
     check_launch();
 }
 
@@ -744,9 +951,19 @@ hipExtLaunchKernelGGL((k_sep_eval_blk<G, BC, BS, U>), dim3((unsigned)(num_cus * 
     if (n_longev_nl > 0)
         hipLaunchKernelGGL(k_sep_eval_long, dim3((unsigned)n_longev_nl), dim3(1024), 0, stream, P, d_longev_nlrows.p, d_longev_nlslots.p, d_x, f_tol, 1, O);
     if (n_tape_nl > 0 || n_host_nl > 0) {
-        LAUNCH_1(k_tape_eval, n_tape_nl, stream, P, d_taperows_nl.p, n_tape_nl, d_x, O);
+        // tape rows: the classed shapes in one launch (k_tape_classed, statistics folded in), the others through the interpreter
+        // and k_gj_stats.  profile: the tape part has an event record of its own (tape_eval_*; sweep_eval_* stays the separable kernel)
+        size_t ta = 0, tb = 0;
+        const bool ev = prm.profile && n_tape_nl > 0;
+        if (ev) { ta = ev_get(); tb = ev_get(); KTN_HIP(hipEventRecord(ev_pool[ta], stream)); }
+        const int64_t n_int = (int64_t)d_tapeint_nl.n;
+        LAUNCH_1(k_tape_eval, n_int, stream, P, d_tapeint_nl.p, n_int, d_x, O);
         if (n_host_nl > 0) host_eval(d_x);
-        LAUNCH_1(k_gj_stats, m_nl, stream, P, d_nlrows.p, m_nl, d_x, f_tol, (int)KTN_ROW_TAPE, O);
+        launch_tape_classed(true, d_tc_mslot.p, d_x, f_tol);
+        if (n_int > 0 || n_host_nl > 0)
+            LAUNCH_1(k_gj_stats, m_nl, stream, P, d_nlrows.p, m_nl, d_x, f_tol, (int)KTN_ROW_TAPE,
+                     (const uint8_t*)(tc_rows_nl > 0 ? d_tc_rowflag.p : nullptr), O);
+        if (ev) { KTN_HIP(hipEventRecord(ev_pool[tb], stream)); ev_recs.push_back({4, ta, tb, tape_bytes}); }
     }
     check_launch();
     exclusive_scan(d_flag.p, d_rank.p, (size_t)m_nl);

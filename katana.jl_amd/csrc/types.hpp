@@ -30,6 +30,7 @@ struct TiledMat {
 
 struct NlpDev; struct SweepOut; struct LpRows; struct SpMat;        // kernels.hpp
 struct SepSlot; struct SepPartial; struct ColRec; struct RowRec;    // kernels.hpp
+struct TapeClassMeta; struct TapeClassDev;                           // tape_classes.hpp
 struct MidState;                                                     // mid_lp.hpp
 struct EcpArena;                                                     // batch_ecp.hpp
 
