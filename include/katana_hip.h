@@ -332,6 +332,27 @@ int ktn_lp_solve(ktn_handle h, double row_tol, double gap_tol, int32_t* lp_statu
  * rescaling (dr = dc = 1): kernel-level parity hook for tests */
 int ktn_lp_pdhg_raw(ktn_handle h, const double* x0, const double* y0, double eta,
                     double omega, int64_t iters, double* x_out, double* y_out);
+/* a scripted run from a prescribed state: kernel-level parity hook for tests.  x, y and the anchors x0, y0 are given
+ * in the stored LP's space and scaled as a solve scales its start; `k` is the Halpern counter of the first op; the ops
+ * run through the launch paths of the solve itself (lane groups, trips, packed / tiled forms and their KTN_*
+ * development switches included).  Outputs (each may be NULL) are in the SCALED space: x, y, anchors, the point
+ * (xt, yt) of the last check, q[0..15] the row sums and q[16..31] the column sums of the last check, xnext / ynext
+ * and *spec = 1 when that check left the next iterate there, and the scaling dr (rows), dc (columns). */
+#define KTN_LPOP_STEP 0      /* one plain iteration (x-step, y-step, Halpern update) */
+#define KTN_LPOP_CHECK 1     /* a check iteration: (xt, yt) and the 32 sums */
+#define KTN_LPOP_ADVANCE 2   /* the Halpern update after a check */
+#define KTN_LPOP_RESTART 3   /* restart from the point of the last check (k = 0 afterwards) */
+#define KTN_LPS_IDENTITY 1   /* flags: dr = dc = 1 instead of the solve's equilibration */
+#define KTN_LPS_PACKED 2     /*        plain steps read the packed per-row / per-column records */
+#define KTN_LPS_NO_SPEC 4    /*        checks do not precompute the next iterate */
+int ktn_lp_script(ktn_handle h, const double* x, const double* y, const double* x0, const double* y0,
+                  double eta, double omega, int64_t k, int32_t flags, const int32_t* ops, int64_t nops,
+                  double* x_out, double* y_out, double* x0_out, double* y0_out, double* xt_out,
+                  double* yt_out, double* q, double* xnext, double* ynext, int32_t* spec,
+                  double* dr, double* dc);
+/* the equilibration of the current LP, computed afresh: dr, dc and the factors before the last (sum-norm) pass
+ * (dr_r, dc_r; they need lp_ruiz_warm > 0): kernel-level parity hook for tests */
+int ktn_lp_scaling(ktn_handle h, double* dr, double* dc, double* dr_r, double* dc_r);
 int64_t ktn_num_lp_sols(ktn_handle h);           /* :VisData lp_sols, src/model.jl:267 */
 int ktn_get_lp_sol(ktn_handle h, int64_t k, double* x_out, int64_t n);
 
@@ -345,6 +366,11 @@ int ktn_get_lp_sol(ktn_handle h, int64_t k, double* x_out, int64_t n);
  *        "sweep_batched"        1 when the sweep is the batch-blocked one (many short rows)
  *        "precompute_multirow"  1 when precompute! runs four rows per lane group
  *        "sep_long_rows"        rows beyond 8 192 entries, evaluated one workgroup per row
+ * which form of the LP kernels the last ktn_lp_script ran (written by it, for tests):
+ *        "lp_grp_rows" "lp_grp_cols" lanes per row / column G;   "lp_packed" "lp_packed_trips" packed records on, outputs per group T
+ *        "lp_long_rows" "lp_long_cols" rows / columns beyond 2 048 entries;   "lp_tiled" "lp_tiled_check" "lp_tiled_pieces"
+ *        "lp_check_spec"        1 when the last check left the next iterate in xnext / ynext;   "lp_check_pinned"
+ *        "lp_scale_fused_passes" "lp_scale_split_passes"  equilibration passes in the one-launch / three-kernel form (counters)
  * with params.profile = 1, per hot kernel K in {kx, ky, sweep_eval}:
  *        "K_time_s" "K_launches" "K_bytes"  from the start/stop hipEvents of hipExtLaunchKernelGGL
  *        on the engine's own stream (dispatch begin/end, as rocprofv3 --kernel-trace reports) */

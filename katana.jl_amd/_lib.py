@@ -12,6 +12,8 @@ MIN, MAX = 0, 1
 ROW_SEP, ROW_TAPE, ROW_HOST = 0, 1, 2
 ATOM_LIN, ATOM_QUAD, ATOM_EXP, ATOM_NEGLOG = 0, 1, 2, 3
 CUT_KELLEY, CUT_SUPPORTING = 0, 1          # ktn_params.cut_algo
+LPOP_STEP, LPOP_CHECK, LPOP_ADVANCE, LPOP_RESTART = range(4)      # ktn_lp_script ops
+LPS_IDENTITY, LPS_PACKED, LPS_NO_SPEC = 1, 2, 4                   # ktn_lp_script flags
 (OP_CONST, OP_VAR, OP_ADD, OP_SUB, OP_MUL, OP_DIV, OP_NEG, OP_POWC, OP_EXP, OP_LOG, OP_SQRT, OP_SIN,
  OP_COS) = range(13)
 
@@ -92,6 +94,9 @@ PROTOTYPES = {
     "ktn_lp_get_duals": (c_i32, [C.c_void_p, P(c_f64), c_i64]),
     "ktn_lp_solve": (c_i32, [C.c_void_p, c_f64, c_f64, P(c_i32), P(c_i64)]),
     "ktn_lp_pdhg_raw": (c_i32, [C.c_void_p, P(c_f64), P(c_f64), c_f64, c_f64, c_i64, P(c_f64), P(c_f64)]),
+    "ktn_lp_script": (c_i32, [C.c_void_p, P(c_f64), P(c_f64), P(c_f64), P(c_f64), c_f64, c_f64, c_i64, c_i32, P(c_i32), c_i64]
+                      + [P(c_f64)] * 9 + [P(c_i32), P(c_f64), P(c_f64)]),
+    "ktn_lp_scaling": (c_i32, [C.c_void_p, P(c_f64), P(c_f64), P(c_f64), P(c_f64)]),
     "ktn_num_lp_sols": (c_i64, [C.c_void_p]),
     "ktn_get_lp_sol": (c_i32, [C.c_void_p, c_i64, P(c_f64), c_i64]),
     "ktn_get_stat": (c_f64, [C.c_void_p, C.c_char_p]),

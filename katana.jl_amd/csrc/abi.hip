@@ -293,6 +293,35 @@ int ktn_lp_pdhg_raw(ktn_handle h, const double* x0, const double* y0, double eta
         return KTN_OK;
     })
 }
+int ktn_lp_script(ktn_handle h, const double* x, const double* y, const double* x0, const double* y0, double eta, double omega,
+                  int64_t k, int32_t flags, const int32_t* ops, int64_t nops, double* x_out, double* y_out, double* x0_out,
+                  double* y0_out, double* xt_out, double* yt_out, double* q, double* xnext, double* ynext, int32_t* spec,
+                  double* dr, double* dc) {
+    KTN_TRY(h, {
+        Engine* e = h->eng;
+        KTN_REQUIRE(e->loaded, "no problem loaded");
+        KTN_REQUIRE(x && x0 && (e->M == 0 || (y && y0)), "lp_script: state and anchors are required");
+        KTN_REQUIRE(eta > 0.0 && omega > 0.0 && std::isfinite(eta) && std::isfinite(omega) && k >= 0, "lp_script: bad eta, omega or k");
+        KTN_REQUIRE(nops >= 0 && nops <= 4096 && (nops == 0 || ops), "lp_script: bad op list");
+        KTN_REQUIRE((flags & ~(KTN_LPS_IDENTITY | KTN_LPS_PACKED | KTN_LPS_NO_SPEC)) == 0, "lp_script: unknown flag");
+        KTN_REQUIRE(!e->row_sharded() && e->n_blocks == 0, "lp_script: one-GPU LPs without blocks only");
+        for (int64_t o = 0; o < nops; ++o) KTN_REQUIRE(ops[o] >= KTN_LPOP_STEP && ops[o] <= KTN_LPOP_RESTART, "lp_script: unknown op");
+        e->lp_script(Engine::LpScriptIO{x, y, x0, y0, eta, omega, k, flags, ops, nops, x_out, y_out, x0_out, y0_out, xt_out, yt_out, q,
+                                        xnext, ynext, spec, dr, dc});
+        return KTN_OK;
+    })
+}
+int ktn_lp_scaling(ktn_handle h, double* dr, double* dc, double* dr_r, double* dc_r) {
+    KTN_TRY(h, {
+        Engine* e = h->eng;
+        KTN_REQUIRE(e->loaded, "no problem loaded");
+        KTN_REQUIRE(dc && dc_r && (e->M == 0 || (dr && dr_r)), "lp_scaling: output buffers are required");
+        KTN_REQUIRE(e->prm.lp_ruiz_warm > 0, "lp_scaling: dr_r / dc_r are kept with lp_ruiz_warm > 0 only");
+        KTN_REQUIRE(!e->row_sharded(), "lp_scaling: one-GPU LPs only");
+        e->lp_scaling(dr, dc, dr_r, dc_r);
+        return KTN_OK;
+    })
+}
 int64_t ktn_num_lp_sols(ktn_handle h) { return (h && h->eng) ? (int64_t)h->eng->lp_sols.size() : -1; }
 int ktn_get_lp_sol(ktn_handle h, int64_t k, double* x_out, int64_t n) {
     KTN_TRY(h, {

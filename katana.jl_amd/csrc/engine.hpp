@@ -592,6 +592,26 @@ struct Engine {
     bool lp_solve_mid(LpResult* R);
     void pdhg_raw(const double* x0, const double* y0, double eta, double omega_, int64_t iters, double* x_out,
                   double* y_out);
+    // pieces of lp_solve_core that the scripted test hook shares with it (lp.hip)
+    void lp_pick_groups();
+    void lp_choose_tiled(bool same_matrix);
+    void lp_set_anchors(bool want_packed);
+    void lp_read_check(double* q);
+    void lp_restart();
+    void lp_advance(bool spec, int64_t k, double rho);
+    struct LpScriptIO {
+        const double *x, *y, *x0, *y0;
+        double eta, omega;
+        int64_t k;
+        int32_t flags;
+        const int32_t* ops;
+        int64_t nops;
+        double *x_out, *y_out, *x0_out, *y0_out, *xt_out, *yt_out, *q_out, *xnext_out, *ynext_out;
+        int32_t* spec_out;
+        double *dr_out, *dc_out;
+    };
+    void lp_script(const LpScriptIO& io);
+    void lp_scaling(double* dr_out, double* dc_out, double* drr_out, double* dcr_out);
 
     // ================================================================ ECP driver ====
     bool recession_ray();

@@ -80,6 +80,7 @@ void Engine::compute_scaling(bool identity) {
                 hipLaunchKernelGGL(k_scale_stat_upd_both, dim3((unsigned)(br + bc)), dim3(kBlock), 0, stream, M, lp_rowptr.p, lp_col.p, Wval(), n_lp,
                                    c_ptr.p, c_row.p, c_val.p, dr.p, dc.p, mode, dr2.p, dc2.p, cap_c, gr, gc, br);
                 dr.swap(dr2); dc.swap(dc2);
+                stats["lp_scale_fused_passes"] += 1.0;
                 continue;
             }
             if (n_long > 0) {
@@ -101,6 +102,7 @@ void Engine::compute_scaling(bool identity) {
                 allreduce(statc.p, (size_t)n_lp, mode ? 0 : 1);
             }
             LAUNCH_1(k_scale_apply2, std::max(M, n_lp), stream, M, dr.p, statr.p, n_lp, dc.p, statc.p, cap_c);
+            stats["lp_scale_split_passes"] += 1.0;
         }
     }
     scal_rows = identity ? 0 : M;
@@ -679,6 +681,91 @@ bool Engine::lp_solve_mid(LpResult* R) {
     return ok;
 }
 
+// ---- pieces of a first-order solve that lp_solve_core and the scripted test hook (lp_script) share ----
+// lanes per row / column: by the average length, then the development overrides
+void Engine::lp_pick_groups() {
+    const int64_t n = n_lp, m = M;
+    const double avg_r = m ? (double)NNZ / (double)m : 1.0, avg_c = n ? (double)NNZ / (double)n : 1.0;
+    grp_rows = pick_group(avg_r);
+    grp_cols = pick_group(avg_c);
+    if (dev.grp_rows > 0) grp_rows = dev.grp_rows;
+    if (dev.grp_cols > 0) grp_cols = dev.grp_cols;
+}
+
+// LPs beyond the caches: tiled copies of A^ and A^' (kernels.hpp "tiled SpMV") serve the plain steps and the check
+// iterations; the power iteration keeps the CSR / CSC kernels
+void Engine::lp_choose_tiled(bool same_matrix) {
+    {
+        const bool tenv = dev.tiled >= 0;
+        // ... and dense enough: every (tile, block) unit stages a 64 KB block of the input vector, so a matrix with few entries
+        // per unit pays more for the staging than for its entries (n = 1e6, 5.8e6 entries: 350 per unit, 1.31 s tiled against
+        // 0.49 s with the CSR kernels; cfg4: 9 500 per unit)
+        const int64_t units_t = ceil_div(M, (int64_t)kTileOut) * ceil_div(n_lp, (int64_t)kTileIn);
+        const int64_t units_tt = ceil_div(n_lp, (int64_t)kTileOut) * ceil_div(M, (int64_t)kTileIn);
+        tiled_on = prm.lp_tiled_nnz > 0 && NNZ >= prm.lp_tiled_nnz && n_lp >= 2 * kTileIn && M >= 2 * kTileIn &&
+                   NNZ >= 4096 * std::max(units_t, units_tt);
+        if (tenv) tiled_on = dev.tiled != 0 && M > 0 && NNZ > 0;
+        if (same_matrix) tiled_on = tiled_built;            // the copies of the previous solve (or their absence) still fit
+        else if (tiled_on) {
+            auto tt = std::chrono::steady_clock::now();
+            tiled_on = build_tiled(tA, M, n_lp, lp_rowptr.p, lp_col.p, r_sval.p, kLongRow) &&
+                       build_tiled(tAT, n_lp, M, c_ptr.p, c_row.p, c_sval.p, (int64_t)1 << 62);
+            tpart.resize((size_t)std::max<int64_t>(tA.pieces * M, tAT.pieces * n_lp), stream);
+            stats["lp_tiled_builds"] += 1.0;
+            stats["lp_tiled_build_time_s"] += std::chrono::duration<double>(std::chrono::steady_clock::now() - tt).count();
+            if (!tiled_on) stats["lp_tiled_overflows"] += 1.0;
+        }
+        tiled_built = tiled_on;
+    }
+}
+
+// anchors z0 = z; with the packed records of the plain steps when asked for (not for the tiled / row-sharded forms, whose
+// steps are split into SpMV + element-wise kernels)
+void Engine::lp_set_anchors(bool want_packed) {
+    const int64_t n = n_lp, m = M;
+    const size_t mm = (size_t)std::max<int64_t>(m, 1);
+    packed_on = want_packed && !tiled_on && !row_sharded() && NNZ < ((int64_t)1 << 31) && !dev.no_packed;
+    if (dev.packed_trips > 0) packed_trips = dev.packed_trips;
+    if (packed_on) {
+        d_crec.resize((size_t)n, stream); d_cbl.resize((size_t)n, stream); d_rrec.resize(mm, stream);
+        LAUNCH_1(k_pack_both, std::max(n, m), stream, n, c_ptr.p, ch.p, lh.p, uh.p, xh.p, x0h.p, d_crec.p, d_cbl.p,
+                 m, lp_rowptr.p, loh.p, hih.p, yh.p, y0h.p, d_rrec.p);
+    } else {
+        KTN_HIP(hipMemcpyAsync(x0h.p, xh.p, n * sizeof(double), hipMemcpyDeviceToDevice, stream));
+        if (m > 0) KTN_HIP(hipMemcpyAsync(y0h.p, yh.p, m * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    }
+}
+
+// the 2 kChkQ sums of the last check: q[0 .. kChkQ) rows, q[kChkQ ..) columns
+void Engine::lp_read_check(double* q) {
+    if (chk_pinned()) {
+        sync();
+        std::memcpy(q, h_chk, 2 * kChkQ * sizeof(double));
+    } else {
+        KTN_HIP(hipMemcpyAsync(q, chkout.p, 2 * kChkQ * sizeof(double), hipMemcpyDeviceToHost, stream));
+        sync();
+        ipc_check();
+    }
+}
+
+// restart from the point of the last check: z <- T(z), z0 <- T(z), in the arrays and in the packed records
+void Engine::lp_restart() {
+    const int64_t n = n_lp, m = M;
+    LAUNCH_1(k_restart_set, std::max(n, m), stream, n, m, xth.p, xh.p, x0h.p, yth.p, yh.p, y0h.p, packed_on ? d_crec.p : (ColRec*)nullptr,
+             packed_on ? d_rrec.p : (RowRec*)nullptr);
+}
+
+// the Halpern update after a check that neither ended nor restarted the solve
+void Engine::lp_advance(bool spec, int64_t k, double rho) {
+    const int64_t n = n_lp, m = M;
+    if (spec) {                                       // the check kernels left the update in xnext / ynext
+        xh.swap(xnext); yh.swap(ynext);
+    } else {
+        const double w = (double)(k + 1) / (double)(k + 2);
+        LAUNCH_1(k_halpern2, std::max(n, m), stream, n, m, xh.p, xth.p, x0h.p, yh.p, yth.p, y0h.p, w, rho);
+    }
+}
+
 LpResult Engine::lp_solve_core(double tol_p, double tol_g, int mode, bool identity_scaling) {
     auto t0 = std::chrono::steady_clock::now();
     LpResult R;
@@ -714,38 +801,11 @@ LpResult Engine::lp_solve_core(double tol_p, double tol_g, int mode, bool identi
         hipLaunchKernelGGL(k_epi_var, dim3(1), dim3(1), 0, stream, xh.p, (int32_t)n0, epi_scal.p, (const double*)dc.p, -1, have_omega ? 0 : 1, sgn, epi_newest.p);
     }
     check_launch();
-    const double avg_r = m ? (double)NNZ / (double)m : 1.0, avg_c = n ? (double)NNZ / (double)n : 1.0;
-    grp_rows = pick_group(avg_r);
-    grp_cols = pick_group(avg_c);
-    if (dev.grp_rows > 0) grp_rows = dev.grp_rows;
-    if (dev.grp_cols > 0) grp_cols = dev.grp_cols;
+    lp_pick_groups();
     SpMat A{lp_rowptr.p, lp_col.p, r_sval.p};
     SpMat AT{c_ptr.p, c_row.p, c_sval.p};
-    // LPs beyond the caches: tiled copies of A^ and A^' (kernels.hpp "tiled SpMV") serve the plain steps and the check
-    // iterations; the power iteration keeps the CSR / CSC kernels
-    {
-        const bool tenv = dev.tiled >= 0;
-        // ... and dense enough: every (tile, block) unit stages a 64 KB block of the input vector, so a matrix with few entries
-        // per unit pays more for the staging than for its entries (n = 1e6, 5.8e6 entries: 350 per unit, 1.31 s tiled against
-        // 0.49 s with the CSR kernels; cfg4: 9 500 per unit)
-        const int64_t units_t = ceil_div(M, (int64_t)kTileOut) * ceil_div(n_lp, (int64_t)kTileIn);
-        const int64_t units_tt = ceil_div(n_lp, (int64_t)kTileOut) * ceil_div(M, (int64_t)kTileIn);
-        tiled_on = prm.lp_tiled_nnz > 0 && NNZ >= prm.lp_tiled_nnz && n_lp >= 2 * kTileIn && M >= 2 * kTileIn &&
-                   NNZ >= 4096 * std::max(units_t, units_tt);
-        if (tenv) tiled_on = dev.tiled != 0 && M > 0 && NNZ > 0;
-        if (same_matrix) tiled_on = tiled_built;            // the copies of the previous solve (or their absence) still fit
-        else if (tiled_on) {
-            auto tt = std::chrono::steady_clock::now();
-            tiled_on = build_tiled(tA, M, n_lp, lp_rowptr.p, lp_col.p, r_sval.p, kLongRow) &&
-                       build_tiled(tAT, n_lp, M, c_ptr.p, c_row.p, c_sval.p, (int64_t)1 << 62);
-            tpart.resize((size_t)std::max<int64_t>(tA.pieces * M, tAT.pieces * n_lp), stream);
-            stats["lp_tiled_builds"] += 1.0;
-            stats["lp_tiled_build_time_s"] += std::chrono::duration<double>(std::chrono::steady_clock::now() - tt).count();
-            if (!tiled_on) stats["lp_tiled_overflows"] += 1.0;
-        }
-        tiled_built = tiled_on;
-        scaled_version = lp_version; scaled_identity = identity_scaling;
-    }
+    lp_choose_tiled(same_matrix);
+    scaled_version = lp_version; scaled_identity = identity_scaling;
 
     // Step size eta = 0.998 / sigma_max(A^).  sigma_max comes from 8 power iterations (round 1: 20; hashed start
     // vector: a constant one can be orthogonal to every row).  The power iteration approaches sigma_max
@@ -883,16 +943,7 @@ LpResult Engine::lp_solve_core(double tol_p, double tol_g, int mode, bool identi
 
     // anchors z0 = z; with the packed records of the plain steps (not for the tiled / row-sharded forms, whose steps are
     // split into SpMV + element-wise kernels)
-    packed_on = !tiled_on && !row_sharded() && NNZ < ((int64_t)1 << 31) && !dev.no_packed;
-    if (dev.packed_trips > 0) packed_trips = dev.packed_trips;
-    if (packed_on) {
-        d_crec.resize((size_t)n, stream); d_cbl.resize((size_t)n, stream); d_rrec.resize(mm, stream);
-        LAUNCH_1(k_pack_both, std::max(n, m), stream, n, c_ptr.p, ch.p, lh.p, uh.p, xh.p, x0h.p, d_crec.p, d_cbl.p,
-                 m, lp_rowptr.p, loh.p, hih.p, yh.p, y0h.p, d_rrec.p);
-    } else {
-        KTN_HIP(hipMemcpyAsync(x0h.p, xh.p, n * sizeof(double), hipMemcpyDeviceToDevice, stream));
-        if (m > 0) KTN_HIP(hipMemcpyAsync(y0h.p, yh.p, m * sizeof(double), hipMemcpyDeviceToDevice, stream));
-    }
+    lp_set_anchors(true);
 
     const double ky_bytes = (double)NNZ * 12 + 8.0 * (m + 1) + 8.0 * 5 * m + 8.0 * n;
     const double kx_bytes = (double)NNZ * 12 + 8.0 * (n + 1) + 8.0 * 7 * n + 8.0 * m;
@@ -949,14 +1000,7 @@ LpResult Engine::lp_solve_core(double tol_p, double tol_g, int mode, bool identi
         const bool spec_next = launch_check(A, AT, tau, sigma, (double)(k + 1) / (double)(k + 2), rho);
         check_launch();
         double q[2 * kChkQ];
-        if (chk_pinned()) {
-            sync();
-            std::memcpy(q, h_chk, sizeof(q));
-        } else {
-            KTN_HIP(hipMemcpyAsync(q, chkout.p, sizeof(q), hipMemcpyDeviceToHost, stream));
-            sync();
-            ipc_check();
-        }
+        lp_read_check(q);
         if (prm.profile) ev_flush();
         const double dyAdx = q[0], dy2 = q[1], dobj_rows = q[2], dy0sq = q[3], yt2 = q[4], pviol = q[12];
         const double dx2 = q[kChkQ + 5], pobj = q[kChkQ + 6] + obj_shift, dobj_cols = q[kChkQ + 7], dx0sq = q[kChkQ + 8],
@@ -1085,8 +1129,7 @@ LpResult Engine::lp_solve_core(double tol_p, double tol_g, int mode, bool identi
                 KTN_HIP(hipMemsetAsync(d_anynf.p + 1, 0, sizeof(int32_t), stream));
                 LAUNCH_1(k_consolidate, list_count(), stream, list_count(), list_heads(), d_cutprev.p, pw.p, Wlo(), Whi(), dr.p, tol_p, yth.p,
                          d_anynf.p + 1);
-                LAUNCH_1(k_restart_set, std::max(n, m), stream, n, m, xth.p, xh.p, x0h.p, yth.p, yh.p, y0h.p, packed_on ? d_crec.p : (ColRec*)nullptr,
-                         packed_on ? d_rrec.p : (RowRec*)nullptr);
+                lp_restart();
                 k = 0;
                 r_last_check = 0.0;
                 ++it;
@@ -1127,19 +1170,13 @@ LpResult Engine::lp_solve_core(double tol_p, double tol_g, int mode, bool identi
                 if (om_clamp_dn > 1.0) om = std::max(om, om_old / om_clamp_dn);
                 om = std::min(std::max(om, omega_ref * 1e-3), omega_ref * 1e3);
             }
-            LAUNCH_1(k_restart_set, std::max(n, m), stream, n, m, xth.p, xh.p, x0h.p, yth.p, yh.p, y0h.p, packed_on ? d_crec.p : (ColRec*)nullptr,
-                         packed_on ? d_rrec.p : (RowRec*)nullptr);
+            lp_restart();
             stats["lp_restarts"] += 1.0;
             k = 0;
             ++it;
             continue;
         }
-        if (spec_next) {                                  // the check kernels left the update in xnext / ynext
-            xh.swap(xnext); yh.swap(ynext);
-        } else {
-            const double w = (double)(k + 1) / (double)(k + 2);
-            LAUNCH_1(k_halpern2, std::max(n, m), stream, n, m, xh.p, xth.p, x0h.p, yh.p, yth.p, y0h.p, w, rho);
-        }
+        lp_advance(spec_next, k, rho);
         ++k; ++it;
         plain_next = true;       // (after a restart k == 0 and the next pass is a check again: it needs r0)
     }
@@ -1236,6 +1273,107 @@ void Engine::pdhg_raw(const double* x0, const double* y0, double eta, double ome
     check_launch();
     KTN_HIP(hipMemcpyAsync(x_out, xh.p, n * sizeof(double), hipMemcpyDeviceToHost, stream));
     if (m > 0) KTN_HIP(hipMemcpyAsync(y_out, yh.p, m * sizeof(double), hipMemcpyDeviceToHost, stream));
+    sync();
+}
+
+// Scripted test hook: the state (x, y) with anchors (x0, y0), given in the stored LP's space and scaled by k_prep_both as a
+// solve scales its start, then a short list of ops through the member functions lp_solve_core itself runs.  k is the
+// Halpern counter of the first op.  flags: KTN_LPS_IDENTITY (dr = dc = 1), KTN_LPS_PACKED (packed records for the plain
+// steps), KTN_LPS_NO_SPEC (the check does not leave the update in xnext / ynext: the advance is k_halpern2).
+void Engine::lp_script(const LpScriptIO& io) {
+    const bool identity = (io.flags & KTN_LPS_IDENTITY) != 0;
+    ensure_matrix(false);
+    find_long_rows();
+    scal_rows = 0;                                       // (a cold equilibration, whatever ran on this handle before)
+    compute_scaling(identity);
+    scaled_version = 0;                                  // (lp_solve_core must not take this setup for its own)
+    const int64_t n = n_lp, m = M;
+    const size_t mm = (size_t)std::max<int64_t>(m, 1);
+    ch.resize(n, stream); lh.resize(n, stream); uh.resize(n, stream); xh.resize(n, stream);
+    x0h.resize(n, stream); xth.resize(n, stream); xbar.resize(n, stream); pv.resize(n, stream);
+    loh.resize(mm, stream); hih.resize(mm, stream); yh.resize(mm, stream); y0h.resize(mm, stream);
+    yth.resize(mm, stream); pw.resize(mm, stream);
+    const double sgn = (sense == KTN_MAX) ? -1.0 : 1.0;
+    auto prep = [&](const double* xs, const double* ys) {
+        KTN_HIP(hipMemcpyAsync(lp_x.p, xs, n * sizeof(double), hipMemcpyHostToDevice, stream));
+        if (m > 0) KTN_HIP(hipMemcpyAsync(lp_y.p, ys, m * sizeof(double), hipMemcpyHostToDevice, stream));
+        LAUNCH_1(k_prep_both, std::max(n, m), stream,
+                 PrepCols{n, Wc(), lp_l.p, lp_u.p, dc.p, lp_x.p, (const double*)nullptr, sgn, 0, ch.p, lh.p, uh.p, xh.p},
+                 PrepRows{m, Wlo(), Whi(), dr.p, lp_y.p, 0, loh.p, hih.p, yh.p});
+    };
+    lp_pick_groups();
+    SpMat A{lp_rowptr.p, lp_col.p, r_sval.p};
+    SpMat AT{c_ptr.p, c_row.p, c_sval.p};
+    lp_choose_tiled(false);
+    prep(io.x0, io.y0);                                  // the anchors first: lp_set_anchors takes them from xh / yh ...
+    lp_set_anchors((io.flags & KTN_LPS_PACKED) != 0);
+    prep(io.x, io.y);                                    // ... then the state itself
+    check_launch();
+    stats["lp_long_rows"] = (double)n_long; stats["lp_long_cols"] = (double)n_longc;
+    stats["lp_packed"] = packed_on ? 1.0 : 0.0; stats["lp_packed_trips"] = (double)packed_trips;
+    stats["lp_grp_rows"] = (double)grp_rows; stats["lp_grp_cols"] = (double)grp_cols;
+    stats["lp_tiled"] = tiled_on ? 1.0 : 0.0;
+    stats["lp_tiled_check"] = (tiled_on && m > 0 && !dev.no_tiled_check) ? 1.0 : 0.0;
+    stats["lp_tiled_pieces"] = tiled_on ? (double)std::max(tA.pieces, tAT.pieces) : 0.0;
+    stats["lp_check_pinned"] = chk_pinned() ? 1.0 : 0.0;
+    const double tau = io.eta / io.omega, sigma = io.eta * io.omega, rho = 1.0;
+    int64_t k = io.k;
+    bool checked = false, spec = false;
+    double q[2 * kChkQ];
+    for (int q_ = 0; q_ < 2 * kChkQ; ++q_) q[q_] = 0.0;
+    for (int64_t o = 0; o < io.nops; ++o) {
+        const double w = (double)(k + 1) / (double)(k + 2);
+        switch (io.ops[o]) {
+            case KTN_LPOP_STEP:
+                launch_x(AT, tau, w, rho, true, nullptr, nullptr);
+                launch_y(A, sigma, w, rho, nullptr, nullptr);
+                ++k; checked = false;
+                break;
+            case KTN_LPOP_CHECK:
+                spec = launch_check(A, AT, tau, sigma, (io.flags & KTN_LPS_NO_SPEC) ? -1.0 : w, rho);
+                check_launch();
+                lp_read_check(q);
+                if (spec && io.xnext_out) xnext.download(io.xnext_out, (size_t)n, stream);
+                if (spec && io.ynext_out && m > 0) ynext.download(io.ynext_out, (size_t)m, stream);
+                checked = true;
+                break;
+            case KTN_LPOP_ADVANCE:
+                KTN_REQUIRE(checked, "lp_script: advance without a check before it");
+                lp_advance(spec, k, rho);
+                ++k; checked = false;
+                break;
+            case KTN_LPOP_RESTART:
+                KTN_REQUIRE(checked, "lp_script: restart without a check before it");
+                lp_restart();
+                k = 0; checked = false;
+                break;
+            default:
+                KTN_REQUIRE(false, "lp_script: unknown op");
+        }
+        if ((o & 255) == 255) sync();
+    }
+    check_launch();
+    sync();
+    stats["lp_check_spec"] = spec ? 1.0 : 0.0;
+    if (io.spec_out) *io.spec_out = spec ? 1 : 0;
+    if (io.q_out) std::memcpy(io.q_out, q, sizeof(q));
+    auto out = [&](DBuf<double>& b, double* dst, int64_t cnt) { if (dst && cnt > 0) b.download(dst, (size_t)cnt, stream); };
+    out(xh, io.x_out, n); out(x0h, io.x0_out, n); out(xth, io.xt_out, n); out(dc, io.dc_out, n);
+    out(yh, io.y_out, m); out(y0h, io.y0_out, m); out(yth, io.yt_out, m); out(dr, io.dr_out, m);
+    sync();
+}
+
+// Scaling hook: a cold compute_scaling(false) on the current LP; dr, dc and the factors before the Pock-Chambolle pass
+// (dr_r, dc_r: kept when lp_ruiz_warm > 0)
+void Engine::lp_scaling(double* dr_out, double* dc_out, double* drr_out, double* dcr_out) {
+    ensure_matrix(false);
+    find_long_rows();
+    scal_rows = 0;
+    compute_scaling(false);
+    scaled_version = 0;
+    stats["lp_long_rows"] = (double)n_long; stats["lp_long_cols"] = (double)n_longc;
+    if (M > 0) { dr.download(dr_out, (size_t)M, stream); dr_r.download(drr_out, (size_t)M, stream); }
+    dc.download(dc_out, (size_t)n_lp, stream); dc_r.download(dcr_out, (size_t)n_lp, stream);
     sync();
 }
 

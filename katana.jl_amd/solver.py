@@ -310,6 +310,39 @@ class KatanaNonlinearModel:
         L.check(self._h, self._lib.ktn_lp_pdhg_raw(self._h, _p(x0), _p(y0p), eta, omega, iters, _p(xo), _p(yo)))
         return xo, yo[:m]
 
+    def lp_script(self, x, y, x0, y0, eta, omega, k, ops, identity=True, packed=False, no_spec=False):
+        """ktn_lp_script: ops (L.LPOP_*) from the state (x, y) with anchors (x0, y0), all given in the stored LP's space.
+        Returns a dict of the SCALED x, y, x0, y0, xt, yt, the 32 check sums q, xnext / ynext (None unless the last check left
+        them), and the scaling dr, dc."""
+        n, m = self.num_var, int(self._lib.ktn_lp_num_rows(self._h))
+        pad = lambda a: a if len(a) else np.zeros(1)
+        ins = [pad(_f64(a)) for a in (x, y, x0, y0)]
+        assert len(ins[0]) == len(ins[2]) == n and (m == 0 or len(ins[1]) == len(ins[3]) == m)
+        ops = np.ascontiguousarray(ops, dtype=np.int32)
+        flags = (L.LPS_IDENTITY if identity else 0) | (L.LPS_PACKED if packed else 0) | (L.LPS_NO_SPEC if no_spec else 0)
+        o = {k_: np.zeros(n) for k_ in ("x", "x0", "xt", "xnext", "dc")}
+        o.update({k_: np.zeros(max(m, 1)) for k_ in ("y", "y0", "yt", "ynext", "dr")})
+        o["q"] = np.zeros(32)
+        spec = C.c_int32(0)
+        L.check(self._h, self._lib.ktn_lp_script(
+            self._h, _p(ins[0]), _p(ins[1]), _p(ins[2]), _p(ins[3]), eta, omega, int(k), flags,
+            _p(ops if len(ops) else np.zeros(1, dtype=np.int32), C.c_int32), len(ops), _p(o["x"]), _p(o["y"]), _p(o["x0"]),
+            _p(o["y0"]), _p(o["xt"]), _p(o["yt"]), _p(o["q"]), _p(o["xnext"]), _p(o["ynext"]), C.byref(spec), _p(o["dr"]),
+            _p(o["dc"])))
+        for k_ in ("y", "y0", "yt", "ynext", "dr"):
+            o[k_] = o[k_][:m]
+        o["spec"] = bool(spec.value)
+        if not o["spec"]:
+            o["xnext"] = o["ynext"] = None
+        return o
+
+    def lp_scaling(self):
+        """ktn_lp_scaling: (dr, dc, dr_r, dc_r) of a fresh equilibration of the current LP (needs lp_ruiz_warm > 0)"""
+        n, m = self.num_var, int(self._lib.ktn_lp_num_rows(self._h))
+        dr, drr, dc, dcr = np.zeros(max(m, 1)), np.zeros(max(m, 1)), np.zeros(n), np.zeros(n)
+        L.check(self._h, self._lib.ktn_lp_scaling(self._h, _p(dr), _p(dc), _p(drr), _p(dcr)))
+        return dr[:m], dc, drr[:m], dcr
+
 
 class KatanaHipSeparator:
     """The first-order separator (KatanaFirstOrderSeparator, src/separators.jl:58-120) in batched,

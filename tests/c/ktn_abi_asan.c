@@ -65,6 +65,8 @@ int main(void) {
     EXPECT(ktn_lp_num_rows(NULL) < 0 && ktn_lp_nnz(NULL) < 0 && ktn_lp_get_rows(NULL, i8, i4, d8, d8, d8) == KTN_E_INVALID);
     EXPECT(ktn_lp_get_objective(NULL, d8, 8, d8) == KTN_E_INVALID && ktn_lp_get_duals(NULL, d8, 8) == KTN_E_INVALID);
     EXPECT(ktn_lp_solve(NULL, 1e-6, 1e-6, i4, i8) == KTN_E_INVALID && ktn_lp_pdhg_raw(NULL, d8, d8, 1.0, 1.0, 1, d8, d8) == KTN_E_INVALID);
+    EXPECT(ktn_lp_script(NULL, d8, d8, d8, d8, 1.0, 1.0, 0, 0, i4, 0, d8, d8, d8, d8, d8, d8, d8, d8, d8, i4, d8, d8) == KTN_E_INVALID);
+    EXPECT(ktn_lp_scaling(NULL, d8, d8, d8, d8) == KTN_E_INVALID);
     EXPECT(ktn_num_lp_sols(NULL) < 0 && ktn_get_lp_sol(NULL, 0, d8, 8) == KTN_E_INVALID);
     EXPECT(!(ktn_get_stat(NULL, "pdhg_iters") > 0.0) && !(ktn_get_stat(NULL, NULL) > 0.0));
     EXPECT(ktn_sweep_lp_point(NULL, 1e-6, i8, d8) == KTN_E_INVALID && ktn_lp_nnz_from(NULL, 0) < 0);

@@ -49,6 +49,13 @@ def test_raw_pdhg_iterations_match_numpy(iters):
     xn, yn = _halpern_numpy(A, c, inst.l_var, inst.u_var, lo, hi, x0, y0, eta, omega, iters)
     assert np.max(np.abs(xg - xn)) <= 1e-11 * (1 + np.max(np.abs(xn)))
     assert np.max(np.abs(yg - yn)) <= 1e-11 * (1 + np.max(np.abs(yn)))
+    # ... and the packed-record kernels of a real solve (k_pdhg_x_packed / k_pdhg_y_packed), which lp_pdhg_raw never runs
+    from katana_jl_amd import _lib as L
+    o = m.lp_script(x0, y0, x0, y0, eta, omega, 0, [L.LPOP_STEP] * iters, identity=True, packed=True)
+    assert m.stat("lp_packed") == 1
+    xg, yg = o["x"], o["y"]
+    assert np.max(np.abs(xg - xn)) <= 1e-11 * (1 + np.max(np.abs(xn)))
+    assert np.max(np.abs(yg - yn)) <= 1e-11 * (1 + np.max(np.abs(yn)))
 
 
 @pytest.mark.parametrize("seed", [0, 1])
