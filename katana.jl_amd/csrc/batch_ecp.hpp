@@ -347,7 +347,7 @@ static __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B) {
                     ecp_spmv<4, 4>(nb, cptr, crow, csval, ys, [&](int j) { return EcpPre{ch[j], lh[j], uh[j]}; },
                                    [&](int j, double acc, const EcpPre& p) {
                         const double xv = xs[j];
-                        const double xtv = clampd(xv - tau * (p.a - acc), p.b, p.c);
+                        const double xtv = prox_x(xv, tau, p.a, acc, p.b, p.c);
                         xts[j] = 2.0 * xtv - xv;
                         xs[j] = w * (2.0 * xtv - xv) + (1.0 - w) * x0s[j];
                     });
@@ -356,7 +356,7 @@ static __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B) {
                                    [&](int r, double acc, const EcpPre& p) {
                         const double y1 = ys[r];
                         const double v = y1 - sigma * acc;
-                        const double ytv = v + sigma * clampd(-v * inv_sigma, p.a, p.b);
+                        const double ytv = v + sigma * clampd(-v * inv_sigma, p.a, p.b);   // not prox_y: -v * (1 / sigma) rounds differently from -v / sigma
                         ys[r] = w * (2.0 * ytv - y1) + (1.0 - w) * y0s[r];
                     });
                     __syncthreads();
@@ -368,7 +368,7 @@ static __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B) {
 #pragma unroll
             for (int i = 0; i < kEcpQ; ++i) a[i] = 0.0;
             ecp_spmv<4, 4>(nb, cptr, crow, csval, ys, [&](int j) { return EcpPre{ch[j], lh[j], uh[j]}; },
-                           [&](int j, double acc, const EcpPre& p) { xts[j] = clampd(xs[j] - tau * (p.a - acc), p.b, p.c); });
+                           [&](int j, double acc, const EcpPre& p) { xts[j] = prox_x(xs[j], tau, p.a, acc, p.b, p.c); });
             __syncthreads();
             {
                 const int lane = tid & 3;
@@ -378,8 +378,7 @@ static __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B) {
                     axt = group_sum<4>(axt); axk = group_sum<4>(axk);
                     if (lane == 0) {
                         const double loi = loh[r], hii = hih[r], y1 = ys[r];
-                        const double v = y1 - sigma * (2.0 * axt - axk);
-                        const double ytv = v + sigma * clampd(-v / sigma, loi, hii);
+                        const double ytv = prox_y(y1, sigma, 2.0 * axt - axk, loi, hii);
                         yts[r] = ytv;
                         axv[r] = axt;
                         const double dy = ytv - y1;

@@ -182,7 +182,7 @@ static __global__ __launch_bounds__(kBlkThreads) void k_pdhg_blocks(BlkLp P) {
                             const int j = j0 + t * (kBlkThreads / GX);
                             if (j < nb) {
                                 const double xv = xs[j];
-                                const double xtv = clampd(xv - tau * (cj[t] - acc[t]), lj[t], uj[t]);
+                                const double xtv = prox_x(xv, tau, cj[t], acc[t], lj[t], uj[t]);
                                 xts[j] = 2.0 * xtv - xv;
                                 xs[j] = w * (2.0 * xtv - xv) + (1.0 - w) * x0s[j];
                             }
@@ -210,8 +210,7 @@ static __global__ __launch_bounds__(kBlkThreads) void k_pdhg_blocks(BlkLp P) {
                             const int r = rr + t * (kBlkThreads / GY);
                             if (r < mb) {
                                 const double yv = ys[r];
-                                const double v = yv - sigma * acc[t];
-                                const double ytv = v + sigma * clampd(-v / sigma, loi[t], hii[t]);
+                                const double ytv = prox_y(yv, sigma, acc[t], loi[t], hii[t]);
                                 ys[r] = w * (2.0 * ytv - yv) + (1.0 - w) * y0s[r];
                             }
                         }
@@ -235,7 +234,7 @@ static __global__ __launch_bounds__(kBlkThreads) void k_pdhg_blocks(BlkLp P) {
             double acc = 0.0;
             for (int64_t e = beg + lane; e < end; e += GX) acc += P.cval[e] * ys[P.crowl[e]];
             acc = group_sum<GX>(acc);
-            if (lane == 0) xts[j] = clampd(xs[j] - tau * (P.c[gj] - acc), P.l[gj], P.u[gj]);
+            if (lane == 0) xts[j] = prox_x(xs[j], tau, P.c[gj], acc, P.l[gj], P.u[gj]);
         }
         __syncthreads();
         for (int r = tid / GY; r < mb; r += kBlkThreads / GY) {
@@ -253,8 +252,7 @@ static __global__ __launch_bounds__(kBlkThreads) void k_pdhg_blocks(BlkLp P) {
             axk = group_sum<GY>(axk);
             if (lane == 0) {
                 const double loi = P.lo[gi], hii = P.hi[gi], yv = ys[r];
-                const double v = yv - sigma * (2.0 * axt - axk);
-                const double ytv = v + sigma * clampd(-v / sigma, loi, hii);
+                const double ytv = prox_y(yv, sigma, 2.0 * axt - axk, loi, hii);
                 yts[r] = ytv;
                 const double dy = ytv - yv;
                 a[0] += dy * (axt - axk);

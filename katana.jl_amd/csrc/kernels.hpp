@@ -82,6 +82,42 @@ __device__ __forceinline__ void block_max_nonneg(double* addr, double v) {
 }
 __device__ __forceinline__ double clampd(double v, double lo, double hi) { return fmin(fmax(v, lo), hi); }
 
+// Block-wide SUM of Q values per thread in a fixed shape, hence run-to-run identical: xor-butterfly inside every wavefront, lane 0 of
+// every wavefront to LDS, ONE barrier for all Q, then thread 0 adds the wavefronts' cells to 0.0 in order; the sums replace v in
+// thread 0 (only there).  Every thread of the block reaches the call.  sh: the CALLER's cells -- a kernel that goes on to
+// use them again puts its own barrier in between.
+// (Reductions that start from wavefront 0's cell instead of 0.0 -- the two differ for a sum of -0.0 -- or that reduce maxima and flags
+//  along with the sums keep their own text: chk_block_store, k_chk_final, k_scale_stat_long, k_sep_eval_long, k_esh_long; so does
+//  k_setup_norms_partial, where thread q finishes quantity q.)
+template <int BLOCK, int Q>
+__device__ __forceinline__ void block_sum(double (&v)[Q], double (*sh)[BLOCK / 64]) {
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v[q] += __shfl_xor(v[q], off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int q = 0; q < Q; ++q) sh[q][threadIdx.x >> 6] = v[q];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int q = 0; q < Q; ++q) v[q] = 0.0;
+        for (int k = 0; k < BLOCK / 64; ++k) {
+#pragma unroll
+            for (int q = 0; q < Q; ++q) v[q] += sh[q][k];
+        }
+    }
+}
+// one quantity: returns the sum (valid in thread 0)
+template <int BLOCK>
+__device__ __forceinline__ double block_sum(double v, double (&sh)[BLOCK / 64]) {
+    double a[1] = {v};
+    block_sum<BLOCK>(a, &sh);
+    return a[0];
+}
+
 // Six scalars a sweep / a purge hands back to the host -- the last elements of two (flag, exclusive scan) pairs, the
 // largest violation and two int flags -- written by ONE thread into pinned, device-mapped host memory instead of six
 // device-to-host copies (a copy kernel of ~4.5 us each).  Counts are exact in a double below 2^53.
@@ -1067,6 +1103,22 @@ struct SpMat {
     const double* val;   // scaled values
 };
 
+// ---- the arithmetic of a PDHG step, written once: every form of the step (plain, skip, long, packed, tiled epilogue, row-sharded,
+// batch) and the speculative slots of the check kernels call these, so they agree bit for bit by construction ----------------------
+// reflected Halpern update of one coordinate: t = T(z), v = z, v0 = the anchor z0
+__device__ __forceinline__ double halpern(double w, double rho, double t, double v, double v0) {
+    return w * ((1.0 + rho) * t - rho * v) + (1.0 - w) * v0;
+}
+// xt = clip(x - tau (c - A'y), l, u)
+__device__ __forceinline__ double prox_x(double xv, double tau, double c, double aty, double l, double u) {
+    return clampd(xv - tau * (c - aty), l, u);
+}
+// v = y - sigma A xbar;  yt = v + sigma clip(-v / sigma, lo, hi)
+__device__ __forceinline__ double prox_y(double yv, double sigma, double ax, double lo, double hi) {
+    const double v = yv - sigma * ax;
+    return v + sigma * clampd(-v / sigma, lo, hi);
+}
+
 // Block-level accumulation of kChkQ quantities: [0..11] sums, [12..15] maxima.
 struct ChkAcc {
     double s[kChkQ];
@@ -1130,23 +1182,25 @@ __global__ __launch_bounds__(kBlock) void k_pdhg_x(int64_t n, SpMat AT, const do
     // the per-column scalars are requested up front by every lane of the group (same address: one
     // transaction), so their latency overlaps the gather chain instead of following the reduction
     // (check form with xbar != nullptr: the slot receives the Halpern update the iteration WOULD make -- if the host decides to go
-    //  on, it swaps that array in for x instead of launching k_halpern2; same expression, same bits)
+    //  on, it swaps that array in for x instead of launching k_halpern2; the same halpern(), hence the same bits)
     const double xv = x[j], cj = c[j], lj = l[j], uj = u[j], x0j = (UPDATE || xbar) ? x0[j] : 0.0;
     double acc = 0.0;
     for (int64_t e = beg + lane; e < end; e += G) acc += AT.val[e] * y[AT.idx[e]];
     acc = group_sum<G>(acc);
     if (lane == 0) {
-        const double xtv = clampd(xv - tau * (cj - acc), lj, uj);
-        if (UPDATE) { xbar[j] = 2.0 * xtv - xv; x[j] = w * ((1.0 + rho) * xtv - rho * xv) + (1.0 - w) * x0j; }
+        const double xtv = prox_x(xv, tau, cj, acc, lj, uj);
+        if (UPDATE) { xbar[j] = 2.0 * xtv - xv; x[j] = halpern(w, rho, xtv, xv, x0j); }
         else {
             xt[j] = xtv;
-            if (xbar) xbar[j] = w * ((1.0 + rho) * xtv - rho * xv) + (1.0 - w) * x0j;
+            if (xbar) xbar[j] = halpern(w, rho, xtv, xv, x0j);
         }
     }
 }
 
 // The x-step of an LP with long columns (a variable every cut contains): lane groups for the ordinary columns, one
-// 1024-thread workgroup per long column (fixed-shape reduction: butterfly per wavefront, wavefronts in order).
+// 1024-thread workgroup per long column (block_sum: a fixed-shape reduction).  No speculative slot: the check form ignores xbar.
+// (Not one body with k_pdhg_x: through a shared inline body the compiler fetches the SpMat kernel argument as one wide scalar
+//  load at entry instead of field by field at first use -- harmless, but not the same machine code.)
 template <int G, bool UPDATE>
 __global__ __launch_bounds__(kBlock) void k_pdhg_x_skip(int64_t n, SpMat AT, const double* __restrict__ y,
                                                         double* __restrict__ x, const double* __restrict__ x0,
@@ -1163,8 +1217,8 @@ __global__ __launch_bounds__(kBlock) void k_pdhg_x_skip(int64_t n, SpMat AT, con
     for (int64_t e = beg + lane; e < end; e += G) acc += AT.val[e] * y[AT.idx[e]];
     acc = group_sum<G>(acc);
     if (lane == 0) {
-        const double xtv = clampd(xv - tau * (cj - acc), lj, uj);
-        if (UPDATE) { xbar[j] = 2.0 * xtv - xv; x[j] = w * ((1.0 + rho) * xtv - rho * xv) + (1.0 - w) * x0j; }
+        const double xtv = prox_x(xv, tau, cj, acc, lj, uj);
+        if (UPDATE) { xbar[j] = 2.0 * xtv - xv; x[j] = halpern(w, rho, xtv, xv, x0j); }
         else xt[j] = xtv;
     }
 }
@@ -1178,15 +1232,11 @@ __global__ __launch_bounds__(1024) void k_pdhg_x_long(const int32_t* __restrict_
     const int64_t j = cols[blockIdx.x];
     double acc = 0.0;
     for (int64_t e = AT.ptr[j] + threadIdx.x; e < AT.ptr[j + 1]; e += 1024) acc += AT.val[e] * y[AT.idx[e]];
-    acc = group_sum<64>(acc);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-    __syncthreads();
+    const double a = block_sum<1024>(acc, sh);
     if (threadIdx.x == 0) {
-        double a = 0.0;
-        for (int k = 0; k < 1024 / 64; ++k) a += sh[k];
         const double xv = x[j];
-        const double xtv = clampd(xv - tau * (c[j] - a), l[j], u[j]);
-        if (UPDATE) { xbar[j] = 2.0 * xtv - xv; x[j] = w * ((1.0 + rho) * xtv - rho * xv) + (1.0 - w) * x0[j]; }
+        const double xtv = prox_x(xv, tau, c[j], a, l[j], u[j]);
+        if (UPDATE) { xbar[j] = 2.0 * xtv - xv; x[j] = halpern(w, rho, xtv, xv, x0[j]); }
         else xt[j] = xtv;
     }
 }
@@ -1195,33 +1245,11 @@ __global__ __launch_bounds__(1024) void k_pdhg_x_long(const int32_t* __restrict_
 // Per column the x-step reads (beg, len) as one 8-byte pair and (c, l, u, x0) as one 32-byte record instead of seven
 // separate arrays; per row the y-step reads (lo, hi, y0, beg | len) as one 32-byte record.  The records mirror ch / lh /
 // uh / x0h and loh / hih / y0h (which the check kernels keep using) and are rewritten where those change: at the start
-// of a solve (k_pack_cols / k_pack_rows) and at restarts (k_restart_set).
+// of a solve (k_pack_both) and at restarts (k_restart_set).
 struct __attribute__((aligned(32))) ColRec { double c, l, u, x0; };
 struct __attribute__((aligned(32))) RowRec { double lo, hi, y0; int32_t beg, len; };
 
-static __global__ __launch_bounds__(kBlock) void k_pack_cols(int64_t n, const int64_t* __restrict__ ptr, const double* __restrict__ c,
-                                                      const double* __restrict__ l, const double* __restrict__ u,
-                                                      const double* __restrict__ x, double* __restrict__ x0,
-                                                      ColRec* __restrict__ rec, int2* __restrict__ bl) {
-    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (j >= n) return;
-    const double xv = x[j];
-    x0[j] = xv;
-    ColRec r; r.c = c[j]; r.l = l[j]; r.u = u[j]; r.x0 = xv;
-    rec[j] = r;
-    bl[j] = make_int2((int)ptr[j], (int)(ptr[j + 1] - ptr[j]));
-}
-static __global__ __launch_bounds__(kBlock) void k_pack_rows(int64_t m, const int64_t* __restrict__ ptr, const double* __restrict__ lo,
-                                                      const double* __restrict__ hi, const double* __restrict__ y,
-                                                      double* __restrict__ y0, RowRec* __restrict__ rec) {
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= m) return;
-    const double yv = y[i];
-    y0[i] = yv;
-    RowRec r; r.lo = lo[i]; r.hi = hi[i]; r.y0 = yv; r.beg = (int32_t)ptr[i]; r.len = (int32_t)(ptr[i + 1] - ptr[i]);
-    rec[i] = r;
-}
-// the packed records of the columns and of the rows in one launch (the bodies of k_pack_cols / k_pack_rows)
+// the packed records of the columns and of the rows in one launch (thread i takes column i and row i)
 static __global__ __launch_bounds__(kBlock) void k_pack_both(int64_t n, const int64_t* __restrict__ cptr, const double* __restrict__ c,
                                                       const double* __restrict__ l, const double* __restrict__ u, const double* __restrict__ x,
                                                       double* __restrict__ x0, ColRec* __restrict__ crec, int2* __restrict__ bl, int64_t m,
@@ -1273,9 +1301,9 @@ __global__ __launch_bounds__(kBlock) void k_pdhg_x_packed(int64_t n, const int2*
         const int64_t j = g0 + t * groups;
         const double a = group_sum<G>(acc[t]);
         if (lane == 0 && j < n) {
-            const double xtv = clampd(xv[t] - tau * (r[t].c - a), r[t].l, r[t].u);
+            const double xtv = prox_x(xv[t], tau, r[t].c, a, r[t].l, r[t].u);
             xbar[j] = 2.0 * xtv - xv[t];
-            x[j] = w * ((1.0 + rho) * xtv - rho * xv[t]) + (1.0 - w) * r[t].x0;
+            x[j] = halpern(w, rho, xtv, xv[t], r[t].x0);
         }
     }
 }
@@ -1315,16 +1343,10 @@ __global__ __launch_bounds__(kBlock) void k_pdhg_y_packed(int64_t m, const int32
             for (int k = 0; k < 4; ++k) acc += v[k] * xg[k];
         }
         for (; e < end; e += kBlock) acc += val[e] * xbar[idx[e]];
-        acc = group_sum<64>(acc);
-        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-        __syncthreads();
+        const double a = block_sum<kBlock>(acc, sh);
         if (threadIdx.x == 0) {
-            double a = 0.0;
-            for (int k = 0; k < kBlock / 64; ++k) a += sh[k];
             const double yv = y[i];
-            const double v = yv - sigma * a;
-            const double ytv = v + sigma * clampd(-v / sigma, rr.lo, rr.hi);
-            y[i] = w * ((1.0 + rho) * ytv - rho * yv) + (1.0 - w) * rr.y0;
+            y[i] = halpern(w, rho, prox_y(yv, sigma, a, rr.lo, rr.hi), yv, rr.y0);
         }
         return;
     }
@@ -1350,9 +1372,7 @@ __global__ __launch_bounds__(kBlock) void k_pdhg_y_packed(int64_t m, const int32
         const int64_t i = g0 + t * groups;
         const double a = group_sum<G>(acc[t]);
         if (lane == 0 && i < m && r[t].len >= 0) {
-            const double v = yv[t] - sigma * a;
-            const double ytv = v + sigma * clampd(-v / sigma, r[t].lo, r[t].hi);
-            y[i] = w * ((1.0 + rho) * ytv - rho * yv[t]) + (1.0 - w) * r[t].y0;
+            y[i] = halpern(w, rho, prox_y(yv[t], sigma, a, r[t].lo, r[t].hi), yv[t], r[t].y0);
         }
     }
 }
@@ -1394,9 +1414,7 @@ __global__ __launch_bounds__(kBlock) void k_pdhg_y(int64_t m, SpMat A, const dou
     for (int64_t e = beg + lane; e < end; e += G) acc += A.val[e] * xbar[A.idx[e]];
     acc = group_sum<G>(acc);
     if (lane == 0) {
-        const double v = yv - sigma * acc;
-        const double ytv = v + sigma * clampd(-v / sigma, loi, hii);
-        y[i] = w * ((1.0 + rho) * ytv - rho * yv) + (1.0 - w) * y0i;
+        y[i] = halpern(w, rho, prox_y(yv, sigma, acc, loi, hii), yv, y0i);
     }
 }
 
@@ -1429,10 +1447,9 @@ __global__ __launch_bounds__(kBlock) void k_pdhg_y_chk(int64_t m, SpMat A, const
     axt = group_sum<G>(axt);
     axk = group_sum<G>(axk);
     if (mine && lane == 0) {
-        const double v = yv - sigma * (2.0 * axt - axk);
-        const double ytv = v + sigma * clampd(-v / sigma, loi, hii);
+        const double ytv = prox_y(yv, sigma, 2.0 * axt - axk, loi, hii);
         yt[i] = ytv;
-        if (ynext) ynext[i] = w * ((1.0 + rho) * ytv - rho * yv) + (1.0 - w) * y0i;      // (see k_pdhg_x: the update the iteration would make)
+        if (ynext) ynext[i] = halpern(w, rho, ytv, yv, y0i);      // (see k_pdhg_x: the update the iteration would make)
         chk_row_accumulate(a, ytv, yv, y0i, axt, axk, loi, hii, dri);
     }
     chk_block_store<kBlock, kChkRowMask, G>(a, partials);
@@ -1459,26 +1476,20 @@ __global__ __launch_bounds__(kLongBlock) void k_pdhg_y_long(const int32_t* __res
         if (CHECK) acc2 += v * xb[c];
     }
     __shared__ double sh[2][kLongBlock / 64];
-    acc = group_sum<64>(acc);
-    if (CHECK) acc2 = group_sum<64>(acc2);
-    if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = acc; sh[1][threadIdx.x >> 6] = acc2; }
-    __syncthreads();
+    double a2[2] = {acc, acc2};
+    block_sum<kLongBlock>(a2, sh);
     if (threadIdx.x == 0) {
-        double ax = 0.0, ax2 = 0.0;
-        for (int k = 0; k < kLongBlock / 64; ++k) { ax += sh[0][k]; ax2 += sh[1][k]; }
+        const double ax = a2[0], ax2 = a2[1];
         const double yv = y[i];
         if (CHECK) {
-            const double v = yv - sigma * (2.0 * ax - ax2);
-            const double ytv = v + sigma * clampd(-v / sigma, lo[i], hi[i]);
+            const double ytv = prox_y(yv, sigma, 2.0 * ax - ax2, lo[i], hi[i]);
             yt[i] = ytv;
             ChkAcc a; a.init();
             chk_row_accumulate(a, ytv, yv, y0[i], ax, ax2, lo[i], hi[i], dr[i]);
 #pragma unroll
             for (int q = 0; q < kChkQ; ++q) partials[(int64_t)blockIdx.x * kChkQ + q] = a.s[q];
         } else {
-            const double v = yv - sigma * ax;
-            const double ytv = v + sigma * clampd(-v / sigma, lo[i], hi[i]);
-            y[i] = w * ((1.0 + rho) * ytv - rho * yv) + (1.0 - w) * y0[i];
+            y[i] = halpern(w, rho, prox_y(yv, sigma, ax, lo[i], hi[i]), yv, y0[i]);
         }
     }
 }
@@ -1522,8 +1533,8 @@ static __global__ __launch_bounds__(kBlock) void k_halpern2(int64_t n, int64_t m
                                                     const double* __restrict__ x0, double* __restrict__ y,
                                                     const double* __restrict__ yt, const double* __restrict__ y0, double w, double rho) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i < n) x[i] = w * ((1.0 + rho) * xt[i] - rho * x[i]) + (1.0 - w) * x0[i];
-    if (i < m) y[i] = w * ((1.0 + rho) * yt[i] - rho * y[i]) + (1.0 - w) * y0[i];
+    if (i < n) x[i] = halpern(w, rho, xt[i], x[i], x0[i]);
+    if (i < m) y[i] = halpern(w, rho, yt[i], y[i], y0[i]);
 }
 
 // second stage of the deterministic reductions: one block of kRedBlocks threads per (side, quantity) -- blockIdx.x =
@@ -1554,6 +1565,24 @@ static __global__ __launch_bounds__(kRedBlocks) void k_chk_final(const double* _
 //  s5 sum dx^2  s6 primal objective  s7 dual objective (bounds)  s8 sum (xt-x0)^2  s9 sum xt^2
 //  s10 Farkas value (bounds part)  s11 its absolute terms  m14 max reduced cost of the c=0 problem on an infinite bound
 //  m13 max unscaled dual residual (reduced cost not absorbable by a finite bound)
+__device__ __forceinline__ void chk_col_accumulate(ChkAcc& a, double xtv, double xv, double x0v, double aty, double cj, double lj,
+                                                   double uj, double dcj) {
+    const double dx = xtv - xv;
+    a.s[5] += dx * dx;
+    a.s[6] += cj * xtv;
+    const double r = cj - aty;
+    double bad = 0.0;
+    if (r > 0.0) { if (isfinite(lj)) a.s[7] += lj * r; else bad = r; }
+    else if (r < 0.0) { if (isfinite(uj)) a.s[7] += uj * r; else bad = -r; }
+    const double d0 = xtv - x0v;
+    a.s[8] += d0 * d0;
+    a.s[9] += xtv * xtv;
+    a.s[13] = fmax(a.s[13], bad / dcj);
+    // Farkas value of yt: the dual objective with c = 0 (positive <=> the rows + bounds are infeasible)
+    const double r0 = -aty;
+    if (r0 > 0.0) { if (isfinite(lj)) { a.s[10] += lj * r0; a.s[11] += fabs(lj * r0); } else a.s[14] = fmax(a.s[14], r0); }
+    else if (r0 < 0.0) { if (isfinite(uj)) { a.s[10] += uj * r0; a.s[11] += fabs(uj * r0); } else a.s[14] = fmax(a.s[14], -r0); }
+}
 // Column side of the check: A'yt needs yt, which only exists after the y-step, so this one SpMV pass stays a kernel of
 // its own -- G lanes per column over the whole chip, like the x-step.
 template <int G>
@@ -1573,21 +1602,7 @@ __global__ __launch_bounds__(kBlock) void k_chk_cols(int64_t n, SpMat AT, const 
     for (int64_t e = beg + lane; e < end; e += G) aty += AT.val[e] * yt[AT.idx[e]];
     aty = group_sum<G>(aty);
     if (on && lane == 0) {
-        const double dx = xtv - xv;
-        a.s[5] += dx * dx;
-        a.s[6] += cj * xtv;
-        const double r = cj - aty;
-        double bad = 0.0;
-        if (r > 0.0) { if (isfinite(lj)) a.s[7] += lj * r; else bad = r; }
-        else if (r < 0.0) { if (isfinite(uj)) a.s[7] += uj * r; else bad = -r; }
-        const double d0 = xtv - x0v;
-        a.s[8] += d0 * d0;
-        a.s[9] += xtv * xtv;
-        a.s[13] = fmax(a.s[13], bad / dcj);
-        // Farkas value of yt: the dual objective with c = 0 (positive <=> the rows + bounds are infeasible)
-        const double r0 = -aty;
-        if (r0 > 0.0) { if (isfinite(lj)) { a.s[10] += lj * r0; a.s[11] += fabs(lj * r0); } else a.s[14] = fmax(a.s[14], r0); }
-        else if (r0 < 0.0) { if (isfinite(uj)) { a.s[10] += uj * r0; a.s[11] += fabs(uj * r0); } else a.s[14] = fmax(a.s[14], -r0); }
+        chk_col_accumulate(a, xtv, xv, x0v, aty, cj, lj, uj, dcj);
     }
     chk_block_store<kBlock, kChkColMask, G>(a, partials);
 }
@@ -1604,8 +1619,8 @@ __global__ __launch_bounds__(kBlock) void k_x_prox(int64_t n, const double* __re
     const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (j >= n) return;
     const double xv = x[j];
-    const double xtv = clampd(xv - tau * (c[j] - aty[j]), l[j], u[j]);
-    if (UPDATE) { xbar[j] = 2.0 * xtv - xv; x[j] = w * ((1.0 + rho) * xtv - rho * xv) + (1.0 - w) * x0[j]; }
+    const double xtv = prox_x(xv, tau, c[j], aty[j], l[j], u[j]);
+    if (UPDATE) { xbar[j] = 2.0 * xtv - xv; x[j] = halpern(w, rho, xtv, xv, x0[j]); }
     else xt[j] = xtv;
 }
 // column side of the check from the all-reduced A'yt (same sums as k_chk_cols; identical on every rank)
@@ -1618,20 +1633,7 @@ static __global__ __launch_bounds__(kBlock) void k_chk_cols_vec(int64_t n, const
     ChkAcc a; a.init();
     if (j < n) {
         const double xtv = xt[j], xv = x[j], x0v = x0[j], cj = c[j], lj = l[j], uj = u[j], dcj = dc[j], aty = atyv[j];
-        const double dx = xtv - xv;
-        a.s[5] += dx * dx;
-        a.s[6] += cj * xtv;
-        const double r = cj - aty;
-        double bad = 0.0;
-        if (r > 0.0) { if (isfinite(lj)) a.s[7] += lj * r; else bad = r; }
-        else if (r < 0.0) { if (isfinite(uj)) a.s[7] += uj * r; else bad = -r; }
-        const double d0 = xtv - x0v;
-        a.s[8] += d0 * d0;
-        a.s[9] += xtv * xtv;
-        a.s[13] = fmax(a.s[13], bad / dcj);
-        const double r0 = -aty;
-        if (r0 > 0.0) { if (isfinite(lj)) { a.s[10] += lj * r0; a.s[11] += fabs(lj * r0); } else a.s[14] = fmax(a.s[14], r0); }
-        else if (r0 < 0.0) { if (isfinite(uj)) { a.s[10] += uj * r0; a.s[11] += fabs(uj * r0); } else a.s[14] = fmax(a.s[14], -r0); }
+        chk_col_accumulate(a, xtv, xv, x0v, aty, cj, lj, uj, dcj);
     }
     chk_block_store<kBlock, kChkColMask>(a, partials);
 }
@@ -1702,8 +1704,8 @@ __global__ __launch_bounds__(kBlock) void k_x_prox_ipc(int64_t n, IpcPeers P, in
     double aty = ipc_load(P.data[0] + off + j);
     for (int r = 1; r < world; ++r) aty += ipc_load(P.data[r] + off + j);
     const double xv = x[j];
-    const double xtv = clampd(xv - tau * (c[j] - aty), l[j], u[j]);
-    if (UPDATE) { xbar[j] = 2.0 * xtv - xv; x[j] = w * ((1.0 + rho) * xtv - rho * xv) + (1.0 - w) * x0[j]; }
+    const double xtv = prox_x(xv, tau, c[j], aty, l[j], u[j]);
+    if (UPDATE) { xbar[j] = 2.0 * xtv - xv; x[j] = halpern(w, rho, xtv, xv, x0[j]); }
     else xt[j] = xtv;
 }
 static __global__ __launch_bounds__(kBlock) void k_probe_fill(int64_t n, double* __restrict__ v, double base) {
@@ -1880,7 +1882,7 @@ __device__ __forceinline__ double tile_pieces_sum(const double* __restrict__ par
     for (; p < np; ++p) acc += part[(int64_t)p * n_out + o];
     return acc;
 }
-// epilogues of the tiled steps: the pieces in order, then exactly the arithmetic of k_pdhg_x / k_pdhg_y
+// epilogues of the tiled steps: the pieces in order, then prox_x / prox_y and halpern as in k_pdhg_x / k_pdhg_y
 static __global__ __launch_bounds__(kBlock) void k_x_epilogue(int64_t n, const int32_t* __restrict__ pcnt, const double* __restrict__ part,
                                                        double* __restrict__ x, const double* __restrict__ x0, double* __restrict__ xbar,
                                                        const double* __restrict__ c, const double* __restrict__ l,
@@ -1889,9 +1891,9 @@ static __global__ __launch_bounds__(kBlock) void k_x_epilogue(int64_t n, const i
     if (j >= n) return;
     const double xv = x[j], cj = c[j], lj = l[j], uj = u[j], x0j = x0[j];
     const double acc = tile_pieces_sum(part, j, n, pcnt);
-    const double xtv = clampd(xv - tau * (cj - acc), lj, uj);
+    const double xtv = prox_x(xv, tau, cj, acc, lj, uj);
     xbar[j] = 2.0 * xtv - xv;
-    x[j] = w * ((1.0 + rho) * xtv - rho * xv) + (1.0 - w) * x0j;
+    x[j] = halpern(w, rho, xtv, xv, x0j);
 }
 static __global__ __launch_bounds__(kBlock) void k_y_epilogue(int64_t m, const int32_t* __restrict__ pcnt, const double* __restrict__ part,
                                                        const int64_t* __restrict__ rowptr, int64_t long_thresh, double* __restrict__ y,
@@ -1902,9 +1904,7 @@ static __global__ __launch_bounds__(kBlock) void k_y_epilogue(int64_t m, const i
     if (rowptr && rowptr[i + 1] - rowptr[i] > long_thresh) return;      // served by k_pdhg_y_long (rowptr == NULL: no long rows)
     const double yv = y[i], loi = lo[i], hii = hi[i], y0i = y0[i];
     const double acc = tile_pieces_sum(part, i, m, pcnt);
-    const double v = yv - sigma * acc;
-    const double ytv = v + sigma * clampd(-v / sigma, loi, hii);
-    y[i] = w * ((1.0 + rho) * ytv - rho * yv) + (1.0 - w) * y0i;
+    y[i] = halpern(w, rho, prox_y(yv, sigma, acc, loi, hii), yv, y0i);
 }
 
 // ---- check iteration on the tiled copy: four tiled passes (A'y, A xt, A x, A'yt) with element-wise epilogues; the sums are
@@ -1916,7 +1916,7 @@ static __global__ __launch_bounds__(kBlock) void k_x_epilogue_chk(int64_t n, con
                                                            const double* __restrict__ u, double tau) {
     const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (j >= n) return;
-    xt[j] = clampd(x[j] - tau * (c[j] - tile_pieces_sum(part, j, n, pcnt)), l[j], u[j]);
+    xt[j] = prox_x(x[j], tau, c[j], tile_pieces_sum(part, j, n, pcnt), l[j], u[j]);
 }
 static __global__ __launch_bounds__(kBlock) void k_tile_vec(int64_t n_out, const int32_t* __restrict__ pcnt, const double* __restrict__ part,
                                                      double* __restrict__ out) {
@@ -1936,8 +1936,7 @@ static __global__ __launch_bounds__(kBlock) void k_y_epilogue_chk(int64_t m, con
     if (mine) {
         const double yv = y[i], loi = lo[i], hii = hi[i], axt = axt_v[i];
         const double axk = tile_pieces_sum(part, i, m, pcnt);
-        const double v = yv - sigma * (2.0 * axt - axk);
-        const double ytv = v + sigma * clampd(-v / sigma, loi, hii);
+        const double ytv = prox_y(yv, sigma, 2.0 * axt - axk, loi, hii);
         yt[i] = ytv;
         chk_row_accumulate(a, ytv, yv, y0[i], axt, axk, loi, hii, dr[i]);
     }
@@ -2076,21 +2075,31 @@ static __global__ __launch_bounds__(kBlock) void k_tile_fill_sorted(int64_t n_ou
 // Ruiz / Pock-Chambolle passes on the UNSCALED matrix with the current dr, dc:
 //   mode 0: out_i = dr_i * max_e |a_e| dc_col(e)     mode 1: out_i = dr_i * sum_e |a_e| dc_col(e)
 // (the same kernel serves columns through the CSC mirror with the roles of dr/dc swapped)
-template <int G>
-__global__ __launch_bounds__(kBlock) void k_scale_stat(int64_t m, const int64_t* __restrict__ ptr,
-                                                       const int32_t* __restrict__ idx, const double* __restrict__ val,
-                                                       const double* __restrict__ dself, const double* __restrict__ dother,
-                                                       int mode, double* __restrict__ out) {
+// SKIP: rows longer than skip_longer are left to k_scale_stat_long (one 1024-thread workgroup per long row)
+template <int G, bool SKIP>
+__device__ __forceinline__ void scale_stat_body(int64_t m, const int64_t* __restrict__ ptr,
+                                                const int32_t* __restrict__ idx, const double* __restrict__ val,
+                                                const double* __restrict__ dself, const double* __restrict__ dother,
+                                                int mode, double* __restrict__ out, int64_t skip_longer) {
     const int64_t i = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / G;
     const int lane = threadIdx.x & (G - 1);
     if (i >= m) return;
+    const int64_t beg = ptr[i], end = ptr[i + 1];
+    if (SKIP && end - beg > skip_longer) return;
     double acc = 0.0;
-    for (int64_t e = ptr[i] + lane; e < ptr[i + 1]; e += G) {
+    for (int64_t e = beg + lane; e < end; e += G) {
         const double v = fabs(val[e]) * dother[idx[e]];
         acc = mode ? acc + v : fmax(acc, v);
     }
     acc = mode ? group_sum<G>(acc) : group_max<G>(acc);
     if (lane == 0) out[i] = dself[i] * acc;
+}
+template <int G>
+__global__ __launch_bounds__(kBlock) void k_scale_stat(int64_t m, const int64_t* __restrict__ ptr,
+                                                       const int32_t* __restrict__ idx, const double* __restrict__ val,
+                                                       const double* __restrict__ dself, const double* __restrict__ dother,
+                                                       int mode, double* __restrict__ out) {
+    scale_stat_body<G, false>(m, ptr, idx, val, dself, dother, mode, out, 0);
 }
 // statistic and update in one launch: dnew_i = dself_i / sqrt(dself_i * stat_i) (unchanged where the statistic is 0 or not
 // finite) -- the arithmetic of k_scale_stat followed by k_scale_apply2, without the third launch of every pass.  Rows and
@@ -2132,24 +2141,13 @@ static __global__ __launch_bounds__(kBlock) void k_scale_stat_upd_both(int64_t m
     else
         scale_stat_upd_side((int64_t)(blockIdx.x - br) * kBlock + threadIdx.x, gc, n, cptr, cidx, cval, dc, dr, mode, dc_new, cap_c);
 }
-// the same with the long rows left to k_scale_stat_long (one 1024-thread workgroup per long row)
+// the same with the long rows left to k_scale_stat_long
 template <int G>
 __global__ __launch_bounds__(kBlock) void k_scale_stat_skip(int64_t m, const int64_t* __restrict__ ptr,
                                                             const int32_t* __restrict__ idx, const double* __restrict__ val,
                                                             const double* __restrict__ dself, const double* __restrict__ dother,
                                                             int mode, double* __restrict__ out, int64_t skip_longer) {
-    const int64_t i = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / G;
-    const int lane = threadIdx.x & (G - 1);
-    if (i >= m) return;
-    const int64_t beg = ptr[i], end = ptr[i + 1];
-    if (end - beg > skip_longer) return;
-    double acc = 0.0;
-    for (int64_t e = beg + lane; e < end; e += G) {
-        const double v = fabs(val[e]) * dother[idx[e]];
-        acc = mode ? acc + v : fmax(acc, v);
-    }
-    acc = mode ? group_sum<G>(acc) : group_max<G>(acc);
-    if (lane == 0) out[i] = dself[i] * acc;
+    scale_stat_body<G, true>(m, ptr, idx, val, dself, dother, mode, out, skip_longer);
 }
 static __global__ __launch_bounds__(1024) void k_scale_stat_long(const int32_t* __restrict__ rows, const int64_t* __restrict__ ptr,
                                                           const int32_t* __restrict__ idx, const double* __restrict__ val,
@@ -2162,7 +2160,7 @@ static __global__ __launch_bounds__(1024) void k_scale_stat_long(const int32_t* 
         const double v = fabs(val[e]) * dother[idx[e]];
         acc = mode ? acc + v : fmax(acc, v);
     }
-    acc = mode ? group_sum<64>(acc) : group_max<64>(acc);
+    acc = mode ? group_sum<64>(acc) : group_max<64>(acc);     // (sum or maximum by `mode`: not block_sum)
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -2171,13 +2169,7 @@ static __global__ __launch_bounds__(1024) void k_scale_stat_long(const int32_t* 
         out[i] = dself[i] * a;
     }
 }
-static __global__ __launch_bounds__(kBlock) void k_scale_apply(int64_t m, double* __restrict__ d, const double* __restrict__ stat) {
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= m) return;
-    const double s = stat[i];
-    if (s > 0.0 && isfinite(s)) d[i] /= sqrt(s);
-}
-// rows and columns in one launch.  cap_c bounds the column factors: in the epigraph-shifted working form a column that
+// d_i /= sqrt(stat_i), rows and columns in one launch.  cap_c bounds the column factors: in the epigraph-shifted working form a column that
 // occurs only in the dense cuts holds nothing but DIFFERENCES of nearly equal derivatives (1e-7 ... rounding noise); the
 // equilibration would blow such a column up by that factor and its cost with it (||c^|| 1e17 seen: primal weight and
 // tolerances meaningless).  A smaller factor than Pock-Chambolle's keeps ||A^||_2 <= 1.  (inf for every other solve.)
@@ -2293,12 +2285,6 @@ static __global__ __launch_bounds__(kBlock) void k_unscale(int64_t n, const doub
     if (i < n) z[i] = zh[i] * d[i];
 }
 
-static __global__ __launch_bounds__(kBlock) void k_div_vec(int64_t n, const double* __restrict__ a, const double* __restrict__ d,
-                                                    double* __restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i < n) out[i] = a[i] / d[i];
-}
-
 // ---------------------------------------------------------- generic vector ops ----
 template <int G>
 __global__ __launch_bounds__(kBlock) void k_spmv(int64_t m, SpMat A, const double* __restrict__ v, double* __restrict__ out) {
@@ -2312,6 +2298,7 @@ __global__ __launch_bounds__(kBlock) void k_spmv(int64_t m, SpMat A, const doubl
 }
 // Row-side products of a matrix with a few LONG rows (dense epigraph cuts): the lane groups skip them and one 1024-thread
 // workgroup per long row does them (k_spmv_long) -- a 1e4-entry row given to a 32-lane group made the whole launch wait 60 us.
+// (Not one body with k_spmv, for the reason given at k_pdhg_x_skip.)
 template <int G>
 __global__ __launch_bounds__(kBlock) void k_spmv_skip(int64_t m, SpMat A, const double* __restrict__ v, double* __restrict__ out,
                                                       int64_t skip_longer) {
@@ -2331,14 +2318,8 @@ static __global__ __launch_bounds__(1024) void k_spmv_long(const int32_t* __rest
     const int64_t i = rows[blockIdx.x];
     double acc = 0.0;
     for (int64_t e = A.ptr[i] + threadIdx.x; e < A.ptr[i + 1]; e += 1024) acc += A.val[e] * v[A.idx[e]];
-    acc = group_sum<64>(acc);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double a = 0.0;
-        for (int k = 0; k < 1024 / 64; ++k) a += sh[k];
-        out[i] = a;
-    }
+    const double a = block_sum<1024>(acc, sh);
+    if (threadIdx.x == 0) out[i] = a;
 }
 // partials[b] = sum over the block's grid-stride share of a_i * b_i  (b may alias a)
 static __global__ __launch_bounds__(kBlock) void k_dot_partial(int64_t n, const double* __restrict__ a, const double* __restrict__ b,
@@ -2346,14 +2327,8 @@ static __global__ __launch_bounds__(kBlock) void k_dot_partial(int64_t n, const 
     double acc = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) acc += a[i] * b[i];
     __shared__ double sh[kBlock / 64];
-    acc = group_sum<64>(acc);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double v = 0.0;
-        for (int k = 0; k < kBlock / 64; ++k) v += sh[k];
-        partials[blockIdx.x] = v;
-    }
+    const double v = block_sum<kBlock>(acc, sh);
+    if (threadIdx.x == 0) partials[blockIdx.x] = v;
 }
 // The four sums every LP solve needs before its first step -- ||A^||_F^2, ||c^||^2 and the finite parts of ||lo^||^2, ||hi^||^2 -- in ONE
 // launch (+ one final): partials[q * gridDim + b].  Each sum runs over its array exactly as k_dot_partial / k_finite_sq_partial
@@ -2368,6 +2343,7 @@ static __global__ __launch_bounds__(kBlock) void k_setup_norms_partial(int64_t n
     for (int64_t i = t0; i < m; i += stride) { const double v = lo[i]; if (isfinite(v)) acc[2] += v * v; }
     for (int64_t i = t0; i < m; i += stride) { const double v = hi[i]; if (isfinite(v)) acc[3] += v * v; }
     __shared__ double sh[4][kBlock / 64];
+    // (not block_sum: thread q finishes quantity q)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const double v = group_sum<64>(acc[q]);
@@ -2385,14 +2361,8 @@ static __global__ __launch_bounds__(kRedBlocks) void k_sum_final_multi(const dou
     __shared__ double sh[kRedBlocks / 64];
     const double* p = partials + (int64_t)blockIdx.x * nblocks;
     double v = ((int)threadIdx.x < nblocks) ? p[threadIdx.x] : 0.0;
-    v = group_sum<64>(v);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int k = 0; k < kRedBlocks / 64; ++k) t += sh[k];
-        out[blockIdx.x] = t;
-    }
+    const double t = block_sum<kRedBlocks>(v, sh);
+    if (threadIdx.x == 0) out[blockIdx.x] = t;
 }
 // partials[b] = sum of log|a_i| (and |b_i|, b optional) over the finite non-zero entries, partials[gridDim + b] = their count:
 // a magnitude statistic that a handful of outliers cannot move (see Engine::lp_solve_core, the initial primal weight)
@@ -2405,46 +2375,16 @@ static __global__ __launch_bounds__(kBlock) void k_logabs_partial(int64_t n, con
         if (b) { const double v = fabs(b[i]); if (v > 0.0 && isfinite(v)) { ls += log(v); cnt += 1.0; } }
     }
     __shared__ double sh[2][kBlock / 64];
-    ls = group_sum<64>(ls); cnt = group_sum<64>(cnt);
-    if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = ls; sh[1][threadIdx.x >> 6] = cnt; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double u = 0.0, v = 0.0;
-        for (int k = 0; k < kBlock / 64; ++k) { u += sh[0][k]; v += sh[1][k]; }
-        partials[blockIdx.x] = u; partials[gridDim.x + blockIdx.x] = v;
-    }
-}
-// partials[b] = sum of (a_i d_i)^2: the squared norm of a vector in scaled coordinates without materialising it
-static __global__ __launch_bounds__(kBlock) void k_scaled_sq_partial(int64_t n, const double* __restrict__ a, const double* __restrict__ d,
-                                                              double* __restrict__ partials) {
-    double acc = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) { const double v = a[i] * d[i]; acc += v * v; }
-    __shared__ double sh[kBlock / 64];
-    acc = group_sum<64>(acc);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double v = 0.0;
-        for (int k = 0; k < kBlock / 64; ++k) v += sh[k];
-        partials[blockIdx.x] = v;
-    }
+    double r[2] = {ls, cnt};
+    block_sum<kBlock>(r, sh);
+    if (threadIdx.x == 0) { partials[blockIdx.x] = r[0]; partials[gridDim.x + blockIdx.x] = r[1]; }
 }
 static __global__ __launch_bounds__(kRedBlocks) void k_sum_final(const double* __restrict__ partials, int nblocks,
                                                           double* __restrict__ out) {
     __shared__ double sh[kRedBlocks / 64];
     double v = ((int)threadIdx.x < nblocks) ? partials[threadIdx.x] : 0.0;
-    v = group_sum<64>(v);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int k = 0; k < kRedBlocks / 64; ++k) t += sh[k];
-        out[0] = t;
-    }
-}
-static __global__ __launch_bounds__(kBlock) void k_scale_vec(int64_t n, double* __restrict__ z, double s) {
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i < n) z[i] *= s;
+    const double t = block_sum<kRedBlocks>(v, sh);
+    if (threadIdx.x == 0) out[0] = t;
 }
 // out = a / sqrt(*normsq)  (normalisation of the power iteration without a host round trip)
 static __global__ __launch_bounds__(kBlock) void k_normalize(int64_t n, const double* __restrict__ a, const double* __restrict__ normsq,
@@ -2460,14 +2400,8 @@ static __global__ __launch_bounds__(kRedBlocks) void k_normalize_sum(int64_t n, 
     __shared__ double sh[kRedBlocks / 64];
     __shared__ double s_tot;
     double v = partials[threadIdx.x];
-    v = group_sum<64>(v);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int k = 0; k < kRedBlocks / 64; ++k) t += sh[k];
-        s_tot = t;
-    }
+    const double t = block_sum<kRedBlocks>(v, sh);
+    if (threadIdx.x == 0) s_tot = t;
     __syncthreads();
     const double s = s_tot;
     const int64_t i = (int64_t)blockIdx.x * kRedBlocks + threadIdx.x;
@@ -2696,14 +2630,8 @@ static __global__ __launch_bounds__(kBlock) void k_sum_partial(int64_t n, const 
     double acc = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) acc += a[i];
     __shared__ double sh[kBlock / 64];
-    acc = group_sum<64>(acc);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double v = 0.0;
-        for (int k = 0; k < kBlock / 64; ++k) v += sh[k];
-        partials[blockIdx.x] = v;
-    }
+    const double v = block_sum<kBlock>(acc, sh);
+    if (threadIdx.x == 0) partials[blockIdx.x] = v;
 }
 
 // ---------------------------------------------------------- epigraph reference shift ----
@@ -2806,14 +2734,8 @@ static __global__ __launch_bounds__(kBlock) void k_finite_sq_partial(int64_t n, 
         if (isfinite(v)) acc += v * v;
     }
     __shared__ double sh[kBlock / 64];
-    acc = group_sum<64>(acc);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double v = 0.0;
-        for (int k = 0; k < kBlock / 64; ++k) v += sh[k];
-        partials[blockIdx.x] = v;
-    }
+    const double v = block_sum<kBlock>(acc, sh);
+    if (threadIdx.x == 0) partials[blockIdx.x] = v;
 }
 
 static __global__ __launch_bounds__(kBlock) void k_hash_fill(int64_t n, double* __restrict__ z) {
