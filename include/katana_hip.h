@@ -57,6 +57,16 @@ extern "C" {
                             derivatives come from the caller's own eval_g / eval_jac_g / eval_f / eval_grad_f through
                             the callbacks below, once per sweep; isconstrsat, gencut, round_coefs, _addcut and the LP
                             still run on the device (SURVEY.md section 8b "Evaluator consumed")                     */
+#define KTN_ROW_QUAD 3   /* sparse quadratic, declared by the caller (the LP/QP surface, src/solver.jl:46):
+                            g_i(x) = rconst_i + sum_e a_e x[c_e] + 1/2 sum_e x[c_e] sum_{k in seg(e)} q_k x[qcol_k]
+                            e runs over the row's Jacobian entries [rowptr[i], rowptr[i+1]); a_e = p0[e] (p1 and atom_kind are
+                            ignored, as for tape rows); seg(e) = [quad_ptr[e], quad_ptr[e+1]) is row c_e of the SYMMETRIC Q_i,
+                            stored in full -- both (r, c) and (c, r).  Symmetry is the caller's contract and is NOT checked:
+                            the gradient entry is computed as a_e + s_e with s_e = sum_k q_k x[qcol_k], which is the
+                            derivative only of a symmetric Q_i.  Every qcol_k must be a column of the row's own structure.
+                            ktn_optimize_blocks falls back to the ordinary loop on such rows, the supporting-hyperplane
+                            root search keeps Kelley's cut on them; row-sharding them is untested and the Python host
+                            mirror refuses it                                                                         */
 
 /* MathProgBase.eval_g + eval_jac_g (src/separators.jl:112-113) for the KTN_ROW_HOST rows: write g[i] and
  * jac[rowptr[i] .. rowptr[i+1]) (CSR order of ktn_nlp_desc) for every such row i; other entries are ignored.
@@ -219,7 +229,7 @@ typedef struct {
     const double*  tape_arg;
     /* objective f(x): isobjlinear src/model.jl:125; same two forms                  */
     int32_t obj_linear;
-    int32_t obj_kind;           /* KTN_ROW_SEP, KTN_ROW_TAPE or KTN_ROW_HOST         */
+    int32_t obj_kind;           /* KTN_ROW_SEP, KTN_ROW_TAPE, KTN_ROW_HOST or KTN_ROW_QUAD */
     int64_t obj_nnz;            /* separable objective entries                       */
     const int32_t* obj_col;
     const uint8_t* obj_atom_kind;
@@ -229,6 +239,18 @@ typedef struct {
     int64_t        obj_tape_len;
     const int32_t* obj_tape_op;
     const double*  obj_tape_arg;
+    /* sparse-quadratic rows (KTN_ROW_QUAD); all NULL / zero when there are none, so a zero-initialised description of a
+     * caller that does not know these fields keeps its meaning.  (They follow the tape fields; the callback triple below
+     * stays the last three members, which the bindings rely on.) */
+    const int64_t* quad_ptr;    /* [nnz+1] over ALL Jacobian entries, or NULL when there are no KTN_ROW_QUAD rows (the
+                                   tape_ptr convention); the segments of the entries of other rows must be empty        */
+    const int32_t* quad_col;    /* [qnnz] column of the second factor (0-based, a column of the row's structure)       */
+    const double*  quad_val;    /* [qnnz] q_k                                                                          */
+    /* objective with obj_kind = KTN_ROW_QUAD: obj_col / obj_p0 are the structure and the linear part a, obj_const the
+     * constant, obj_quad_ptr [obj_nnz+1] the segments (NULL: no quadratic part) */
+    const int64_t* obj_quad_ptr;
+    const int32_t* obj_quad_col;
+    const double*  obj_quad_val;
     /* host-evaluator fallback (KTN_ROW_HOST rows / objective); NULL when unused.  Called on the thread that is
      * inside ktn_loadproblem / ktn_optimize / ktn_ecp_step / ktn_sep_precompute / ktn_sep_sweep.            */
     ktn_eval_rows_cb eval_rows;
@@ -366,12 +388,14 @@ int ktn_get_lp_sol(ktn_handle h, int64_t k, double* x_out, int64_t n);
  *        "sweep_batched"        1 when the sweep is the batch-blocked one (many short rows)
  *        "precompute_multirow"  1 when precompute! runs four rows per lane group
  *        "sep_long_rows"        rows beyond 8 192 entries, evaluated one workgroup per row
+ *        "quad_rows" "quad_nnz" KTN_ROW_QUAD rows (the epigraph row of a KTN_ROW_QUAD objective included) and their Q entries
+ *        "quad_group"           lanes per Jacobian entry G of k_quad_jac (4 .. 64), from the mean segment length; 0 without such rows
  * which form of the LP kernels the last ktn_lp_script ran (written by it, for tests):
  *        "lp_grp_rows" "lp_grp_cols" lanes per row / column G;   "lp_packed" "lp_packed_trips" packed records on, outputs per group T
  *        "lp_long_rows" "lp_long_cols" rows / columns beyond 2 048 entries;   "lp_tiled" "lp_tiled_check" "lp_tiled_pieces"
  *        "lp_check_spec"        1 when the last check left the next iterate in xnext / ynext;   "lp_check_pinned"
  *        "lp_scale_fused_passes" "lp_scale_split_passes"  equilibration passes in the one-launch / three-kernel form (counters)
- * with params.profile = 1, per hot kernel K in {kx, ky, sweep_eval}:
+ * with params.profile = 1, per hot kernel K in {kx, ky, sweep_eval, tape_eval, quad_eval}:
  *        "K_time_s" "K_launches" "K_bytes"  from the start/stop hipEvents of hipExtLaunchKernelGGL
  *        on the engine's own stream (dispatch begin/end, as rocprofv3 --kernel-trace reports) */
 double ktn_get_stat(ktn_handle h, const char* name);

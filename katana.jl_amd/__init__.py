@@ -15,13 +15,14 @@ a model without one raises.
 """
 from . import _lib
 from .expr import Expr, var, const, exp, log, sqrt, sin, cos, from_sexpr
-from .nlp import NLPDescription, SeparableNLP, ExprNLP, CallbackNLP, Problem, fuse_problems
-from .solver import (KatanaSolver, KatanaNonlinearModel, KatanaHipSeparator, NonlinearModel,
+from .nlp import NLPDescription, SeparableNLP, ExprNLP, CallbackNLP, QuadNLP, Problem, fuse_problems
+from .solver import (KatanaSolver, KatanaNonlinearModel, KatanaHipSeparator, NonlinearModel, LinearQuadraticModel,
+                     quad_triplets_to_engine,
                      getKatanaModel, getKatanaCuts, getKatanaSols, STATUS_SYMBOLS)
 from .jump_like import Model
 from . import instances
 from .batch import solve_batch, solve_batch_sharded
 
 __all__ = ["KatanaSolver", "KatanaNonlinearModel", "KatanaHipSeparator", "NonlinearModel", "getKatanaModel",
-           "getKatanaCuts", "getKatanaSols", "NLPDescription", "SeparableNLP", "ExprNLP", "CallbackNLP", "Problem", "fuse_problems", "Model", "Expr", "var",
+           "getKatanaCuts", "getKatanaSols", "LinearQuadraticModel", "quad_triplets_to_engine", "QuadNLP", "NLPDescription", "SeparableNLP", "ExprNLP", "CallbackNLP", "Problem", "fuse_problems", "Model", "Expr", "var",
            "const", "exp", "log", "sqrt", "sin", "cos", "from_sexpr", "instances", "STATUS_SYMBOLS", "solve_batch", "solve_batch_sharded"]

@@ -9,7 +9,7 @@ KTN_OK = 0
 E_INVALID, E_NODEVICE, E_HIP, E_NOMEM, E_UNSUPPORTED = -1, -2, -3, -4, -5
 STATUS_NONE, STATUS_OPTIMAL, STATUS_UNBOUNDED, STATUS_INFEASIBLE, STATUS_USERLIMIT, STATUS_ERROR = range(6)
 MIN, MAX = 0, 1
-ROW_SEP, ROW_TAPE, ROW_HOST = 0, 1, 2
+ROW_SEP, ROW_TAPE, ROW_HOST, ROW_QUAD = 0, 1, 2, 3
 ATOM_LIN, ATOM_QUAD, ATOM_EXP, ATOM_NEGLOG = 0, 1, 2, 3
 CUT_KELLEY, CUT_SUPPORTING = 0, 1          # ktn_params.cut_algo
 LPOP_STEP, LPOP_CHECK, LPOP_ADVANCE, LPOP_RESTART = range(4)      # ktn_lp_script ops
@@ -40,6 +40,8 @@ class KtnNlpDesc(C.Structure):
                 ("tape_arg", P(c_f64)), ("obj_linear", c_i32), ("obj_kind", c_i32), ("obj_nnz", c_i64),
                 ("obj_col", P(c_i32)), ("obj_atom_kind", P(c_u8)), ("obj_p0", P(c_f64)), ("obj_p1", P(c_f64)),
                 ("obj_const", c_f64), ("obj_tape_len", c_i64), ("obj_tape_op", P(c_i32)), ("obj_tape_arg", P(c_f64)),
+                ("quad_ptr", P(c_i64)), ("quad_col", P(c_i32)), ("quad_val", P(c_f64)),
+                ("obj_quad_ptr", P(c_i64)), ("obj_quad_col", P(c_i32)), ("obj_quad_val", P(c_f64)),
                 ("eval_rows", C.c_void_p), ("eval_obj", C.c_void_p), ("eval_user", C.c_void_p)]
 
 

@@ -69,6 +69,7 @@ struct DevParams {
     int sweep_batched = -1;        // KTN_SWEEP_BATCHED    0 = row kernel instead of the batch-blocked sweep for many short rows, 1 = always
     int tape_classed = -1;         // KTN_TAPE_CLASSED     tape rows by shape class (k_tape_classed): -1 = classes of >= 64 rows, 0 = interpreter for
                                    //                      every tape row, 1 = every class of >= 2 rows
+    int quad_group = 0;            // KTN_QUAD_GROUP       lanes per Jacobian entry of k_quad_jac (0 = by mean segment length)
     int tiled_wg = 2;              // KTN_TILED_WG         workgroups per CU of k_spmv_tiled
     int ecp_power = 20;            // KTN_ECP_POWER        power passes of the device-side batch loop
     int grp_rows = 0, grp_cols = 0;// KTN_GRP_ROWS / COLS  lanes per LP row / column (0 = by average length)
@@ -96,6 +97,7 @@ struct DevParams {
         force_collective = flag("KTN_FORCE_COLLECTIVE");
         sweep_rows = geti("KTN_SWEEP_ROWS", sweep_rows); blk_cfg = geti("KTN_BLK_CFG", blk_cfg); sweep_blocked = geti("KTN_SWEEP_BLOCKED", sweep_blocked);
         sweep_batched = geti("KTN_SWEEP_BATCHED", sweep_batched); tape_classed = geti("KTN_TAPE_CLASSED", tape_classed);
+        quad_group = geti("KTN_QUAD_GROUP", quad_group);
         tiled_wg = geti("KTN_TILED_WG", tiled_wg); ecp_power = geti("KTN_ECP_POWER", ecp_power);
         grp_rows = geti("KTN_GRP_ROWS", grp_rows); grp_cols = geti("KTN_GRP_COLS", grp_cols); tiled = geti("KTN_TILED", tiled);
         smax_reuse = getd("KTN_SMAX_REUSE", smax_reuse); power_passes = geti("KTN_POWER_PASSES", power_passes);
@@ -178,6 +180,16 @@ struct Engine {
     void build_tape_classes(const std::vector<int64_t>& nodeptr, const std::vector<int32_t>& nop, const std::vector<int32_t>& na,
                             const std::vector<int32_t>& nb, const std::vector<double>& nc, const std::vector<int32_t>& tape_all);
     TapeClassDev tape_class_view();
+    // KTN_ROW_QUAD rows (quad_rows.hpp; built by build_quad_rows at load): the Q entries in two streams, the QUAD rows' Jacobian
+    // entries numbered in row order, and two launch lists -- all QUAD rows (precompute_all), those among the NL rows (sweep)
+    int64_t n_quad = 0, n_quad_nl = 0, n_quad_ent = 0, n_quad_ent_nl = 0, quad_nnz = 0;
+    int grp_quad = 4, grp_quad_rows = 4;
+    double quad_bytes = 0.0;                   // algorithmic bytes of one evaluation of the NL QUAD rows
+    DBuf<int32_t> d_qcol, d_qrows_all, d_qrows_nl;
+    DBuf<double> d_qval, d_qvterm;
+    DBuf<int64_t> d_qptr, d_qjidx, d_qslots_all, d_qslots_nl, d_qtbase_all, d_qtbase_nl, d_qent_nl;
+    void build_quad_rows(const ktn_nlp_desc* d);
+    void launch_quad(bool nl_only, const double* d_x, double f_tol);
     // sweep state
     DBuf<double> d_g, d_jac, d_bconst, d_maxc, d_xs, d_ray, d_scal;
     DBuf<int32_t> d_nonfin, d_violslots, d_anynf;
@@ -474,7 +486,7 @@ struct Engine {
     // profile mode: the timed launches go through hipExtLaunchKernelGGL, whose start/stop events
     // carry the dispatch's own begin/end timestamps (what rocprofv3 --kernel-trace reports)
     void ev_flush() {   // stream must be synchronised
-        static const char* names[5] = {"kx", "ky", "sweep_eval", "allreduce", "tape_eval"};
+        static const char* names[6] = {"kx", "ky", "sweep_eval", "allreduce", "tape_eval", "quad_eval"};
         for (auto& r : ev_recs) {
             float ms = 0.f;
             if (hipEventElapsedTime(&ms, ev_pool[r.a], ev_pool[r.b]) == hipSuccess) {

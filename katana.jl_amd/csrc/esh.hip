@@ -9,7 +9,7 @@ namespace ktn {
 
 // At load (the caller's description is valid only now): which rows take part, and the auxiliary min-max problem
 //     min s   over (x, s), s in [-1, +inf):   linear rows as they are;   g_i(x) - s <= ub_i  /  g_i(x) + s >= lb_i  per taking-part row
-// (a separable row gains a LIN atom on s, a tape row VAR s and SUB / ADD; every other row is dropped).
+// (a separable row gains a LIN atom on s, a tape row VAR s and SUB / ADD; every other nonlinear row is dropped).
 void Engine::esh_build_aux(const double* l_var, const double* u_var, const double* l_constr, const double* u_constr,
                            const ktn_nlp_desc* d) {
     delete child;
@@ -45,12 +45,15 @@ void Engine::esh_build_aux(const double* l_var, const double* u_var, const doubl
         const uint8_t kind = d->row_kind ? d->row_kind[i] : KTN_ROW_SEP;
         const bool lin = d->row_linear && d->row_linear[i];
         const int side = h_esh_side[(size_t)i];
-        if (kind == KTN_ROW_HOST || (!lin && side == 0)) continue;
+        // (only separable and tape rows have a program the auxiliary problem can carry: host-evaluated rows and nonlinear QUAD rows
+        //  are dropped; a QUAD row declared linear has an empty Q and goes in as the separable row of LIN atoms it is)
+        const bool quad_lin = kind == KTN_ROW_QUAD && lin;
+        if ((kind != KTN_ROW_SEP && kind != KTN_ROW_TAPE && !quad_lin) || (!lin && side == 0)) continue;
         for (int64_t e = d->rowptr[i]; e < d->rowptr[i + 1]; ++e) {
             A.col.push_back(d->col[e]);
-            A.akind.push_back(d->atom_kind ? d->atom_kind[e] : 0);
+            A.akind.push_back(d->atom_kind && !quad_lin ? d->atom_kind[e] : 0);
             A.p0.push_back(d->p0 ? d->p0[e] : 0.0);
-            A.p1.push_back(d->p1 ? d->p1[e] : 0.0);
+            A.p1.push_back(d->p1 && !quad_lin ? d->p1[e] : 0.0);
         }
         if (kind == KTN_ROW_TAPE) {
             for (int64_t t = d->tape_ptr[i]; t < d->tape_ptr[i + 1]; ++t) { A.top.push_back(d->tape_op[t]); A.targ.push_back(d->tape_arg[t]); }
@@ -68,7 +71,7 @@ void Engine::esh_build_aux(const double* l_var, const double* u_var, const doubl
         }
         A.rowptr.push_back((int64_t)A.col.size());
         A.tptr.push_back((int64_t)A.top.size());
-        A.kind.push_back(kind);
+        A.kind.push_back(quad_lin ? (uint8_t)KTN_ROW_SEP : kind);
         A.lin.push_back(lin ? 1 : 0);
         A.rconst.push_back(d->rconst ? d->rconst[i] : 0.0);
         A.lc.push_back(l_constr[i]);

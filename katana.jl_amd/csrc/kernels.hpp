@@ -354,7 +354,7 @@ __global__ __launch_bounds__(kBlock) void k_sep_sweep(NlpDev P, const int32_t* _
 // kernel evaluates them, one 1 024-thread workgroup per row (thread-strided partial sums, wavefront butterflies, the block's
 // wavefronts in order: a fixed summation order).
 constexpr int kLongEval = 8192;
-constexpr uint8_t kRowSepLong = 3;
+constexpr uint8_t kRowSepLong = 4;          // (device-side only; 3 is KTN_ROW_QUAD)
 static __global__ __launch_bounds__(1024) void k_sep_eval_long(NlpDev P, const int32_t* __restrict__ rows, const int64_t* __restrict__ slots,
                                                         const double* __restrict__ x, double f_tol, int flags_on, SweepOut O) {
     __shared__ double sh[16][3];
@@ -792,7 +792,7 @@ static __global__ __launch_bounds__(kBlock) void k_gj_stats(NlpDev P, const int3
     const int64_t gid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (gid >= m_nl) return;
     const int32_t r = nl_rows[gid];
-    if (kind_filter >= 0 && (P.row_kind[r] == KTN_ROW_SEP || P.row_kind[r] == 3)) return;     // tape rows and host-evaluated rows (3 = kRowSepLong: k_sep_eval_long's)
+    if (kind_filter >= 0 && (P.row_kind[r] == KTN_ROW_SEP || P.row_kind[r] == kRowSepLong || P.row_kind[r] == KTN_ROW_QUAD)) return;     // tape rows and host-evaluated rows (k_sep_eval_long's and k_quad_stats' rows have theirs)
     if (classed && classed[r]) return;                                                        // k_tape_classed has done this row's part
     const int64_t beg = P.rowptr[r], end = P.rowptr[r + 1];
     const double g = O.g[r];

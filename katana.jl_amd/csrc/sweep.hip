@@ -6,6 +6,7 @@
 #include "launch.hpp"
 #include "kernels.hpp"
 #include "tape_classes.hpp"
+#include "quad_rows.hpp"
 #include "batch_lp.hpp"
 #include "batch_ecp.hpp"
 
@@ -284,6 +285,126 @@ TapeClassDev Engine::tape_class_view() {
     return T;
 }
 
+// ------------------------------------------------------------------------------------
+// KTN_ROW_QUAD rows (quad_rows.hpp): validation of the caller's quad_* arrays and the device layout.  Host work and uploads
+// only; called from loadproblem once the extended structure and the NL row list stand.
+// ------------------------------------------------------------------------------------
+void Engine::build_quad_rows(const ktn_nlp_desc* d) {
+    n_quad = n_quad_nl = n_quad_ent = n_quad_ent_nl = quad_nnz = 0;
+    quad_bytes = 0.0;
+    stats["quad_rows"] = stats["quad_nnz"] = stats["quad_group"] = 0.0;
+    const int64_t nnz0 = h_rowptr[(size_t)m0];
+    std::vector<int32_t> qrows;
+    bool constr_quad = false;
+    for (int64_t i = 0; i < m_ext; ++i)
+        if (h_rowkind[(size_t)i] == KTN_ROW_QUAD) { qrows.push_back((int32_t)i); if (i < m0) constr_quad = true; }
+    KTN_REQUIRE(!constr_quad || d->quad_ptr != nullptr, "KTN_ROW_QUAD rows without quad_ptr");
+    if (d->quad_ptr) {
+        KTN_REQUIRE(d->quad_ptr[0] >= 0, "quad_ptr not monotone");
+        for (int64_t e = 0; e < nnz0; ++e) KTN_REQUIRE(d->quad_ptr[e + 1] >= d->quad_ptr[e], "quad_ptr not monotone");
+        for (int64_t i = 0; i < m0; ++i)
+            KTN_REQUIRE(h_rowkind[(size_t)i] == KTN_ROW_QUAD || d->quad_ptr[h_rowptr[(size_t)i + 1]] == d->quad_ptr[h_rowptr[(size_t)i]],
+                        "quad_ptr: a row that is not KTN_ROW_QUAD has a non-empty segment");
+        KTN_REQUIRE(d->quad_ptr[nnz0] == 0 || (d->quad_col != nullptr && d->quad_val != nullptr), "quad_ptr without quad_col / quad_val");
+    }
+    const bool obj_quad = h_rowkind[(size_t)m0] == KTN_ROW_QUAD;
+    if (obj_quad && d->obj_quad_ptr) {
+        KTN_REQUIRE(d->obj_quad_ptr[0] >= 0, "obj_quad_ptr not monotone");
+        for (int64_t e = 0; e < d->obj_nnz; ++e) KTN_REQUIRE(d->obj_quad_ptr[e + 1] >= d->obj_quad_ptr[e], "obj_quad_ptr not monotone");
+        KTN_REQUIRE(d->obj_quad_ptr[d->obj_nnz] == 0 || (d->obj_quad_col != nullptr && d->obj_quad_val != nullptr),
+                    "obj_quad_ptr without obj_quad_col / obj_quad_val");
+        KTN_REQUIRE(!(d->obj_linear && d->obj_quad_ptr[d->obj_nnz] > d->obj_quad_ptr[0]), "obj_linear = 1 with a non-empty objective Q");
+    }
+    if (qrows.empty()) {
+        d_qcol.release(); d_qval.release(); d_qptr.release(); d_qjidx.release(); d_qvterm.release();
+        return;
+    }
+    std::vector<int32_t> qcol;
+    std::vector<double> qval;
+    std::vector<int64_t> qptr(1, 0), jidx, tbase;
+    std::vector<uint8_t> in_row((size_t)n0 + 1, 0);
+    for (int32_t i : qrows) {
+        const int64_t rb = h_rowptr[(size_t)i], re = h_rowptr[(size_t)i + 1];
+        const bool obj = i == m0;
+        const int64_t* ptr = obj ? d->obj_quad_ptr : d->quad_ptr;
+        const int32_t* qc = obj ? d->obj_quad_col : d->quad_col;
+        const double* qv = obj ? d->obj_quad_val : d->quad_val;
+        const int64_t own = obj ? d->obj_nnz : re - rb;            // (the epigraph row's last entry, t, has no segment)
+        const int64_t eb = obj ? 0 : rb;
+        for (int64_t e = 0; e < own; ++e) in_row[(size_t)h_col[(size_t)(rb + e)]] = 1;
+        tbase.push_back((int64_t)jidx.size());
+        const int64_t q0 = (int64_t)qcol.size();
+        for (int64_t e = 0; e < re - rb; ++e) {
+            if (ptr && e < own)
+                for (int64_t k = ptr[eb + e]; k < ptr[eb + e + 1]; ++k) {
+                    const int32_t c = qc[k];
+                    if (c < 0 || c >= n0 || !in_row[(size_t)c]) {
+                        for (int64_t f = 0; f < own; ++f) in_row[(size_t)h_col[(size_t)(rb + f)]] = 0;
+                        throw Error(KTN_E_INVALID, "quad_col: column " + std::to_string(c) + " is not in the structure of row " + std::to_string(i));
+                    }
+                    qcol.push_back(c); qval.push_back(qv[k]);
+                }
+            jidx.push_back(rb + e);
+            qptr.push_back((int64_t)qcol.size());
+        }
+        for (int64_t e = 0; e < own; ++e) in_row[(size_t)h_col[(size_t)(rb + e)]] = 0;
+        if (!obj && d->row_linear && d->row_linear[i])
+            KTN_REQUIRE((int64_t)qcol.size() == q0, "row_linear = 1 on a KTN_ROW_QUAD row with a non-empty Q");
+    }
+    n_quad = (int64_t)qrows.size(); n_quad_ent = (int64_t)jidx.size(); quad_nnz = (int64_t)qcol.size();
+    // launch lists: all QUAD rows; the QUAD rows among the NL rows
+    std::vector<int64_t> nl_slot((size_t)m_ext, -1), slots_all, slots_nl, tbase_nl, ent_nl;
+    std::vector<int32_t> rows_nl;
+    for (size_t si = 0; si < h_nlrows.size(); ++si) nl_slot[(size_t)h_nlrows[si]] = (int64_t)si;
+    int64_t qnnz_nl = 0;
+    for (size_t k = 0; k < qrows.size(); ++k) {
+        const int32_t i = qrows[k];
+        slots_all.push_back(nl_slot[(size_t)i]);
+        if (nl_slot[(size_t)i] < 0) continue;
+        rows_nl.push_back(i); slots_nl.push_back(nl_slot[(size_t)i]); tbase_nl.push_back(tbase[k]);
+        const int64_t len = h_rowptr[(size_t)i + 1] - h_rowptr[(size_t)i];
+        for (int64_t e = 0; e < len; ++e) ent_nl.push_back(tbase[k] + e);
+        qnnz_nl += qptr[(size_t)(tbase[k] + len)] - qptr[(size_t)tbase[k]];
+    }
+    n_quad_nl = (int64_t)rows_nl.size(); n_quad_ent_nl = (int64_t)ent_nl.size();
+    if (n_quad_nl == n_quad) ent_nl.clear();                       // the same list: entry t = position
+    grp_quad = pick_group(n_quad_ent ? (double)quad_nnz / (double)n_quad_ent : 4.0);
+    if (dev.quad_group == 4 || dev.quad_group == 8 || dev.quad_group == 16 || dev.quad_group == 32 || dev.quad_group == 64) grp_quad = dev.quad_group;
+    grp_quad_rows = pick_group((double)n_quad_ent / (double)n_quad);
+    // algorithmic bytes of one evaluation of the NL QUAD rows: 12 per Q entry and 8 per gathered x; per Jacobian entry the segment
+    // pointer, index, (a, -) pair, column, x, Jacobian and value term written and read back; per row its record and outputs
+    quad_bytes = 20.0 * (double)qnnz_nl + (8.0 + 8.0 + 16.0 + 4.0 + 8.0 + 16.0 + 16.0 + 4.0 + 8.0) * (double)n_quad_ent_nl + (28.0 + 16.0 + 48.0) * (double)n_quad_nl;
+    d_qcol.upload(qcol, stream); d_qval.upload(qval, stream); d_qptr.upload(qptr, stream); d_qjidx.upload(jidx, stream);
+    d_qvterm.resize((size_t)n_quad_ent + 1, stream);
+    d_qrows_all.upload(qrows, stream); d_qslots_all.upload(slots_all, stream); d_qtbase_all.upload(tbase, stream);
+    d_qrows_nl.upload(rows_nl, stream); d_qslots_nl.upload(slots_nl, stream); d_qtbase_nl.upload(tbase_nl, stream); d_qent_nl.upload(ent_nl, stream);
+    sync();
+    stats["quad_rows"] = (double)n_quad;
+    stats["quad_nnz"] = (double)quad_nnz;
+    stats["quad_group"] = (double)grp_quad;
+}
+
+// k_quad_jac + k_quad_stats over the QUAD rows among the NL rows (the sweep: flags by NL slot) or over all of them (precompute_all)
+void Engine::launch_quad(bool nl_only, const double* d_x, double f_tol) {
+    const int64_t nr = nl_only ? n_quad_nl : n_quad, ne = nl_only ? n_quad_ent_nl : n_quad_ent;
+    if (nr == 0) return;
+    NlpDev P = nlp_view();
+    SweepOut O = sweep_view();
+    QuadDev Q{d_qcol.p, d_qval.p, d_qptr.p, d_qjidx.p, d_qvterm.p};
+    QuadList L;
+    L.rows = nl_only ? d_qrows_nl.p : d_qrows_all.p;
+    L.slots = nl_only ? d_qslots_nl.p : d_qslots_all.p;
+    L.tbase = nl_only ? d_qtbase_nl.p : d_qtbase_all.p;
+    L.ent = (nl_only && n_quad_nl != n_quad) ? d_qent_nl.p : nullptr;
+    L.n_rows = nr; L.n_ent = ne;
+    size_t ta = 0, tb = 0;
+    const bool ev = prm.profile && nl_only;
+    if (ev) { ta = ev_get(); tb = ev_get(); KTN_HIP(hipEventRecord(ev_pool[ta], stream)); }
+    LAUNCH_G(grp_quad, k_quad_jac, ne, stream, P, Q, L, d_x, O);
+    LAUNCH_G(grp_quad_rows, k_quad_stats, nr, stream, P, Q, L, d_x, f_tol, nl_only ? 1 : 0, O);
+    if (ev) { KTN_HIP(hipEventRecord(ev_pool[tb], stream)); ev_recs.push_back({5, ta, tb, quad_bytes}); }
+}
+
 void Engine::loadproblem(int64_t num_var, int64_t num_constr, const double* l_var, const double* u_var,
                          const double* l_constr, const double* u_constr, int32_t sense_, const ktn_nlp_desc* d) {
     KTN_REQUIRE(d != nullptr, "nlp description is NULL");
@@ -347,6 +468,16 @@ void Engine::loadproblem(int64_t num_var, int64_t num_constr, const double* l_va
         p1.push_back(0.0);
         rconst[m0] = d->obj_const;
         h_rowkind[m0] = KTN_ROW_SEP;
+    } else if (d->obj_kind == KTN_ROW_QUAD) {
+        // f(x) - t as a QUAD row: the caller's entries first, then t with coefficient -1 and an empty segment
+        KTN_REQUIRE(d->obj_nnz == 0 || (d->obj_col != nullptr && d->obj_p0 != nullptr), "KTN_ROW_QUAD objective without obj_col / obj_p0");
+        for (int64_t e = 0; e < d->obj_nnz; ++e) {
+            KTN_REQUIRE(d->obj_col[e] >= 0 && d->obj_col[e] < n0, "objective column out of range");
+            h_col.push_back(d->obj_col[e]); akind.push_back(0); p0.push_back(d->obj_p0[e]); p1.push_back(0.0);
+        }
+        h_col.push_back((int32_t)n0); akind.push_back(0); p0.push_back(-1.0); p1.push_back(0.0);
+        rconst[m0] = d->obj_const;
+        h_rowkind[m0] = KTN_ROW_QUAD;
     } else if (d->obj_kind == KTN_ROW_HOST) {
         // dense row, like the reference's own epigraph row (src/nlpeval.jl:49-54)
         KTN_REQUIRE(d->eval_obj != nullptr, "KTN_ROW_HOST objective without eval_obj callback");
@@ -368,6 +499,10 @@ void Engine::loadproblem(int64_t num_var, int64_t num_constr, const double* l_va
     }
     h_rowptr.push_back((int64_t)h_col.size());
     nnz_ext = (int64_t)h_col.size();
+    for (int64_t i = 0; i < m0; ++i) {                   // atom_kind and p1 are ignored for QUAD rows
+        if (h_rowkind[i] != KTN_ROW_QUAD) continue;
+        for (int64_t e = h_rowptr[i]; e < h_rowptr[i + 1]; ++e) { akind[(size_t)e] = 0; p1[(size_t)e] = 0.0; }
+    }
     padzero[m0] = (h_rowptr[m0 + 1] - h_rowptr[m0]) < (n0 + 1) ? 1 : 0;
 
     lapl("extended structure (host)");
@@ -378,7 +513,7 @@ void Engine::loadproblem(int64_t num_var, int64_t num_constr, const double* l_va
     {
         std::vector<int32_t> hostrows;
         for (int64_t i = 0; i < m_ext; ++i) {
-            KTN_REQUIRE(h_rowkind[i] <= KTN_ROW_HOST, "unknown row kind");
+            KTN_REQUIRE(h_rowkind[i] <= KTN_ROW_QUAD, "unknown row kind");
             if (h_rowkind[i] != KTN_ROW_HOST) continue;
             hostrows.push_back((int32_t)i);
             if (i < m0) host_constr_rows = true;
@@ -442,6 +577,7 @@ void Engine::loadproblem(int64_t num_var, int64_t num_constr, const double* l_va
         if (dist.rank == 0) h_nlrows.push_back((int32_t)m0);      // row-sharded: the epigraph row belongs to rank 0
     }
     m_nl = (int64_t)h_nlrows.size();
+    build_quad_rows(d);                                          // (validates the quad_* arrays: host-side only, nothing is launched)
     esh_build_aux(l_var, u_var, l_constr, u_constr, d);         // (esh.hip; cut_algo = KTN_CUT_SUPPORTING only)
     has_inf_bound = false;
     for (int64_t j = 0; j < n_lp; ++j)
@@ -604,10 +740,10 @@ void Engine::loadproblem(int64_t num_var, int64_t num_constr, const double* l_va
     // the slots are visited in order -- 20 B per entry.
     {
         d_sbck.release(); d_sbrow.release(); d_sbpp.release(); d_sbseg.release();
-        sb_on = !blk_on && 2 * m_nl >= (int64_t)3 * kSbRows * num_cus && n_tape_nl == 0 && n_host_nl == 0 && (double)nnz_nl / (double)std::max<int64_t>(m_nl, 1) <= 128.0 &&
+        sb_on = !blk_on && 2 * m_nl >= (int64_t)3 * kSbRows * num_cus && n_tape_nl == 0 && n_host_nl == 0 && n_quad_nl == 0 && (double)nnz_nl / (double)std::max<int64_t>(m_nl, 1) <= 128.0 &&
                 n_lp <= (int64_t)kSbCols * 64;
         if (dev.sweep_batched == 0) sb_on = false;
-        if (dev.sweep_batched == 1) sb_on = m_nl > 0 && n_tape_nl == 0 && n_host_nl == 0 && n_lp <= (int64_t)kSbCols * 64 && !blk_on;
+        if (dev.sweep_batched == 1) sb_on = m_nl > 0 && n_tape_nl == 0 && n_host_nl == 0 && n_quad_nl == 0 && n_lp <= (int64_t)kSbCols * 64 && !blk_on;
         if (sb_on) {
             sb_nb = ceil_div(n_lp, (int64_t)kSbCols);
             sb_batches = ceil_div(m_nl, (int64_t)kSbRows);
@@ -879,6 +1015,7 @@ void Engine::precompute_all(const double* d_x) {
     }
     if (n_longev > 0)
         hipLaunchKernelGGL(k_sep_eval_long, dim3((unsigned)n_longev), dim3(1024), 0, stream, P, d_longev_rows.p, d_longev_slots.p, d_x, 0.0, 0, O);
+    launch_quad(false, d_x, 0.0);
     LAUNCH_1(k_tape_eval, (int64_t)d_tapeint_all.n, stream, P, d_tapeint_all.p, (int64_t)d_tapeint_all.n, d_x, O);
     if (n_host > 0) host_eval(d_x);
     // cut constants / maxima of tape rows from the materialised Jacobian (flags unused here)
@@ -950,6 +1087,7 @@ hipExtLaunchKernelGGL((k_sep_eval_blk<G, BC, BS, U>), dim3((unsigned)(num_cus * 
     }
     if (n_longev_nl > 0)
         hipLaunchKernelGGL(k_sep_eval_long, dim3((unsigned)n_longev_nl), dim3(1024), 0, stream, P, d_longev_nlrows.p, d_longev_nlslots.p, d_x, f_tol, 1, O);
+    launch_quad(true, d_x, f_tol);
     if (n_tape_nl > 0 || n_host_nl > 0) {
         // tape rows: the classed shapes in one launch (k_tape_classed, statistics folded in), the others through the interpreter
         // and k_gj_stats.  profile: the tape part has an event record of its own (tape_eval_*; sweep_eval_* stays the separable kernel)

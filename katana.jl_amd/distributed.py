@@ -292,6 +292,8 @@ class ShardedKatanaModel:
 def shard_rows(inst, rank, world):
     """rank's shard for the row-sharded LP: all variables and the objective, the block [m_lin r / w, m_lin (r+1) / w) of the
     linear rows and the block of the NL rows given by shard_bounds"""
+    if getattr(inst, "quad_ptr", None) is not None or np.any(np.asarray(getattr(inst, "row_kind", ())) == 3):
+        raise ValueError("shard_rows: KTN_ROW_QUAD rows cannot be row-sharded (their Q segments are not split)")
     ml = inst.m_lin
     l0, l1 = (ml * rank) // world, (ml * (rank + 1)) // world
     n0, n1 = shard_bounds(inst.m_nl, rank, world)

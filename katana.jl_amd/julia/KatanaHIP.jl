@@ -39,6 +39,7 @@ const KTN_OP_SQRT  = Int32(10)
 const KTN_OP_SIN   = Int32(11)
 const KTN_OP_COS   = Int32(12)
 const KTN_ROW_SEP, KTN_ROW_TAPE, KTN_ROW_HOST = UInt8(0), UInt8(1), UInt8(2)
+const KTN_ROW_QUAD = UInt8(3)                                                     # sparse-quadratic rows (quad_ptr / quad_col / quad_val)
 const KTN_CUT_KELLEY, KTN_CUT_SUPPORTING = Int32(0), Int32(1)                     # ktn_params.cut_algo
 const STATUS = [:None, :Optimal, :Unbounded, :Infeasible, :UserLimit, :Error]     # KTN_STATUS_* + 1
 
@@ -69,6 +70,8 @@ struct KtnNlpDesc
     obj_linear::Int32; obj_kind::Int32; obj_nnz::Int64
     obj_col::Ptr{Int32}; obj_atom_kind::Ptr{UInt8}; obj_p0::Ptr{Cdouble}; obj_p1::Ptr{Cdouble}
     obj_const::Cdouble; obj_tape_len::Int64; obj_tape_op::Ptr{Int32}; obj_tape_arg::Ptr{Cdouble}
+    quad_ptr::Ptr{Int64}; quad_col::Ptr{Int32}; quad_val::Ptr{Cdouble}
+    obj_quad_ptr::Ptr{Int64}; obj_quad_col::Ptr{Int32}; obj_quad_val::Ptr{Cdouble}
     eval_rows::Ptr{Void}; eval_obj::Ptr{Void}; eval_user::Ptr{Void}
 end
 
@@ -179,6 +182,7 @@ function build_ktn_nlp_desc(d::MathProgBase.AbstractNLPEvaluator, num_var::Int, 
                       MathProgBase.isobjlinear(d) ? Int32(1) : Int32(0),                    # src/model.jl:125
                       Int32(KTN_ROW_TAPE), 0, C_NULL, C_NULL, C_NULL, C_NULL,
                       0.0, length(arrs.obj_tape_op), pointer(arrs.obj_tape_op), pointer(arrs.obj_tape_arg),
+                      C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL,                       # no KTN_ROW_QUAD rows
                       C_NULL, C_NULL, C_NULL)
     return desc, arrs
 end
@@ -259,6 +263,7 @@ function build_host_nlp_desc(d::MathProgBase.AbstractNLPEvaluator, num_var::Int,
                       C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL,
                       MathProgBase.isobjlinear(d) ? Int32(1) : Int32(0), Int32(KTN_ROW_HOST), 0, C_NULL, C_NULL, C_NULL, C_NULL,
                       0.0, 0, C_NULL, C_NULL,
+                      C_NULL, C_NULL, C_NULL, C_NULL, C_NULL, C_NULL,                       # no KTN_ROW_QUAD rows
                       rows_c, obj_c, pointer_from_objref(host))
     return desc, arrs, host
 end

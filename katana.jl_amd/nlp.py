@@ -24,7 +24,8 @@ class NLPDescription:
     def __init__(self, num_var, rowptr, col, row_kind, row_linear, rconst, atom_kind, p0, p1,
                  tape_ptr=None, tape_op=None, tape_arg=None,
                  obj_linear=True, obj_kind=L.ROW_SEP, obj_col=None, obj_atom_kind=None, obj_p0=None, obj_p1=None,
-                 obj_const=0.0, obj_tape_op=None, obj_tape_arg=None):
+                 obj_const=0.0, obj_tape_op=None, obj_tape_arg=None,
+                 quad_ptr=None, quad_col=None, quad_val=None, obj_quad_ptr=None, obj_quad_col=None, obj_quad_val=None):
         i64, i32, u8, f64 = np.int64, np.int32, np.uint8, np.float64
         self.num_var = int(num_var)
         self.rowptr = np.ascontiguousarray(rowptr, dtype=i64)
@@ -50,6 +51,12 @@ class NLPDescription:
         self.obj_const = float(obj_const)
         self.obj_tape_op = np.ascontiguousarray(obj_tape_op if obj_tape_op is not None else [], dtype=i32)
         self.obj_tape_arg = np.ascontiguousarray(obj_tape_arg if obj_tape_arg is not None else [], dtype=f64)
+        # KTN_ROW_QUAD rows: Q segments per Jacobian entry (None: no such rows) and per objective entry
+        opt = lambda a, t: None if a is None else np.ascontiguousarray(a, dtype=t)
+        self.quad_ptr, self.quad_col, self.quad_val = opt(quad_ptr, i64), opt(quad_col, i32), opt(quad_val, f64)
+        self.obj_quad_ptr, self.obj_quad_col, self.obj_quad_val = opt(obj_quad_ptr, i64), opt(obj_quad_col, i32), opt(obj_quad_val, f64)
+        assert self.quad_ptr is None or len(self.quad_ptr) == nnz + 1
+        assert self.obj_quad_ptr is None or len(self.obj_quad_ptr) == k + 1
         assert len(self.row_kind) == self.num_constr and len(self.row_linear) == self.num_constr
         assert len(self.rconst) == self.num_constr and len(self.p0) == nnz and len(self.p1) == nnz
 
@@ -81,6 +88,9 @@ class NLPDescription:
         d.obj_p0, d.obj_p1, d.obj_const = _ptr(self.obj_p0, C.c_double), _ptr(self.obj_p1, C.c_double), self.obj_const
         d.obj_tape_len = len(self.obj_tape_op)
         d.obj_tape_op, d.obj_tape_arg = _ptr(self.obj_tape_op, C.c_int32), _ptr(self.obj_tape_arg, C.c_double)
+        d.quad_ptr, d.quad_col, d.quad_val = _ptr(self.quad_ptr, C.c_int64), _ptr(self.quad_col, C.c_int32), _ptr(self.quad_val, C.c_double)
+        d.obj_quad_ptr, d.obj_quad_col, d.obj_quad_val = (_ptr(self.obj_quad_ptr, C.c_int64), _ptr(self.obj_quad_col, C.c_int32),
+                                                          _ptr(self.obj_quad_val, C.c_double))
         return d
 
 
@@ -139,6 +149,69 @@ def ExprNLP(num_var, objective, constraints, constr_linear=None, obj_linear=None
         kw = dict(obj_kind=L.ROW_TAPE, obj_tape_op=o, obj_tape_arg=a)
     return NLPDescription(num_var, rowptr, col, rkind, rlin, rconst, akind, p0, p1, tptr, top, targ,
                           obj_linear=is_lin, **kw)
+
+
+def _quad_row(num_var, lin_cols, lin_vals, q_rows, q_cols, q_vals):
+    """One quadratic form  a'x + 1/2 x'Qx  in the engine's layout: (cols, a, seg_ptr, seg_col, seg_val).  cols is the sorted union
+    of the columns of the linear part and of Q; a the linear coefficients on it (duplicates summed); entry e's segment
+    [seg_ptr[e], seg_ptr[e+1]) is row cols[e] of Q sorted by column (duplicate triplets summed, in the order given).  Q arrives
+    as SYMMETRIC triplets -- both (r, c) and (c, r) -- which is the caller's contract (include/katana_hip.h) and is not checked."""
+    i64, f64 = np.int64, np.float64
+    lc, lv = np.asarray(lin_cols, dtype=i64).reshape(-1), np.asarray(lin_vals, dtype=f64).reshape(-1)
+    qr, qc, qv = (np.asarray(q_rows, dtype=i64).reshape(-1), np.asarray(q_cols, dtype=i64).reshape(-1),
+                  np.asarray(q_vals, dtype=f64).reshape(-1))
+    if len(lc) != len(lv) or not (len(qr) == len(qc) == len(qv)):
+        raise ValueError("QuadNLP: index and value arrays of one row differ in length")
+    every = np.concatenate([lc, qr, qc])
+    if len(every) and (every.min() < 0 or every.max() >= num_var):
+        raise ValueError("QuadNLP: column index out of range")
+    cols = np.unique(every)
+    a = np.zeros(len(cols))
+    np.add.at(a, np.searchsorted(cols, lc), lv)
+    key, inv = np.unique(qr * np.int64(max(num_var, 1)) + qc, return_inverse=True)
+    val = np.zeros(len(key))
+    np.add.at(val, inv.reshape(-1), qv)
+    r, c = key // max(num_var, 1), key % max(num_var, 1)
+    ptr = np.concatenate([[0], np.cumsum(np.bincount(np.searchsorted(cols, r), minlength=len(cols)))]).astype(i64)
+    return cols.astype(np.int32), a, ptr, c.astype(np.int32), val
+
+
+def QuadNLP(num_var, obj_c, obj_c0, obj_Q, rows):
+    """NLPDescription of a linear / quadratic program in KTN_ROW_QUAD rows (include/katana_hip.h), declared by the caller:
+
+        objective   obj_c'x + obj_c0 + 1/2 x'Qx        obj_c: dense [num_var] or (cols, vals); obj_Q: (q_rows, q_cols, q_vals) or None
+        rows[i]     (lin_cols, lin_vals, q_rows, q_cols, q_vals, const):   lin'x + const + 1/2 x'Q_i x
+
+    in the ENGINE's convention: Q as symmetric triplets stored in full, duplicates summed (solver.quad_triplets_to_engine converts
+    MathProgBase's two conventions).  Builds the sorted union structure per row, the full segments and row_linear (1 where a
+    row's Q is empty; obj_linear likewise)."""
+    if isinstance(obj_c, tuple):
+        oc, ov = obj_c
+    else:
+        ov = np.asarray(obj_c, dtype=np.float64).reshape(-1)
+        if len(ov) != num_var:
+            raise ValueError("QuadNLP: obj_c must have num_var entries (or be a (cols, vals) pair)")
+        oc = np.flatnonzero(ov)
+        ov = ov[oc]
+    oq = obj_Q if obj_Q is not None else ([], [], [])
+    ocols, oa, optr, oqc, oqv = _quad_row(num_var, oc, ov, *oq)
+    rowptr, col, p0, rconst, rlin, qptr, qcol, qval = [0], [], [], [], [], [np.zeros(1, dtype=np.int64)], [], []
+    nq = 0
+    for row in rows:
+        lc, lv, qr, qc, qv, c0 = row
+        cols, a, ptr, sc, sv = _quad_row(num_var, lc, lv, qr, qc, qv)
+        col.append(cols); p0.append(a); rconst.append(float(c0)); rlin.append(1 if len(sv) == 0 else 0)
+        rowptr.append(rowptr[-1] + len(cols))
+        qptr.append(ptr[1:] + nq); qcol.append(sc); qval.append(sv)
+        nq += len(sv)
+    cat = lambda parts, t: np.concatenate(parts).astype(t) if parts else np.zeros(0, dtype=t)
+    m = len(rlin)
+    col = cat(col, np.int32)
+    return NLPDescription(
+        num_var, rowptr, col, np.full(m, L.ROW_QUAD, dtype=np.uint8), rlin, rconst, None, cat(p0, np.float64), None,
+        obj_linear=len(oqv) == 0, obj_kind=L.ROW_QUAD, obj_col=ocols, obj_p0=oa, obj_const=float(obj_c0),
+        quad_ptr=np.concatenate(qptr), quad_col=cat(qcol, np.int32), quad_val=cat(qval, np.float64),
+        obj_quad_ptr=optr, obj_quad_col=oqc, obj_quad_val=oqv)
 
 
 class CallbackNLP(NLPDescription):
@@ -273,6 +346,9 @@ def fuse_problems(problems):
         d = p.d
         if isinstance(d, CallbackNLP) or np.any(d.row_kind == L.ROW_HOST) or d.obj_kind == L.ROW_HOST:
             raise ValueError("problem %d: host-evaluated rows or objective (CallbackNLP) cannot be fused" % k)
+        if np.any(d.row_kind == L.ROW_QUAD) or d.obj_kind == L.ROW_QUAD:
+            raise ValueError("problem %d: KTN_ROW_QUAD rows or objective (QuadNLP) cannot be fused: the device-side batch loop "
+                             "does not take them" % k)
         if p.sense not in ("Min", "Max"):
             raise ValueError("problem %d: sense must be 'Min' or 'Max'" % k)
         if d.num_var != int(p.num_var) or d.num_constr != int(p.num_constr):

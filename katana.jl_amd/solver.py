@@ -62,7 +62,27 @@ def NonlinearModel(s):
     return KatanaNonlinearModel(s)
 
 
-LinearQuadraticModel = NonlinearModel   # src/solver.jl:46: the LP/QP bridge presents the same model
+def quad_triplets_to_engine(rowidx, colidx, vals, convention):
+    """MathProgBase's two ways of stating a quadratic form -> the engine's: symmetric Q of  1/2 x'Qx  as triplets stored in
+    full, both (r, c) and (c, r) (duplicates are summed downstream, nlp.QuadNLP).  T = the matrix the given triplets sum to.
+
+      convention "objective"  (setquadobj!):    the form is  1/2 x'Qx  with Q symmetric and an off-diagonal pair given ONCE standing
+                                                for both entries:  Q = T + T' - diag(T),  i.e.  1/2 sum_r T_rr x_r^2 + sum_{r != c} T_rc x_r x_c
+      convention "constraint" (addquadconstr!): the form is  sum T_rc x_r x_c  with no 1/2:  Q = T + T'  (diagonal doubled)
+
+    so an off-diagonal triplet becomes the two mirrored entries in both, and only the diagonal differs: as given, or doubled."""
+    if convention not in ("objective", "constraint"):
+        raise ValueError("convention must be 'objective' or 'constraint'")
+    r = np.asarray(rowidx, dtype=np.int64).reshape(-1)
+    c = np.asarray(colidx, dtype=np.int64).reshape(-1)
+    v = np.asarray(vals, dtype=np.float64).reshape(-1)
+    if not (len(r) == len(c) == len(v)):
+        raise ValueError("quadratic triplets: index and value arrays differ in length")
+    off = r != c
+    dv = v[~off] * (2.0 if convention == "constraint" else 1.0)
+    return (np.concatenate([r[off], c[off], r[~off]]), np.concatenate([c[off], r[off], c[~off]]),
+            np.concatenate([v[off], v[off], dv]))
+
 
 
 class KatanaNonlinearModel:
@@ -422,3 +442,80 @@ def getKatanaSols(m):                             # src/util.jl:36
         L.check(m._h, m._lib.ktn_get_lp_sol(m._h, i, _p(x), len(x)))
         out.append(x)
     return out
+
+
+class LinearQuadraticModel(KatanaNonlinearModel):
+    """MathProgBase.LinearQuadraticModel(s::KatanaSolver)  src/solver.jl:46 -- the LP / QP / QCQP surface the reference presents
+    through NonlinearToLPQPBridge, stated natively: the rows go to the engine as KTN_ROW_QUAD rows (nlp.QuadNLP), not as
+    expressions.  Indices are 0-based.
+
+        loadproblem(A, collb, colub, obj, rowlb, rowub, sense)    A dense or scipy-sparse, sense "Min" / "Max"
+        setquadobj(rowidx, colidx, vals)                          objective + 1/2 x'Qx, an off-diagonal pair given once
+        addquadconstr(linidx, linval, quadrowidx, quadcolidx, quadval, sense, rhs)     sum linval x + sum quadval x_r x_c {'<', '>'} rhs
+        optimize()                                                assembles the QuadNLP, loads it and solves
+
+    (quad_triplets_to_engine holds both conversions.)  The 8-argument loadproblem(num_var, num_constr, ..., d) of
+    NonlinearModel keeps working on it, and the getters are inherited."""
+
+    def __init__(self, solver):
+        super().__init__(solver)
+        self._lq = None
+
+    def loadproblem(self, *args):
+        if len(args) == 8:
+            self._lq = None
+            return super().loadproblem(*args)
+        if len(args) != 7:
+            raise TypeError("loadproblem(A, collb, colub, obj, rowlb, rowub, sense) or loadproblem(num_var, num_constr, l_var, "
+                            "u_var, l_constr, u_constr, sense, d)")
+        A, collb, colub, obj, rowlb, rowub, sense = args
+        if sense not in ("Min", "Max"):
+            raise ValueError("sense must be 'Min' or 'Max'")
+        if hasattr(A, "tocsr"):
+            A = A.tocsr()
+            A.sum_duplicates()
+            m, n = A.shape
+            rp, ci, av = np.asarray(A.indptr, dtype=np.int64), np.asarray(A.indices, dtype=np.int64), _f64(A.data)
+        else:
+            A = np.asarray(A, dtype=np.float64)
+            if A.ndim != 2:
+                A = A.reshape(0, len(np.atleast_1d(collb)))
+            m, n = A.shape
+            nz = A != 0.0
+            rp = np.concatenate([[0], np.cumsum(nz.sum(axis=1))]).astype(np.int64)
+            ci, av = np.nonzero(nz)[1].astype(np.int64), A[nz]
+        collb, colub, obj, rowlb, rowub = _f64(collb), _f64(colub), _f64(obj), _f64(rowlb), _f64(rowub)
+        if not (len(collb) == len(colub) == len(obj) == n and len(rowlb) == len(rowub) == m):
+            raise ValueError("loadproblem: array lengths do not match A (%d x %d)" % (m, n))
+        rows = [(ci[rp[i]:rp[i + 1]], av[rp[i]:rp[i + 1]], [], [], [], 0.0) for i in range(m)]
+        self._lq = dict(n=n, collb=collb, colub=colub, obj=obj, sense=sense, rows=rows, lb=list(rowlb), ub=list(rowub),
+                        objq=None, dirty=True)
+
+    def _need_lq(self):
+        if self._lq is None:
+            raise RuntimeError("no LP loaded: call loadproblem(A, collb, colub, obj, rowlb, rowub, sense) first")
+        return self._lq
+
+    def setquadobj(self, rowidx, colidx, vals):
+        q = self._need_lq()
+        q["objq"] = quad_triplets_to_engine(rowidx, colidx, vals, "objective")
+        q["dirty"] = True
+
+    def addquadconstr(self, linidx, linval, quadrowidx, quadcolidx, quadval, sense, rhs):
+        q = self._need_lq()
+        if sense not in ("<", ">", "="):
+            raise ValueError("addquadconstr: sense must be '<', '>' or '='")
+        qr, qc, qv = quad_triplets_to_engine(quadrowidx, quadcolidx, quadval, "constraint")
+        q["rows"].append((np.asarray(linidx, dtype=np.int64), _f64(linval), qr, qc, qv, 0.0))
+        q["lb"].append(-np.inf if sense == "<" else float(rhs))
+        q["ub"].append(np.inf if sense == ">" else float(rhs))
+        q["dirty"] = True
+
+    def optimize(self):
+        q = self._lq
+        if q is not None and q["dirty"]:
+            from .nlp import QuadNLP
+            d = QuadNLP(q["n"], q["obj"], 0.0, q["objq"], q["rows"])
+            KatanaNonlinearModel.loadproblem(self, q["n"], len(q["rows"]), q["collb"], q["colub"], q["lb"], q["ub"], q["sense"], d)
+            q["dirty"] = False
+        return super().optimize()
