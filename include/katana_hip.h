@@ -186,7 +186,7 @@ typedef struct {
        segment from an interior point x_int to x* for the point where the row reaches its bound and cuts there (supporting
        hyperplanes).  x_int is the caller's (ktn_set_interior_point) or found once per loaded problem
        by the engine on the auxiliary min-max problem.  Not with ktn_optimize_blocks, a row-sharded handle or a cut exchange. */
-    int32_t cut_algo;          /* 0 (KTN_CUT_KELLEY)                                                                     */
+    int32_t cut_algo;          /* 0 (KTN_CUT_KELLEY), 1 (KTN_CUT_SUPPORTING) or 2 (KTN_CUT_SUPPORTING_QUAD)                      */
     int32_t esh_root_iters;    /* 20    Newton / bisection steps of a row's root search                                    */
     double  esh_root_tol;      /* 0.1   the search stops once 0 <= phi <= esh_root_tol * f_tol                            */
     int32_t esh_interior_iters;/* 50    rounds of the auxiliary problem that finds x_int                                   */
@@ -194,6 +194,9 @@ typedef struct {
 
 #define KTN_CUT_KELLEY     0   /* tangent at x* (the reference's linear_oa_cut)          */
 #define KTN_CUT_SUPPORTING 1   /* tangent at the boundary point between x_int and x*     */
+#define KTN_CUT_SUPPORTING_QUAD 2   /* KTN_CUT_SUPPORTING with the declared-quadratic rows (KTN_ROW_QUAD) taking part: their boundary
+                                       point has a closed form (k_esh_quad); LPs of at most 32 columns go to the
+                                       exact small-LP kernel first; refused where 1 is refused */
 
 /* NL-row blocks over several GPUs with a replicated LP: the exchange step of one cutting-plane round.
  * what = 0: the handle has just swept ITS block of NL rows; its new LP rows are the rows from `first_new_row` on.  The callback
@@ -305,14 +308,15 @@ int64_t ktn_numiters(ktn_handle h);
 int64_t ktn_numcuts(ktn_handle h);
 int     ktn_setwarmstart(ktn_handle h, const double* x, int64_t n);
 
-/* ---- supporting-hyperplane cuts (cut_algo = KTN_CUT_SUPPORTING) ------------------------
+/* ---- supporting-hyperplane cuts (cut_algo = KTN_CUT_SUPPORTING or KTN_CUT_SUPPORTING_QUAD) ------
  * The interior point x_int [num_var, without the epigraph variable]: ktn_set_interior_point hands one over (NULL clears
  * it, and the engine then looks for one itself when it next needs it); ktn_loadproblem forgets it, ktn_reset keeps it.
  * ktn_get_interior_point writes the point in use and *found = 1, or *found = 0 when there is none (the engine then
- * cuts as in Kelley's method).  With cut_algo = KTN_CUT_SUPPORTING it first finds or evaluates the point if that has
+ * cuts as in Kelley's method).  With supporting hyperplanes on it first finds or evaluates the point if that has
  * not happened yet.
  * Stats: "esh_rows" "esh_fallback_rows" "esh_newton_steps" "esh_root_time_s" "esh_interior_found" "esh_interior_rounds"
- *        "esh_interior_s" "esh_interior_depth" "esh_interior_time_s" */
+ *        "esh_interior_s" "esh_interior_depth" "esh_interior_time_s"
+ *        "esh_quad_rows" KTN_ROW_QUAD rows cut at their boundary point (KTN_CUT_SUPPORTING_QUAD; cumulative, counted in "esh_rows" too) */
 int ktn_set_interior_point(ktn_handle h, const double* x, int64_t n);
 int ktn_get_interior_point(ktn_handle h, double* x_out, int64_t n, int32_t* found);
 /* lambda of each cut the last sweep appended, in the order of ktn_last_sweep_slots: the cut of that row was taken at

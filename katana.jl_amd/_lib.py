@@ -11,7 +11,7 @@ STATUS_NONE, STATUS_OPTIMAL, STATUS_UNBOUNDED, STATUS_INFEASIBLE, STATUS_USERLIM
 MIN, MAX = 0, 1
 ROW_SEP, ROW_TAPE, ROW_HOST, ROW_QUAD = 0, 1, 2, 3
 ATOM_LIN, ATOM_QUAD, ATOM_EXP, ATOM_NEGLOG = 0, 1, 2, 3
-CUT_KELLEY, CUT_SUPPORTING = 0, 1          # ktn_params.cut_algo
+CUT_KELLEY, CUT_SUPPORTING, CUT_SUPPORTING_QUAD = 0, 1, 2          # ktn_params.cut_algo
 LPOP_STEP, LPOP_CHECK, LPOP_ADVANCE, LPOP_RESTART = range(4)      # ktn_lp_script ops
 LPS_IDENTITY, LPS_PACKED, LPS_NO_SPEC = 1, 2, 4                   # ktn_lp_script flags
 (OP_CONST, OP_VAR, OP_ADD, OP_SUB, OP_MUL, OP_DIV, OP_NEG, OP_POWC, OP_EXP, OP_LOG, OP_SQRT, OP_SIN,

@@ -146,8 +146,8 @@ int ktn_get_interior_point(ktn_handle h, double* x_out, int64_t n, int32_t* foun
     KTN_TRY(h, {
         Engine* e = h->eng;
         KTN_REQUIRE(e->loaded && found, "ktn_get_interior_point: after loadproblem, found != NULL");
-        if (e->prm.cut_algo == KTN_CUT_SUPPORTING && !e->esh_ready) e->esh_prepare();
-        const bool have = e->prm.cut_algo == KTN_CUT_SUPPORTING ? e->xint_found != 0 : e->xint_given;
+        if (e->esh_mode() && !e->esh_ready) e->esh_prepare();
+        const bool have = e->esh_mode() ? e->xint_found != 0 : e->xint_given;
         *found = have ? 1 : 0;
         if (have && x_out) {
             KTN_REQUIRE(n >= e->n0, "ktn_get_interior_point: buffer too small");
@@ -219,7 +219,7 @@ int ktn_sep_gencut(ktn_handle h, int64_t i, int32_t* cols, double* coefs, int64_
         KTN_REQUIRE(*nnz >= len, "gencut: output capacity too small");
         // (cut_algo = KTN_CUT_SUPPORTING: the row's cut moves to its boundary point on the segment from x_int, as the reference's
         //  gencut calls sep.algo; the state of the precompute is restored afterwards)
-        const bool moved = e->prm.cut_algo == KTN_CUT_SUPPORTING && e->esh_gencut_row(i, coefs, constant);
+        const bool moved = e->esh_mode() && e->esh_gencut_row(i, coefs, constant);
         std::memcpy(cols, e->h_col.data() + beg, (size_t)len * sizeof(int32_t));
         if (!moved) {
             if (len) KTN_HIP(hipMemcpyAsync(coefs, e->d_jac.p + beg, (size_t)len * 8, hipMemcpyDeviceToHost, e->stream));
@@ -470,7 +470,7 @@ int ktn_set_cut_exchange(ktn_handle h, ktn_exchange_cb cb, void* user, int64_t f
         Engine* e = h->eng;
         KTN_REQUIRE(e->loaded && first_nl_id >= 0, "ktn_set_cut_exchange: after loadproblem");
         KTN_REQUIRE(cb == nullptr || e->glists, "ktn_set_cut_exchange: enable the global cut lists first (ktn_lp_enable_global_lists)");
-        if (cb != nullptr && e->prm.cut_algo == KTN_CUT_SUPPORTING)
+        if (cb != nullptr && e->esh_mode())
             throw ktn::Error(KTN_E_UNSUPPORTED, "ktn_set_cut_exchange: not available with cut_algo = KTN_CUT_SUPPORTING");
         e->exch_cb = cb; e->exch_user = user; e->exch_lo = first_nl_id;
         return KTN_OK;
@@ -514,7 +514,7 @@ int ktn_optimize_blocks(ktn_handle h, int32_t cut_capacity) {
     KTN_TRY(h, {
         Engine* e = h->eng;
         KTN_REQUIRE(e->loaded && e->n_blocks > 0, "ktn_optimize_blocks: after ktn_loadproblem and ktn_set_blocks");
-        if (e->prm.cut_algo == KTN_CUT_SUPPORTING)
+        if (e->esh_mode())
             throw ktn::Error(KTN_E_UNSUPPORTED, "ktn_optimize_blocks: not available with cut_algo = KTN_CUT_SUPPORTING");
         if (e->M != e->M_base || e->iter != 0) e->reset();
         if (e->optimize_blocks_device(cut_capacity > 0 ? cut_capacity : 12)) return e->status;

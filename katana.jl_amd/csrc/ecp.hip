@@ -150,7 +150,7 @@ void Engine::begin() {
     begun = true;
     lp_status = KTN_STATUS_OPTIMAL;
     if (status == KTN_STATUS_ERROR) return;
-    if (prm.cut_algo == KTN_CUT_SUPPORTING && !esh_ready) esh_prepare();      // x_int, once per loaded problem (esh.hip)
+    if (esh_mode() && !esh_ready) esh_prepare();      // x_int, once per loaded problem (esh.hip)
     if (has_inf_bound) {       // presolve: resolve an initially-unbounded LP  model.jl:228-247
         int64_t i = 0;
         bool unb = recession_ray();

@@ -70,6 +70,7 @@ struct DevParams {
     int tape_classed = -1;         // KTN_TAPE_CLASSED     tape rows by shape class (k_tape_classed): -1 = classes of >= 64 rows, 0 = interpreter for
                                    //                      every tape row, 1 = every class of >= 2 rows
     int quad_group = 0;            // KTN_QUAD_GROUP       lanes per Jacobian entry of k_quad_jac (0 = by mean segment length)
+    int esh_quad_group = 0;        // KTN_ESH_QUAD_GROUP   lanes per row of k_esh_quad (0 = those of k_quad_stats, by mean row length)
     int tiled_wg = 2;              // KTN_TILED_WG         workgroups per CU of k_spmv_tiled
     int ecp_power = 20;            // KTN_ECP_POWER        power passes of the device-side batch loop
     int grp_rows = 0, grp_cols = 0;// KTN_GRP_ROWS / COLS  lanes per LP row / column (0 = by average length)
@@ -97,7 +98,7 @@ struct DevParams {
         force_collective = flag("KTN_FORCE_COLLECTIVE");
         sweep_rows = geti("KTN_SWEEP_ROWS", sweep_rows); blk_cfg = geti("KTN_BLK_CFG", blk_cfg); sweep_blocked = geti("KTN_SWEEP_BLOCKED", sweep_blocked);
         sweep_batched = geti("KTN_SWEEP_BATCHED", sweep_batched); tape_classed = geti("KTN_TAPE_CLASSED", tape_classed);
-        quad_group = geti("KTN_QUAD_GROUP", quad_group);
+        quad_group = geti("KTN_QUAD_GROUP", quad_group); esh_quad_group = geti("KTN_ESH_QUAD_GROUP", esh_quad_group);
         tiled_wg = geti("KTN_TILED_WG", tiled_wg); ecp_power = geti("KTN_ECP_POWER", ecp_power);
         grp_rows = geti("KTN_GRP_ROWS", grp_rows); grp_cols = geti("KTN_GRP_COLS", grp_cols); tiled = geti("KTN_TILED", tiled);
         smax_reuse = getd("KTN_SMAX_REUSE", smax_reuse); power_passes = geti("KTN_POWER_PASSES", power_passes);
@@ -386,8 +387,8 @@ struct Engine {
 
     explicit Engine(const ktn_params& p) : prm(p) {
         dev.from_env();
-        if (prm.cut_algo != KTN_CUT_KELLEY && prm.cut_algo != KTN_CUT_SUPPORTING)
-            throw Error(KTN_E_INVALID, "cut_algo must be KTN_CUT_KELLEY (0) or KTN_CUT_SUPPORTING (1)");
+        if (prm.cut_algo != KTN_CUT_KELLEY && !esh_mode())
+            throw Error(KTN_E_INVALID, "cut_algo must be KTN_CUT_KELLEY (0), KTN_CUT_SUPPORTING (1) or KTN_CUT_SUPPORTING_QUAD (2)");
         int ndev = 0;
         if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
             throw Error(KTN_E_NODEVICE, "no HIP device visible: the Katana HIP engine has no CPU path");
@@ -544,15 +545,24 @@ struct Engine {
     DBuf<int64_t> d_sbseg;
 
     // ================================================================ supporting hyperplanes (esh.hip) ===
-    // cut_algo == KTN_CUT_SUPPORTING: every selected violated row that participates is cut at the point
-    // x_int + lambda_i (x* - x_int) where it reaches its bound.  Participating: separable or tape program, exactly one finite side,
-    // not the epigraph row (h_esh_side: +1 upper side, -1 lower side, 0 not participating), and g_i(x_int) at least 10 f_tol
-    // inside its bound (d_esh_sig: the side, or 0).
+    // cut_algo == KTN_CUT_SUPPORTING or KTN_CUT_SUPPORTING_QUAD: every selected violated row that participates
+    // is cut at the point x_int + lambda_i (x* - x_int) where it reaches its bound.  Participating: separable or tape program -- under
+    // KTN_CUT_SUPPORTING_QUAD also a KTN_ROW_QUAD row not declared linear --, exactly one finite side, not the epigraph row
+    // (h_esh_side: +1 upper side, -1 lower side, 0 not participating), and g_i(x_int) at least 10 f_tol inside its bound (d_esh_sig:
+    // the side, or 0).
+    bool esh_mode() const { return prm.cut_algo == KTN_CUT_SUPPORTING || prm.cut_algo == KTN_CUT_SUPPORTING_QUAD; }
+    bool esh_quad_mode() const { return prm.cut_algo == KTN_CUT_SUPPORTING_QUAD; }
+    int esh_quad_group() const {                // lanes per row of k_esh_quad
+        const int g = dev.esh_quad_group;
+        return (g == 4 || g == 8 || g == 16 || g == 32 || g == 64) ? g : grp_quad_rows;
+    }
     std::vector<int8_t> h_esh_side;
     DBuf<int8_t> d_esh_sig;
     DBuf<double> d_xint, d_lam;
+    DBuf<double> d_jint;                       // Jacobian at x_int by Jacobian entry (k_esh_quad, k_emit_esh); only with taking-part QUAD rows
+    int64_t esh_n_quad_part = 0;               // taking-part QUAD rows (0 unless KTN_CUT_SUPPORTING_QUAD)
     DBuf<int32_t> d_tape_nlslots;              // NL slot of each tape NL row (d_taperows_nl)
-    DBuf<unsigned long long> d_esh_cnt;         // [0] rows cut at x_b, [1] Newton / bisection passes
+    DBuf<unsigned long long> d_esh_cnt;         // [0] rows cut at x_b, [1] Newton / bisection passes, [2] QUAD rows among [0]
     std::vector<double> h_xint;                 // the point in use (n0 entries)
     bool xint_given = false, esh_ready = false;
     int xint_found = 0;
@@ -561,10 +571,11 @@ struct Engine {
     struct EshAux {
         int64_t n = 0, m = 0;
         std::vector<double> lv, uv, lc, uc, rconst, p0, p1, targ, op0, op1;
-        std::vector<int64_t> rowptr, tptr;
-        std::vector<int32_t> col, top, ocol;
+        std::vector<int64_t> rowptr, tptr, qptr;                 // qptr [entries + 1]: Q segments of the QUAD rows, empty for the others
+        std::vector<int32_t> col, top, ocol, qcol;
+        std::vector<double> qval;
         std::vector<uint8_t> kind, lin, akind, okind;
-        bool has_tape = false;
+        bool has_tape = false, has_quad = false;
     } aux;
     Engine* child = nullptr;
     void esh_build_aux(const double* l_var, const double* u_var, const double* l_constr, const double* u_constr, const ktn_nlp_desc* d);

@@ -1,15 +1,18 @@
-// esh.hip -- supporting-hyperplane cuts (cut_algo == KTN_CUT_SUPPORTING): the auxiliary problem that finds
+// esh.hip -- supporting-hyperplane cuts (cut_algo == KTN_CUT_SUPPORTING / _QUAD): the auxiliary problem that finds
 // the interior point, its evaluation, and the host side of the per-row root search in the sweep  (struct Engine: engine.hpp)
 #include "engine.hpp"
 #include "launch.hpp"
 #include "kernels.hpp"
 #include "esh.hpp"
+#include "esh_quad.hpp"
 
 namespace ktn {
 
 // At load (the caller's description is valid only now): which rows take part, and the auxiliary min-max problem
 //     min s   over (x, s), s in [-1, +inf):   linear rows as they are;   g_i(x) - s <= ub_i  /  g_i(x) + s >= lb_i  per taking-part row
-// (a separable row gains a LIN atom on s, a tape row VAR s and SUB / ADD; every other nonlinear row is dropped).
+// (a separable row gains a LIN atom on s, a tape row VAR s and SUB / ADD, a taking-part QUAD row -- KTN_CUT_SUPPORTING_QUAD -- an
+//  entry on s with coefficient -sigma_i and an empty Q segment, as the engine appends t to a quadratic objective; every other
+//  nonlinear row is dropped).
 void Engine::esh_build_aux(const double* l_var, const double* u_var, const double* l_constr, const double* u_constr,
                            const ktn_nlp_desc* d) {
     delete child;
@@ -18,18 +21,22 @@ void Engine::esh_build_aux(const double* l_var, const double* u_var, const doubl
     h_xint.clear();
     aux = EshAux();
     h_esh_side.assign((size_t)m_ext, 0);
-    esh_n_part = 0;
-    if (prm.cut_algo != KTN_CUT_SUPPORTING) return;
+    esh_n_part = esh_n_quad_part = 0;
+    d_jint.release();
+    stats["esh_quad_rows"] = 0.0;
+    if (!esh_mode()) return;
     if (row_sharded()) throw Error(KTN_E_UNSUPPORTED, "cut_algo = KTN_CUT_SUPPORTING is not available on a row-sharded handle");
     std::vector<int32_t> tslots;
     for (size_t si = 0; si < h_nlrows.size(); ++si) {
         const int64_t i = h_nlrows[si];
         if (h_rowkind[(size_t)i] == KTN_ROW_TAPE) tslots.push_back((int32_t)si);
-        if (i >= m0 || (h_rowkind[(size_t)i] != KTN_ROW_SEP && h_rowkind[(size_t)i] != KTN_ROW_TAPE)) continue;
+        const bool quad = esh_quad_mode() && h_rowkind[(size_t)i] == KTN_ROW_QUAD;       // (h_nlrows: not declared linear)
+        if (i >= m0 || (h_rowkind[(size_t)i] != KTN_ROW_SEP && h_rowkind[(size_t)i] != KTN_ROW_TAPE && !quad)) continue;
         const bool lf = std::isfinite(h_lb[(size_t)i]), uf = std::isfinite(h_ub[(size_t)i]);
         if (lf == uf) continue;                                  // two-sided rows, equalities, free rows
         h_esh_side[(size_t)i] = uf ? 1 : -1;
         ++esh_n_part;
+        if (quad) ++esh_n_quad_part;
     }
     d_tape_nlslots.upload(tslots, stream);
     stats["esh_participating_rows"] = (double)esh_n_part;
@@ -41,20 +48,26 @@ void Engine::esh_build_aux(const double* l_var, const double* u_var, const doubl
     A.uv.assign(u_var, u_var + n0); A.uv.push_back(kInf);
     A.rowptr.assign(1, 0);
     A.tptr.assign(1, 0);
+    A.qptr.assign(1, 0);
     for (int64_t i = 0; i < m0; ++i) {
         const uint8_t kind = d->row_kind ? d->row_kind[i] : KTN_ROW_SEP;
         const bool lin = d->row_linear && d->row_linear[i];
         const int side = h_esh_side[(size_t)i];
-        // (only separable and tape rows have a program the auxiliary problem can carry: host-evaluated rows and nonlinear QUAD rows
-        //  are dropped; a QUAD row declared linear has an empty Q and goes in as the separable row of LIN atoms it is)
+        // (host-evaluated rows have no program the auxiliary problem can carry and are dropped, and so are the nonlinear QUAD rows
+        //  that do not take part; a QUAD row declared linear has an empty Q and goes in as the separable row of LIN atoms it is)
         const bool quad_lin = kind == KTN_ROW_QUAD && lin;
-        if ((kind != KTN_ROW_SEP && kind != KTN_ROW_TAPE && !quad_lin) || (!lin && side == 0)) continue;
+        const bool quad_nl = kind == KTN_ROW_QUAD && !lin && esh_quad_mode();
+        if ((kind != KTN_ROW_SEP && kind != KTN_ROW_TAPE && !quad_lin && !quad_nl) || (!lin && side == 0)) continue;
         for (int64_t e = d->rowptr[i]; e < d->rowptr[i + 1]; ++e) {
             A.col.push_back(d->col[e]);
-            A.akind.push_back(d->atom_kind && !quad_lin ? d->atom_kind[e] : 0);
+            A.akind.push_back(d->atom_kind && !quad_lin && !quad_nl ? d->atom_kind[e] : 0);
             A.p0.push_back(d->p0 ? d->p0[e] : 0.0);
-            A.p1.push_back(d->p1 && !quad_lin ? d->p1[e] : 0.0);
+            A.p1.push_back(d->p1 && !quad_lin && !quad_nl ? d->p1[e] : 0.0);
+            if (quad_nl)                                          // the entry's Q segment, re-based
+                for (int64_t k = d->quad_ptr[e]; k < d->quad_ptr[e + 1]; ++k) { A.qcol.push_back(d->quad_col[k]); A.qval.push_back(d->quad_val[k]); }
+            A.qptr.push_back((int64_t)A.qcol.size());
         }
+        if (quad_nl) A.has_quad = true;
         if (kind == KTN_ROW_TAPE) {
             for (int64_t t = d->tape_ptr[i]; t < d->tape_ptr[i + 1]; ++t) { A.top.push_back(d->tape_op[t]); A.targ.push_back(d->tape_arg[t]); }
             A.has_tape = true;
@@ -64,6 +77,7 @@ void Engine::esh_build_aux(const double* l_var, const double* u_var, const doubl
             A.akind.push_back(KTN_ATOM_LIN);
             A.p0.push_back(-(double)side);
             A.p1.push_back(0.0);
+            A.qptr.push_back((int64_t)A.qcol.size());
             if (kind == KTN_ROW_TAPE) {
                 A.top.push_back(KTN_OP_VAR); A.targ.push_back((double)s_col);
                 A.top.push_back(side > 0 ? KTN_OP_SUB : KTN_OP_ADD); A.targ.push_back(0.0);
@@ -104,6 +118,7 @@ void Engine::esh_find_interior() {
         dd.rowptr = A.rowptr.data(); dd.col = A.col.data(); dd.row_kind = A.kind.data(); dd.row_linear = A.lin.data();
         dd.rconst = A.rconst.data(); dd.atom_kind = A.akind.data(); dd.p0 = A.p0.data(); dd.p1 = A.p1.data();
         if (A.has_tape) { dd.tape_ptr = A.tptr.data(); dd.tape_op = A.top.data(); dd.tape_arg = A.targ.data(); }
+        if (A.has_quad) { dd.quad_ptr = A.qptr.data(); dd.quad_col = A.qcol.data(); dd.quad_val = A.qval.data(); }
         dd.obj_linear = 1; dd.obj_kind = KTN_ROW_SEP; dd.obj_nnz = 1;
         dd.obj_col = A.ocol.data(); dd.obj_atom_kind = A.okind.data(); dd.obj_p0 = A.op0.data(); dd.obj_p1 = A.op1.data();
         child->loadproblem(A.n, A.m, A.lv.data(), A.uv.data(), A.lc.data(), A.uc.data(), KTN_MIN, &dd);
@@ -159,6 +174,10 @@ void Engine::esh_prepare() {
     d_xint.upload(xi, stream);
     precompute_all(d_xint.p);
     const std::vector<double> g = d_g.to_host(stream);
+    if (esh_n_quad_part > 0) {                           // the Jacobian at x_int, by Jacobian entry: k_esh_quad interpolates from it
+        d_jint.resize((size_t)nnz_ext, stream);
+        KTN_HIP(hipMemcpyAsync(d_jint.p, d_jac.p, (size_t)nnz_ext * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    }
     std::vector<int8_t> sig((size_t)m_ext, 0);
     double depth = kInf;
     int64_t inside = 0;
@@ -171,7 +190,7 @@ void Engine::esh_prepare() {
     }
     d_esh_sig.upload(sig, stream);
     d_lam.resize((size_t)m_ext, stream);
-    d_esh_cnt.resize(2, stream);
+    d_esh_cnt.resize(3, stream);
     stats["esh_interior_depth"] = esh_n_part ? depth : kInf;
     stats["esh_interior_rows"] = (double)inside;
     if (have_precompute) precompute_all(d_xs.p);        // (ktn_sep_*: the state of the caller's last precompute)
@@ -193,13 +212,18 @@ void Engine::esh_search(const double* d_x, double f_tol) {
         hipLaunchKernelGGL(k_esh_long, dim3((unsigned)n_longev_nl), dim3(1024), 0, stream, P, d_longev_nlrows.p, d_longev_nlslots.p,
                            (const int64_t*)d_flag.p, A, O);
     LAUNCH_1(k_esh_tape, n_tape_nl, stream, P, d_taperows_nl.p, d_tape_nlslots.p, n_tape_nl, (const int64_t*)d_flag.p, A, O);
+    if (esh_n_quad_part > 0 && n_quad_nl > 0) {         // (KTN_CUT_SUPPORTING_QUAD; d_jint stands)
+        const QuadList QL{d_qrows_nl.p, d_qslots_nl.p, d_qtbase_nl.p, nullptr, n_quad_nl, n_quad_ent_nl};
+        LAUNCH_G(esh_quad_group(), k_esh_quad, n_quad_nl, stream, P, QL, (const int64_t*)d_flag.p, (const double*)d_jint.p, A, O);
+    }
     check_launch();
-    unsigned long long c[2] = {0ull, 0ull};
+    unsigned long long c[3] = {0ull, 0ull, 0ull};
     KTN_HIP(hipMemcpyAsync(c, d_esh_cnt.p, sizeof(c), hipMemcpyDeviceToHost, stream));
     sync();
     esh_on = true;
     esh_last_rows = (int64_t)c[0];
     stats["esh_rows"] += (double)c[0];
+    stats["esh_quad_rows"] += (double)c[2];
     stats["esh_newton_steps"] += (double)c[1];
     stats["esh_root_time_s"] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
@@ -210,7 +234,7 @@ void Engine::esh_emit(const double* d_x, int64_t V) {
     stats["esh_fallback_rows"] += (double)(V - (esh_on ? esh_last_rows : 0));
     if (esh_on)
         LAUNCH_G(grp_sweep, k_emit_esh, V, stream, P, d_nlrows.p, d_violslots.p, V, d_x, (const double*)d_xint.p, (const double*)d_lam.p,
-                 d_jac.p, d_maxc.p, prm.cut_coef_rng, 1, M, L);
+                 d_jac.p, (const double*)(esh_n_quad_part > 0 ? d_jint.p : nullptr), d_maxc.p, prm.cut_coef_rng, 1, M, L);
     else
         LAUNCH_G(grp_sweep, k_emit, V, stream, P, d_nlrows.p, d_violslots.p, V, d_x, d_jac.p, d_maxc.p, prm.cut_coef_rng, 1, M, L);
 }
@@ -222,7 +246,7 @@ bool Engine::esh_gencut_row(int64_t i, double* coefs, double* constant) {
     if (!esh_ready) esh_prepare();
     if (!xint_found || i < 0 || i >= m0 || h_esh_side[(size_t)i] == 0) return false;
     const uint8_t kind = h_rowkind[(size_t)i];
-    if (kind != KTN_ROW_SEP && kind != KTN_ROW_TAPE) return false;
+    if (kind != KTN_ROW_SEP && kind != KTN_ROW_TAPE && !(kind == KTN_ROW_QUAD && esh_quad_mode())) return false;
     const int64_t beg = h_rowptr[(size_t)i], len = h_rowptr[(size_t)i + 1] - beg;
     const bool longrow = !blk_on && kind == KTN_ROW_SEP && len > kLongEval;      // (device kind kRowSepLong: k_sep_eval_long's rows)
     // what the precompute left for row i
@@ -247,10 +271,14 @@ bool Engine::esh_gencut_row(int64_t i, double* coefs, double* constant) {
         hipLaunchKernelGGL(k_esh_long, dim3(1), dim3(1024), 0, stream, P, d_esh_one.p, d_esh_slot.p, (const int64_t*)nullptr, A, O);
     else if (kind == KTN_ROW_TAPE)
         LAUNCH_1(k_esh_tape, 1, stream, P, d_esh_one.p, d_esh_one.p, (int64_t)1, (const int64_t*)nullptr, A, O);
+    else if (kind == KTN_ROW_QUAD) {
+        const QuadList QL{d_esh_one.p, d_esh_slot.p, nullptr, nullptr, 1, len};
+        LAUNCH_G(esh_quad_group(), k_esh_quad, 1, stream, P, QL, (const int64_t*)nullptr, (const double*)d_jint.p, A, O);
+    }
     else
         LAUNCH_G(grp_sweep, k_esh_sep, 1, stream, P, d_esh_one.p, (int64_t)1, (const int64_t*)nullptr, A, O);
     check_launch();
-    unsigned long long c[2] = {0ull, 0ull};
+    unsigned long long c[3] = {0ull, 0ull, 0ull};
     KTN_HIP(hipMemcpyAsync(c, d_esh_cnt.p, sizeof(c), hipMemcpyDeviceToHost, stream));
     sync();
     stats["esh_newton_steps"] += (double)c[1];

@@ -1,4 +1,4 @@
-// esh.hpp -- supporting-hyperplane cuts (cut_algo == KTN_CUT_SUPPORTING): the per-row root search on the
+// esh.hpp -- supporting-hyperplane cuts (cut_algo == KTN_CUT_SUPPORTING / _QUAD): the per-row root search on the
 // segment from the interior point x_int to the LP point x*, and the cut emission at the point found.
 //
 // Row i with side sigma_i (+1: g_i <= ub_i, -1: g_i >= lb_i) and bound b_i:
@@ -11,7 +11,8 @@
 //   k_esh_sep<G>   separable rows, G lanes per row (the k_sep_eval layout); the wavefront loops until all of its rows are done
 //   k_esh_long     rows of k_sep_eval_long, one 1 024-thread workgroup per row
 //   k_esh_tape     tape rows, one lane per row through tape_row_eval
-//   k_emit_esh<G>  k_emit with the separable derivatives taken at x_b (tape and long rows: their Jacobian, written at x_b)
+//   k_emit_esh<G>  k_emit with the separable derivatives taken at x_b (tape and long rows: their Jacobian, written at x_b; QUAD rows
+//                  that k_esh_quad of esh_quad.hpp moved: the Jacobian interpolated between x_int and x*)
 #pragma once
 #include "kernels.hpp"
 
@@ -22,7 +23,7 @@ struct EshArgs {
     const double* xi;              // x_int
     const int8_t* sig;             // per extended row: sigma_i when row i takes part (x_int at least 10 f_tol inside), else 0
     double* lam;                   // per extended row: lambda of the row's cut (1: Kelley's cut at x*; set to 1 before a sweep's search)
-    unsigned long long* cnt;       // [0] rows cut at x_b, [1] evaluation passes
+    unsigned long long* cnt;       // [0] rows cut at x_b, [1] evaluation passes, [2] QUAD rows among [0] (k_esh_quad)
     double tol;                    // stop once 0 <= phi <= tol
     int iters;                     // passes per row at most
     int materialize;               // separable rows: also write the Jacobian at x_b (ktn_sep_gencut)
@@ -51,6 +52,10 @@ __device__ __forceinline__ bool esh_step(EshState& s, double phi, double dphi, b
 }
 // the point on the segment; lambda == 1 reads x* itself
 __device__ __forceinline__ double esh_point(double xs, double x0, double lam) { return (lam == 1.0) ? xs : x0 + lam * (xs - x0); }
+
+// A QUAD row's gradient is affine in x, so at x_b it is the interpolation of the Jacobians at x_int (j0) and x* (js).  k_esh_quad
+// (maximum, cut constant, ktn_sep_gencut) and k_emit_esh (the LP row) both take a coefficient from here: the same bits.
+__device__ __forceinline__ double esh_quad_coef(double lam, double js, double j0) { return fma(lam, js - j0, j0); }
 
 // separable rows: G lanes per row.  rows[k] is NL slot k's row; flag == nullptr: every listed row is a candidate.
 template <int G>
@@ -237,13 +242,14 @@ static __global__ __launch_bounds__(kBlock) void k_esh_tape(NlpDev P, const int3
     atomicAdd(&A.cnt[0], 1ull);
 }
 
-// gencut + round_coefs + row append (k_emit) with the separable derivatives at x_b = x_int + lam[r] (x* - x_int)
+// gencut + round_coefs + row append (k_emit) with the separable derivatives at x_b = x_int + lam[r] (x* - x_int); jint (the Jacobian
+// at x_int by Jacobian entry) is NULL unless QUAD rows take part
 template <int G>
 __global__ __launch_bounds__(kBlock) void k_emit_esh(NlpDev P, const int32_t* __restrict__ nl_rows,
                                                      const int32_t* __restrict__ viol_slots, int64_t n_viol,
                                                      const double* __restrict__ x, const double* __restrict__ xi,
                                                      const double* __restrict__ lam, const double* __restrict__ jac,
-                                                     const double* __restrict__ maxc, double cut_coef_rng, int round_coefs,
+                                                     const double* __restrict__ jint, const double* __restrict__ maxc, double cut_coef_rng, int round_coefs,
                                                      int64_t base_row, LpRows L) {
     const int64_t v = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / G;
     const int lane = threadIdx.x & (G - 1);
@@ -252,12 +258,14 @@ __global__ __launch_bounds__(kBlock) void k_emit_esh(NlpDev P, const int32_t* __
     const int64_t beg = P.rowptr[r], end = P.rowptr[r + 1];
     const int64_t dst = L.rowptr[base_row + v];
     const bool sep = P.row_kind[r] == KTN_ROW_SEP;
-    const double lr = sep ? lam[r] : 1.0;
+    const bool quad = jint != nullptr && P.row_kind[r] == KTN_ROW_QUAD && lam[r] < 1.0;
+    const double lr = (sep || quad) ? lam[r] : 1.0;
     const double mx = maxc[r];
     for (int64_t e = beg + lane; e < end; e += G) {
         const int c = P.col[e];
         double der;
         if (sep) { double val; const double2 q = P.pp[e]; atom_eval((unsigned)P.colk[e] >> kKindShift, q.x, q.y, esh_point(x[c], xi[c], lr), val, der); }
+        else if (quad) der = esh_quad_coef(lr, jac[e], jint[e]);
         else der = jac[e];
         if (round_coefs && (der + cut_coef_rng < mx)) der = 0.0;   // model.jl:202-206 (signed max)
         L.col[dst + (e - beg)] = c;

@@ -474,8 +474,13 @@ LpResult Engine::lp_solve(double tol_p, double tol_g, int mode, bool identity_sc
         return lp_solve_core(tol_p, tol_g, mode, identity_scaling);
     }
     if (!dense_ok) return lp_solve_core(tol_p, tol_g, mode, identity_scaling);
-    if (prm.lp_dense_after < 0 || dense_credit > 0) {
-        if (dense_credit > 0) --dense_credit;
+    // (KTN_CUT_SUPPORTING_QUAD with an interior point: every LP the exact kernel can take goes to it.  A supporting cut taken on the
+    //  segment to a loosely solved LP point lands next to the previous one, where Kelley's cut at that point would still be a new
+    //  tangent: measured on the ellipsoid of DESIGN.md section 11, 100 / 231 rounds at n = 4 / 8 with the tolerance schedule against
+    //  49 / 162 from vertices)
+    const bool esh_vertices = esh_quad_mode() && xint_found != 0;
+    if (prm.lp_dense_after < 0 || esh_vertices || dense_credit > 0) {
+        if (dense_credit > 0 && !esh_vertices) --dense_credit;
         LpResult R;
         if (lp_solve_dense(&R)) return R;
         stats["dense_lp_fallbacks"] += 1.0;

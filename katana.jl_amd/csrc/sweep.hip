@@ -1038,7 +1038,7 @@ void Engine::sweep(const double* d_x, double f_tol, int64_t* nviol_out, double* 
     last_sweep_cuts = 0;
     stats["sweeps"] += 1.0;
     if (m_nl == 0) return;
-    if (prm.cut_algo == KTN_CUT_SUPPORTING && !esh_ready) esh_prepare();
+    if (esh_mode() && !esh_ready) esh_prepare();
     NlpDev P = nlp_view();
     SweepOut O = sweep_view();
     KTN_HIP(hipMemsetAsync(d_scal.p, 0, sizeof(double), stream));
@@ -1162,7 +1162,7 @@ hipExtLaunchKernelGGL((k_sep_eval_blk<G, BC, BS, U>), dim3((unsigned)(num_cus * 
         return;
     }
     if (V > 0) {
-        if (prm.cut_algo == KTN_CUT_SUPPORTING) esh_search(d_x, f_tol);     // (esh.hip: moves the selected rows' cuts to x_b)
+        if (esh_mode()) esh_search(d_x, f_tol);     // (esh.hip: moves the selected rows' cuts to x_b)
         lp_rowptr.resize((size_t)(M + V + 1), stream);
         lp_lo.resize((size_t)(M + V), stream);
         lp_hi.resize((size_t)(M + V), stream);
@@ -1176,7 +1176,7 @@ hipExtLaunchKernelGGL((k_sep_eval_blk<G, BC, BS, U>), dim3((unsigned)(num_cus * 
         LpRows L = lp_view();
         LAUNCH_1(k_compact, m_nl, stream, P, d_nlrows.p, m_nl, d_flag.p, d_rank.p, d_cntscan.p, d_bconst.p, M, NNZ, L,
                  d_violslots.p, d_lastcut.p, d_cutprev.p, (int)(prm.lp_dual_inherit && !glists));
-        if (prm.cut_algo == KTN_CUT_SUPPORTING) esh_emit(d_x, V);
+        if (esh_mode()) esh_emit(d_x, V);
         else LAUNCH_G(grp_sweep, k_emit, V, stream, P, d_nlrows.p, d_violslots.p, V, d_x, d_jac.p, d_maxc.p,
                       prm.cut_coef_rng, 1, M, L);
         check_launch();

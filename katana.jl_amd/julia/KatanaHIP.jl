@@ -20,7 +20,7 @@ using JuMP
 import ..KatanaSolver, ..AbstractKatanaSeparator, ..EpigraphNLPEvaluator          # src/solver.jl:6, src/separators.jl:8, src/nlpeval.jl:6
 import ..initialize!, ..precompute!, ..gencut, ..isconstrsat                      # the separator API, src/separators.jl:23-53
 
-export KatanaHipSeparator, supporting_hyperplane_cut
+export KatanaHipSeparator, supporting_hyperplane_cut, supporting_hyperplane_quad_cut
 
 const LIB = get(ENV, "KATANA_HIP_LIB", joinpath(dirname(@__FILE__), "..", "libkatana_hip.so"))
 
@@ -41,6 +41,7 @@ const KTN_OP_COS   = Int32(12)
 const KTN_ROW_SEP, KTN_ROW_TAPE, KTN_ROW_HOST = UInt8(0), UInt8(1), UInt8(2)
 const KTN_ROW_QUAD = UInt8(3)                                                     # sparse-quadratic rows (quad_ptr / quad_col / quad_val)
 const KTN_CUT_KELLEY, KTN_CUT_SUPPORTING = Int32(0), Int32(1)                     # ktn_params.cut_algo
+const KTN_CUT_SUPPORTING_QUAD = Int32(2)
 const STATUS = [:None, :Optimal, :Unbounded, :Infeasible, :UserLimit, :Error]     # KTN_STATUS_* + 1
 
 # :call heads of a MathProgBase expression graph the device tape interpreter evaluates
@@ -295,11 +296,15 @@ end
 # hyperplanes (cut_algo = KTN_CUT_SUPPORTING): KatanaSolver(lp, separator = KatanaFirstOrderSeparator(supporting_hyperplane_cut)).
 # The engine's device search serves it; the reference's own host loop cannot call it.
 supporting_hyperplane_cut(sep, a, b, i) = error("supporting_hyperplane_cut is served by the HIP engine (KatanaHipModel)")
+# The same with the declared-quadratic rows (KTN_ROW_QUAD) taking part, their boundary point in closed form (KTN_CUT_SUPPORTING_QUAD)
+supporting_hyperplane_quad_cut(sep, a, b, i) = error("supporting_hyperplane_quad_cut is served by the HIP engine (KatanaHipModel)")
 
 # cut_algo of a KatanaSolver: the `algo` of its separator, when that is a KatanaFirstOrderSeparator
 function cut_algo_of(s)
     sep = s.model_params.separator
-    (isdefined(sep, :algo) && sep.algo === supporting_hyperplane_cut) ? KTN_CUT_SUPPORTING : KTN_CUT_KELLEY
+    isdefined(sep, :algo) || return KTN_CUT_KELLEY
+    sep.algo === supporting_hyperplane_quad_cut && return KTN_CUT_SUPPORTING_QUAD
+    sep.algo === supporting_hyperplane_cut ? KTN_CUT_SUPPORTING : KTN_CUT_KELLEY
 end
 
 # `s` is the reference's KatanaSolver (src/solver.jl:6-10): lp_solver is ignored (the LP runs on the GPU),

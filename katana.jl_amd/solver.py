@@ -13,7 +13,8 @@ STATUS_SYMBOLS = {L.STATUS_NONE: "None", L.STATUS_OPTIMAL: "Optimal", L.STATUS_U
 _SUPPORTED_FEATURES = ("VisData",)   # src/solver.jl:31-32
 # the cut generator of KatanaFirstOrderSeparator(algo) (src/separators.jl:73-76): ktn_params.cut_algo
 CUT_ALGOS = {"kelley": L.CUT_KELLEY, "linear_oa_cut": L.CUT_KELLEY,
-             "supporting_hyperplane": L.CUT_SUPPORTING, "supporting_hyperplane_cut": L.CUT_SUPPORTING}
+             "supporting_hyperplane": L.CUT_SUPPORTING, "supporting_hyperplane_cut": L.CUT_SUPPORTING,
+             "supporting_hyperplane_quad": L.CUT_SUPPORTING_QUAD, "supporting_hyperplane_quad_cut": L.CUT_SUPPORTING_QUAD}
 
 
 def _cut_algo_code(cut_algo):
@@ -41,7 +42,8 @@ class KatanaSolver:
     `device`, `profile` reach the GPU LP (ktn_params).
 
     `cut_algo` picks the separator's cut generator: "kelley" (the reference's linear_oa_cut, the default) or
-    "supporting_hyperplane" (cut at the boundary point between an interior point and x*), or the ktn_params code."""
+    "supporting_hyperplane" (cut at the boundary point between an interior point and x*), "supporting_hyperplane_quad" (the same
+    with the declared-quadratic rows taking part, their boundary point in closed form), or the ktn_params code."""
 
     def __init__(self, lp_solver=None, separator=None, features=(), f_tol=1e-6, cut_coef_rng=1e9, log_level=10,
                  iter_cap=10000, obj_eps=-1.0, cut_algo="kelley", **gpu_options):
@@ -455,15 +457,20 @@ class LinearQuadraticModel(KatanaNonlinearModel):
         optimize()                                                assembles the QuadNLP, loads it and solves
 
     (quad_triplets_to_engine holds both conversions.)  The 8-argument loadproblem(num_var, num_constr, ..., d) of
-    NonlinearModel keeps working on it, and the getters are inherited."""
+    NonlinearModel keeps working on it, and the getters are inherited.
+
+    The engine sees the problem only inside optimize() and forgets its interior point at every load, so set_interior_point(x) on
+    the 7-argument path keeps x on this object and hands it over after each such load; set_interior_point(None) clears it."""
 
     def __init__(self, solver):
         super().__init__(solver)
         self._lq = None
+        self._xint_pending = None
 
     def loadproblem(self, *args):
         if len(args) == 8:
             self._lq = None
+            self._xint_pending = None
             return super().loadproblem(*args)
         if len(args) != 7:
             raise TypeError("loadproblem(A, collb, colub, obj, rowlb, rowub, sense) or loadproblem(num_var, num_constr, l_var, "
@@ -490,6 +497,19 @@ class LinearQuadraticModel(KatanaNonlinearModel):
         rows = [(ci[rp[i]:rp[i + 1]], av[rp[i]:rp[i + 1]], [], [], [], 0.0) for i in range(m)]
         self._lq = dict(n=n, collb=collb, colub=colub, obj=obj, sense=sense, rows=rows, lb=list(rowlb), ub=list(rowub),
                         objq=None, dirty=True)
+        self._xint_pending = None
+
+    def set_interior_point(self, x):
+        q = self._lq
+        if q is None:                                    # the 8-argument path: the problem is loaded, the engine keeps the point
+            return super().set_interior_point(x)
+        if x is not None:
+            x = _f64(x).copy()
+            if len(x) != q["n"]:
+                raise ValueError("set_interior_point: %d entries for %d variables" % (len(x), q["n"]))
+        self._xint_pending = x
+        if not q["dirty"]:                               # already loaded and unchanged since: the engine can take it now
+            super().set_interior_point(x)
 
     def _need_lq(self):
         if self._lq is None:
@@ -518,4 +538,6 @@ class LinearQuadraticModel(KatanaNonlinearModel):
             d = QuadNLP(q["n"], q["obj"], 0.0, q["objq"], q["rows"])
             KatanaNonlinearModel.loadproblem(self, q["n"], len(q["rows"]), q["collb"], q["colub"], q["lb"], q["ub"], q["sense"], d)
             q["dirty"] = False
+            if self._xint_pending is not None:
+                KatanaNonlinearModel.set_interior_point(self, self._xint_pending)
         return super().optimize()

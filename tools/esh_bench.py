@@ -3,10 +3,14 @@
   vertex family   cfg3, cfg3_qp, cfg2 (seed 0)
   off the vertex  make_instance(n, m_nl = n / 10, k = 16) at n = 200 / 500 / 1000, bound_frac 0 and 0.5, explog and quad
   n-ball          the reference's test/misc.jl family, min sum(x) s.t. sum(x^2) <= 1, at n = 128 / 512 (optimum -sqrt(n))
+  quad            KTN_ROW_QUAD rows, Kelley against supporting_hyperplane_quad (closed-form boundary point): the ellipsoid
+                  min c'x s.t. 1/2 (x - x0)'Q(x - x0) <= 4 at n = 8 / 16 / 40 with the caller's point x0 and with the engine's own
+                  (where its auxiliary problem finds one), and one QCQP of 200 rows 1/2 x'Q_i x <= 1 on 16 of 2 000 columns each
+                  (the rows of tools/quad_bench.py), interior point 0, against the Kelley run's objective
 
 Each line: status, ECP rounds, PDHG iterations, solve seconds (or the stated round budget), objective error against the
 planted value, and the interior-point and root-search seconds and counts of the supporting-hyperplane run.
-Usage: python tools/esh_bench.py [iter_cap=300] [cases=all|vertex|off|ball]"""
+Usage: python tools/esh_bench.py [iter_cap=300] [cases=all|vertex|off|ball|quad]"""
 import json
 import math
 import os
@@ -15,16 +19,17 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+import numpy as np                                                 # noqa: E402
 import katana_jl_amd as ktn                                        # noqa: E402
 
 iter_cap = int(sys.argv[1]) if len(sys.argv) > 1 else 300
 which = sys.argv[2] if len(sys.argv) > 2 else "all"
 STATS = ("pdhg_iters", "esh_rows", "esh_fallback_rows", "esh_newton_steps", "esh_root_time_s", "esh_interior_found",
-         "esh_interior_rounds", "esh_interior_s", "esh_interior_depth", "esh_interior_time_s")
+         "esh_interior_rounds", "esh_interior_s", "esh_interior_depth", "esh_interior_time_s", "esh_quad_rows")
 
 
-def run(name, load, opt, algo):
-    m = ktn.NonlinearModel(ktn.KatanaSolver(log_level=0, iter_cap=iter_cap, cut_algo=algo))
+def run(name, load, opt, algo, **kw):
+    m = ktn.NonlinearModel(ktn.KatanaSolver(log_level=0, iter_cap=iter_cap, cut_algo=algo, **kw))
     load(m)
     t0 = time.perf_counter()
     st = m.optimize()
@@ -35,6 +40,7 @@ def run(name, load, opt, algo):
         v = m.stat(k)
         line[k] = v if v == v else None
     print(json.dumps(line), flush=True)
+    return m
 
 
 def instance_case(name, inst):
@@ -75,3 +81,54 @@ if which in ("all", "off"):
 if which in ("all", "ball"):
     for n in (128, 512):
         ball_case(n)
+
+
+def ellipsoid_case(n, rho=4.0):
+    """tests/quad_cases.ellipsoid with radius rho: f* = c'x0 - sqrt(2 rho c'Q^-1 c)"""
+    rng = np.random.default_rng(n)
+    Uo, _ = np.linalg.qr(rng.standard_normal((n, n)))
+    Q = Uo @ np.diag(np.exp(rng.uniform(0.0, math.log(4.0), n))) @ Uo.T
+    Q = (Q + Q.T) / 2
+    x0, c = rng.uniform(-1.0, 1.0, n), rng.uniform(-1.0, 1.0, n)
+    fstar = float(c @ x0 - math.sqrt(2.0 * rho * (c @ np.linalg.solve(Q, c))))
+    r, cc = np.meshgrid(np.arange(n), np.arange(n), indexing="ij")
+    d = ktn.QuadNLP(n, c, 0.0, None, [(np.arange(n), -(Q @ x0), r.ravel(), cc.ravel(), Q.ravel(), 0.5 * float(x0 @ Q @ x0))])
+
+    def load(point):
+        def f(m):
+            m.loadproblem(n, 1, np.full(n, -10.0), np.full(n, 10.0), [-math.inf], [rho], "Min", d)
+            if point is not None:
+                m.set_interior_point(point)
+        return f
+    run("ellipsoid_%d" % n, load(None), fstar, "kelley")
+    run("ellipsoid_%d_centre" % n, load(x0), fstar, "supporting_hyperplane_quad")
+    run("ellipsoid_%d_engine" % n, load(None), fstar, "supporting_hyperplane_quad", esh_interior_iters=200)
+
+
+def qcqp_case(n=2000, m=200, k=16):
+    """the rows of tools/quad_bench.py (Q_i = 2 I + random symmetric off-diagonal entries of size 1 / k on k distinct columns),
+    min c'x in the +-10 box; x = 0 is 1 inside every row.  No closed form: obj_err is against the Kelley run's objective"""
+    rng = np.random.default_rng(1000 + k)
+    cols = np.stack([np.sort(rng.choice(n, k, replace=False)) for _ in range(m)])
+    R = rng.uniform(-1.0, 1.0, (m, k, k)) / k
+    R[:, np.arange(k), np.arange(k)] = 0.0
+    Qm = (R + R.transpose(0, 2, 1)) / 2 + 2.0 * np.eye(k)
+    c = rng.uniform(-1.0, 1.0, n)
+    c[np.setdiff1d(np.arange(n), cols.ravel())] = 0.0               # (columns in no row would only sit at a box bound)
+    rows = [(cols[i], np.zeros(k), np.repeat(cols[i], k), np.tile(cols[i], k), Qm[i].ravel(), 0.0) for i in range(m)]
+    d = ktn.QuadNLP(n, c, 0.0, None, rows)
+
+    def load(point):
+        def f(mm):
+            mm.loadproblem(n, m, np.full(n, -10.0), np.full(n, 10.0), np.full(m, -math.inf), np.ones(m), "Min", d)
+            if point is not None:
+                mm.set_interior_point(point)
+        return f
+    mk = run("qcqp_%dx%d" % (m, k), load(None), 0.0, "kelley")
+    run("qcqp_%dx%d_zero" % (m, k), load(np.zeros(n)), mk.getobjval(), "supporting_hyperplane_quad")
+
+
+if which in ("all", "quad"):
+    for n in (8, 16, 40):
+        ellipsoid_case(n)
+    qcqp_case()

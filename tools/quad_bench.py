@@ -2,14 +2,17 @@
 columns of 1e5 variables (Q_i = 2 I + random symmetric off-diagonal entries), and the same rows as expression tapes
 sum_i x_i (x_i + sum_{j > i} q_ij x_j): 4 k (k + 1) / 2 - 1 nodes -- at k = 8 that is 143 nodes, 294 of the shape-class kernel's 312
 LDS cells, so the classed kernel takes the row; from k = 9 on the row interpreter does.
-usage: quad_bench.py k [rows=10000] [reps=12] [--tape | --no-tape]
+usage: quad_bench.py k [rows=10000] [reps=12] [--tape | --no-tape | --esh]
   default   one QUAD handle and one tape handle of THIS build in one process (profile = 1): g and the Jacobian compared
             (relative, 1e-12), then both timed, alternating, by the events around their launches of the sweep (quad_eval_time_s /
             tape_eval_time_s): us per sweep min / median / max, algorithmic bytes, the fraction of the 8 TB/s HBM peak, load_s
   --no-tape the QUAD handle alone (k = 128: the tape form is 3.3e8 nodes)
   --tape    the tape handle alone, existing API only (load, precompute, then reset + precompute + sweep `reps` times): the driver to
             put under rocprofv3 --kernel-trace --stats.  KTN_PKG_ROOT=<checkout> imports the package from another (built) checkout,
-            e.g. the parent commit's, whose description struct differs from this one's"""
+            e.g. the parent commit's, whose description struct differs from this one's
+  --esh     the QUAD handle alone with cut_algo = supporting_hyperplane_quad and the interior point 0 (every row violated at x, every
+            row moved): precompute + sweep `reps` times, the driver to put under rocprofv3 --kernel-trace --stats for k_esh_quad
+            next to k_quad_jac"""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.environ.get("KTN_PKG_ROOT") or ROOT)
@@ -18,7 +21,7 @@ import katana_jl_amd as ktn
 
 L = ktn._lib
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
-tape_only, quad_only = "--tape" in sys.argv, "--no-tape" in sys.argv
+tape_only, quad_only, esh_only = "--tape" in sys.argv, "--no-tape" in sys.argv, "--esh" in sys.argv
 k = int(args[0]) if len(args) > 0 else 32
 m = int(float(args[1])) if len(args) > 1 else 10000
 reps = int(args[2]) if len(args) > 2 else 12
@@ -68,9 +71,9 @@ def tape_desc():
                               obj_linear=True, obj_kind=L.ROW_SEP, obj_col=[0], obj_atom_kind=[0], obj_p0=[1.0], obj_p1=[0.0]), Lr
 
 
-def load(d, profile):
+def load(d, profile, **kw):
     t0 = time.perf_counter()
-    model = ktn.NonlinearModel(ktn.KatanaSolver(log_level=0, profile=profile, purge_age=0, cut_cap_factor=0.0))
+    model = ktn.NonlinearModel(ktn.KatanaSolver(log_level=0, profile=profile, purge_age=0, cut_cap_factor=0.0, **kw))
     model.loadproblem(n, m, np.full(n, -INF), np.full(n, INF), np.full(m, -INF), np.ones(m), "Min", d)
     load_s = time.perf_counter() - t0
     sep = ktn.KatanaHipSeparator(model); sep.initialize()
@@ -86,6 +89,16 @@ if tape_only:
         nv, mv = sep.sweep(1e-6)
     print(json.dumps(dict(form="tape", k=k, rows=m, reps=reps, tape_ops_per_row=Lr, violated=nv, maxviol=mv, load_s=round(load_s, 3),
                           classed_rows=int(model.stat("tape_classed_rows")), interp_rows=int(model.stat("tape_interp_rows")))))
+    sys.exit(0)
+
+if esh_only:
+    model, sep, load_s = load(quad_desc(), 0, cut_algo="supporting_hyperplane_quad")
+    model.set_interior_point(np.zeros(n))
+    for r in range(reps):
+        model.reset(); sep.precompute(x)
+        nv, mv = sep.sweep(1e-6)
+    print(json.dumps(dict(form="quad, supporting hyperplanes", k=k, rows=m, reps=reps, violated=nv, load_s=round(load_s, 3),
+                          esh_quad_rows=int(model.stat("esh_quad_rows")), esh_fallback_rows=int(model.stat("esh_fallback_rows")))))
     sys.exit(0)
 
 ktn.NonlinearModel(ktn.KatanaSolver(log_level=0))                      # (device initialisation is not part of load_s)
