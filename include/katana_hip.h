@@ -64,9 +64,10 @@ extern "C" {
                             stored in full -- both (r, c) and (c, r).  Symmetry is the caller's contract and is NOT checked:
                             the gradient entry is computed as a_e + s_e with s_e = sum_k q_k x[qcol_k], which is the
                             derivative only of a symmetric Q_i.  Every qcol_k must be a column of the row's own structure.
-                            ktn_optimize_blocks falls back to the ordinary loop on such rows, the supporting-hyperplane
-                            root search keeps Kelley's cut on them; row-sharding them is untested and the Python host
-                            mirror refuses it                                                                         */
+                            ktn_optimize_blocks evaluates such constraint rows inside its device-side loop (a handle whose
+                            OBJECTIVE is KTN_ROW_QUAD keeps the ordinary loop: see there), the supporting-hyperplane
+                            root search keeps Kelley's cut on them unless cut_algo = KTN_CUT_SUPPORTING_QUAD; row-sharding
+                            them is untested and the Python host mirror refuses it                                     */
 
 /* MathProgBase.eval_g + eval_jac_g (src/separators.jl:112-113) for the KTN_ROW_HOST rows: write g[i] and
  * jac[rowptr[i] .. rowptr[i+1]) (CSR order of ktn_nlp_desc) for every such row i; other entries are ignored.
@@ -466,10 +467,15 @@ int ktn_set_blocks(ktn_handle h, int64_t nblocks, const int64_t* col_offsets);
 /* MathProgBase.optimize! for such a batch with the WHOLE loop of src/model.jl:257-309 of every instance inside its own
  * workgroup (csrc/batch_ecp.hpp): LP scaling, step-size estimate, PDHG with its checks and restarts, the sweep over the
  * instance's NL rows, cut append, column mirror, tolerance schedule and stop rule -- no instance waits for another.  Needs
- * separable or tape rows (no KTN_ROW_HOST), a linear :Min objective, finite variable bounds and the instances' rows grouped instance after instance
- * (instances.fuse_instances, nlp.fuse_problems); `cut_capacity` = room for that many cuts per NL row (<= 0: 12).  Falls back to the ordinary
- * loop when the batch does not qualify or an instance runs out of room.  Returns the status like ktn_optimize; getters as usual
- * (numiters = the largest per-instance count, numcuts = the sum). */
+ * separable, tape or KTN_ROW_QUAD constraint rows (no KTN_ROW_HOST), linear or not, a linear :Min objective, finite variable bounds and the
+ * instances' rows grouped instance after instance (instances.fuse_instances, nlp.fuse_problems); `cut_capacity` = room for that many cuts
+ * per NL row (<= 0: 12).  One deliberate exception: a handle whose objective row has kind KTN_ROW_QUAD -- even declared linear, as a
+ * hand-fused QuadNLP has it -- keeps the ordinary loop; nlp.fuse_problems always emits a KTN_ROW_SEP objective of LIN atoms (a quadratic
+ * objective becomes a QUAD constraint row and an epigraph variable per instance there), so nothing that comes through it is affected.
+ * Falls back to the ordinary loop when the batch does not qualify or an instance runs out of room or of LP iterations.  Returns the
+ * status like ktn_optimize; getters as usual (numiters = the largest per-instance count, numcuts = the sum).  Stats (ktn_get_stat):
+ * "ecp_blocks_launches", "ecp_blocks_fallbacks" (cumulative), "ecp_blocks_tape_rows", "ecp_blocks_quad_rows" (tape / QUAD NL rows the
+ * last device loop served). */
 int ktn_optimize_blocks(ktn_handle h, int32_t cut_capacity);
 
 /* ---- row-sharded LP over several GPUs (no reference counterpart: it splits the LP re-solve of

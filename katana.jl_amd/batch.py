@@ -28,9 +28,10 @@ def _all_instances(items):
 
 def solve_batch(solver, instances, threads=16, describe=SeparableNLP, fused=False, per_instance_lp=False, device_loop=None):
     """Solve every instance; returns (results, wall_seconds).  results[i] = dict(status, objval, iters,
-    numcuts, x) in the order of `instances`.  The items are SeparableInstances or -- expression-built models, tape rows
-    included -- Problems (katana_jl_amd.Problem: the arguments of loadproblem!) or jump_like.Models; a fused batch of the
-    latter is the block-diagonal union of nlp.fuse_problems, and each instance's objective is reported in its own sense.
+    numcuts, x) in the order of `instances`.  The items are SeparableInstances or -- expression-built and declared-quadratic
+    models, tape and KTN_ROW_QUAD rows included -- Problems (katana_jl_amd.Problem: the arguments of loadproblem!) or
+    jump_like.Models; a fused batch of the latter is the block-diagonal union of nlp.fuse_problems (a quadratic objective
+    becomes the instance's own epigraph row there), and each instance's objective is reported in its own sense.
 
     fused=True solves the block-diagonal union of the instances as ONE problem (instances.fuse_instances): the
     cutting-plane loop, the sweep and every PDHG launch then serve the whole batch at once, and the stop rule --
@@ -84,8 +85,10 @@ class FusedBatch:
         import numpy as np
         from .instances import fuse_instances
         self.instances = instances
-        if not _all_instances(instances):                          # Problems / Models, tape rows allowed (nlp.fuse_problems)
-            self.big, self.offs, self._objinfo = fuse_problems([_as_problem(i) for i in instances])
+        if not _all_instances(instances):                          # Problems / Models, tape and QUAD rows allowed (nlp.fuse_problems)
+            probs = [_as_problem(i) for i in instances]
+            self.big, self.offs, self._objinfo = fuse_problems(probs, allow_quad=True)
+            self._nvar = [int(p.num_var) for p in probs]            # (a quadratic objective adds its epigraph variable behind them)
             self.m.loadproblem(*self.big)
             if self.per_instance_lp or self.device_loop:
                 self.m.set_blocks(self.offs)
@@ -119,10 +122,11 @@ class FusedBatch:
         if self._objinfo is not None:
             # each instance's objective in its own sense, from its own LIN coefficients and constant on its slice of x
             common["ecp_blocks_tape_rows"] = m.stat("ecp_blocks_tape_rows")
+            common["ecp_blocks_quad_rows"] = m.stat("ecp_blocks_quad_rows")
             out = []
             for k, (cols, coefs, c0) in enumerate(self._objinfo):
                 xk = x[offs[k]:offs[k + 1]]
-                out.append(dict(common, objval=float(np.sum(coefs * xk[cols]) + c0), x=xk))
+                out.append(dict(common, objval=float(np.sum(coefs * xk[cols]) + c0), x=xk[:self._nvar[k]]))
             return out
         # per-instance objectives: all atoms of the fused objective at once, then sums by instance
         kind, p0, p1, col = self._obj

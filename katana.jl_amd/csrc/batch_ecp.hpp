@@ -5,8 +5,8 @@
 // tolerance schedule and the stop rule -- so that no instance ever waits for another (with a host-driven round per
 // cutting-plane iteration every round waits for its slowest instance: csrc/batch_lp.hpp).
 //
-// The batch is loaded as one block-diagonal problem (instances.fuse_instances, nlp.fuse_problems) of separable or tape rows
-// with a linear objective;
+// The batch is loaded as one block-diagonal problem (instances.fuse_instances, nlp.fuse_problems) of separable, tape or
+// KTN_ROW_QUAD rows with a linear objective;
 // ktn_loadproblem builds the fused LP of the linear rows as usual.  k_ecp_blocks then works on a per-instance ARENA in
 // global memory (the instance's LP in local indices with room for its cuts): CSR rows (unscaled + scaled values), CSC
 // mirror (unscaled + scaled), row bounds, duals, diagonal scalings, scaled problem vectors.  The PDHG iterates live in
@@ -14,6 +14,7 @@
 // mirror is sorted by row after the counting-sort scatter.
 #pragma once
 #include "kernels.hpp"
+#include "quad_rows.hpp"
 
 namespace ktn {
 
@@ -35,6 +36,13 @@ struct EcpBatch {
     NlpDev P; const int32_t* nl_rows;                                                                                 // NL rows (global ids)
     double* jac;                     // Jacobian scratch indexed like the structure (tape rows: written by the eval pass, read by the emit pass)
     int has_tape;                    // some NL row is a KTN_ROW_TAPE row (0: the sweep is the separable one alone)
+    // KTN_ROW_QUAD rows among the NL rows (quad_rows.hpp): the engine's NL launch list; QUAD entries are numbered in row order and
+    // NL rows are grouped by instance, so instance b owns rows [blk_qrow[b], blk_qrow[b+1]) and positions [blk_qent[b], blk_qent[b+1])
+    int has_quad;                    // some NL row is a KTN_ROW_QUAD row (0: nothing below is read)
+    int quad_group;                  // lanes per Jacobian entry of the entry pass (4 .. 64)
+    QuadDev Q;
+    const int32_t* q_rows; const int64_t* q_slots; const int64_t* q_tbase; const int64_t* q_ent;   // q_ent NULL: t = position
+    const int64_t* blk_qrow; const int64_t* blk_qent;                                              // [nb + 1] each
     // ---- arenas
     const EcpArena* arena;
     int32_t* rptr; uint16_t* rcol; double* rval; double* rsval; double* lo; double* hi; double* y; double* dr; double* loh; double* hih;
@@ -127,6 +135,26 @@ __device__ __forceinline__ void ecp_spmv(int count, const int32_t* __restrict__ 
 // (DESIGN.md section 8).
 static __device__ __forceinline__ double ecp_tape_row(const NlpDev& P, int32_t r, const double* xs, int c0, double* jac) {
     return tape_row_eval(P, r, [&](int32_t c) { return xs[c - c0]; }, jac);
+}
+
+// Entry pass of the instance's QUAD rows (k_quad_jac inside the workgroup): G lanes per Jacobian entry walk its Q segment,
+// consecutive lanes on consecutive Q entries, x from the LDS copy; lane 0 writes jac[e] and vterm[t] (quad_entry).
+template <int G>
+static __device__ __forceinline__ void ecp_quad_entries(const EcpBatch& B, int64_t p0, int64_t p1, const double* xs, int c0) {
+    const int lane = threadIdx.x & (G - 1);
+    for (int64_t p = p0 + threadIdx.x / G; p < p1; p += kEcpThreads / G) {
+        const int64_t t = B.q_ent ? B.q_ent[p] : p;
+        const int64_t beg = B.Q.qptr[t], end = B.Q.qptr[t + 1];
+        double s = 0.0;
+        for (int64_t k = beg + lane; k < end; k += G) s += B.Q.qval[k] * xs[B.Q.qcol[k] - c0];
+        s = group_sum<G>(s);                                   // (p is uniform within a lane group: the butterfly never leaves it)
+        if (lane == 0) {
+            const int64_t e = B.Q.jidx[t];
+            const QuadEntry qe = quad_entry(B.P.pp[e].x, s, xs[(B.P.colk[e] & kColMask) - c0]);
+            B.jac[e] = qe.jac;
+            B.Q.vterm[t] = qe.vterm;
+        }
+    }
 }
 
 static __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B) {
@@ -518,15 +546,18 @@ static __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B) {
         __syncthreads();
 
         // ============================================================ separator sweep over the instance's NL rows ======
-        // precompute! + isconstrsat (src/separators.jl:111-120): 16 lanes per separable row, one lane per tape row; flags and
-        // row lengths into icnt
+        // precompute! + isconstrsat (src/separators.jl:111-120): 16 lanes per separable row, one lane per tape row, G lanes per
+        // Jacobian entry and then 16 per row for QUAD rows; flags and row lengths into icnt
         double mv[1] = {0.0};
         int bad_nf = 0;
         {
             const int lane = tid & 15;
             for (int i = tid / 16; i < m_nl; i += kEcpThreads / 16) {
                 const int32_t gr = B.nl_rows[nl0 + i];
-                if (B.has_tape && B.P.row_kind[gr] == KTN_ROW_TAPE) continue;          // (the device row_kind also holds kRowSepLong)
+                if (B.has_tape | B.has_quad) {                                           // (the device row_kind also holds kRowSepLong)
+                    const uint8_t rk = B.P.row_kind[gr];
+                    if (rk == KTN_ROW_TAPE || rk == KTN_ROW_QUAD) continue;
+                }
                 const int64_t beg = B.P.rowptr[gr], end = B.P.rowptr[gr + 1];
                 double g = 0.0;
                 for (int64_t e = beg + lane; e < end; e += 16) {
@@ -558,6 +589,36 @@ static __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B) {
                     icnt[i] = sat ? 0 : (int)(B.P.rowptr[gr + 1] - B.P.rowptr[gr]);
                     yts[i] = g;
                     if (!sat) { double d = fmax(g - ub, lb - g); if (!(d == d)) d = __builtin_inf(); mv[0] = fmax(mv[0], d); }
+                }
+            }
+            // QUAD rows: the two passes of quad_rows.hpp inside the workgroup.  Entry-parallel first (a 1 000-entry row with a
+            // diagonal Q and a 3-entry row cost their own work), then 16 lanes per row over the value terms
+            if (B.has_quad) {
+                const int64_t pe0 = B.blk_qent[b], pe1 = B.blk_qent[b + 1];
+                switch (B.quad_group) {
+                    case 4: ecp_quad_entries<4>(B, pe0, pe1, xs, (int)c0); break;
+                    case 8: ecp_quad_entries<8>(B, pe0, pe1, xs, (int)c0); break;
+                    case 16: ecp_quad_entries<16>(B, pe0, pe1, xs, (int)c0); break;
+                    case 32: ecp_quad_entries<32>(B, pe0, pe1, xs, (int)c0); break;
+                    default: ecp_quad_entries<64>(B, pe0, pe1, xs, (int)c0); break;
+                }
+                __syncthreads();
+                for (int64_t qi = B.blk_qrow[b] + tid / 16; qi < B.blk_qrow[b + 1]; qi += kEcpThreads / 16) {
+                    const int32_t gr = B.q_rows[qi];
+                    const int i = (int)(B.q_slots[qi] - nl0);
+                    const int len = (int)(B.P.rowptr[gr + 1] - B.P.rowptr[gr]);
+                    const int64_t tb = B.q_tbase[qi];
+                    double g = 0.0;
+                    for (int e = lane; e < len; e += 16) g += B.Q.vterm[tb + e];
+                    g = group_sum<16>(g);
+                    if (lane == 0) {
+                        g += B.P.rconst[gr];
+                        const double lb = B.P.lb[gr], ub = B.P.ub[gr];
+                        const bool sat = (g >= lb - f_eff) && (g <= ub + f_eff);       // NaN -> violated
+                        icnt[i] = sat ? 0 : len;
+                        yts[i] = g;
+                        if (!sat) { double d = fmax(g - ub, lb - g); if (!(d == d)) d = __builtin_inf(); mv[0] = fmax(mv[0], d); }
+                    }
                 }
             }
         }
@@ -613,14 +674,15 @@ static __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B) {
                 const int32_t gr = B.nl_rows[nl0 + i];
                 const int64_t beg = B.P.rowptr[gr], end = B.P.rowptr[gr + 1];
                 const int dst = rptr[rnew];
-                const bool tape = B.has_tape && B.P.row_kind[gr] == KTN_ROW_TAPE;     // its entries are in B.jac already
+                // (tape and QUAD rows: the eval pass left their entries in B.jac)
+                const bool in_jac = (B.has_tape && B.P.row_kind[gr] == KTN_ROW_TAPE) || (B.has_quad && B.P.row_kind[gr] == KTN_ROW_QUAD);
                 double dot = 0.0, mx = -__builtin_inf();
                 int nf = 0;
                 for (int64_t e = beg + lane; e < end; e += 16) {
                     const int ck = B.P.colk[e];
                     const int cl = (ck & kColMask) - (int)c0;
                     double der;
-                    if (tape) {
+                    if (in_jac) {
                         der = B.jac[e];
                     } else {
                         const double2 pp = B.P.pp[e];

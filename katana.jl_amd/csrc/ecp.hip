@@ -10,13 +10,19 @@ namespace ktn {
 // Throughput mode, device-side loop (batch_ecp.hpp).  Returns false when the problem does not qualify or an instance
 // could not finish (arena overflow, LP status): the caller then runs the ordinary loop.
 bool Engine::optimize_blocks_device(int cap_mul) {
-    // (rows: separable or tape, linear or not; k_ecp_blocks evaluates tape rows with the interpreter of k_tape_eval)
+    // (rows: separable, tape or QUAD, linear or not; k_ecp_blocks evaluates tape rows with the interpreter of k_tape_eval and QUAD
+    //  rows with the two passes of quad_rows.hpp.  A handle whose OBJECTIVE row is KTN_ROW_QUAD -- a hand-fused QuadNLP; nlp.fuse_problems
+    //  always emits a separable objective of LIN atoms -- keeps the ordinary loop: include/katana_hip.h, ktn_optimize_blocks)
     if (n_blocks <= 0 || !obj_linear || sense != KTN_MIN || has_inf_bound || n_host > 0 || prm.vis_data) return false;
-    for (int64_t i = 0; i < m_ext - 1; ++i) if (h_rowkind[(size_t)i] != KTN_ROW_SEP && h_rowkind[(size_t)i] != KTN_ROW_TAPE) return false;
+    if (h_rowkind[(size_t)(m_ext - 1)] == KTN_ROW_QUAD) return false;
+    for (int64_t i = 0; i < m_ext - 1; ++i)
+        if (h_rowkind[(size_t)i] != KTN_ROW_SEP && h_rowkind[(size_t)i] != KTN_ROW_TAPE && h_rowkind[(size_t)i] != KTN_ROW_QUAD) return false;
     const int nb = (int)n_blocks;
     auto block_of_col = [&](int64_t c) { return (int)(std::upper_bound(h_blkcol.begin(), h_blkcol.end(), c) - h_blkcol.begin()) - 1; };
     // linear rows of the loaded LP (in original row order) and NL slots must be grouped by instance, instance after instance
     std::vector<int64_t> lin_rows, blk_lin((size_t)nb + 1, 0), blk_nl((size_t)nb + 1, 0), nnz_lin((size_t)nb, 0), nnz_nl((size_t)nb, 0);
+    // the instances' ranges of the QUAD NL launch list (build_quad_rows: rows and entry positions in ascending row order)
+    std::vector<int64_t> blk_qrow((size_t)nb + 1, 0), blk_qent((size_t)nb + 1, 0);
     {
         std::vector<char> is_nl((size_t)m0, 0);
         for (auto r : h_nlrows) if (r < m0) is_nl[(size_t)r] = 1;
@@ -44,8 +50,17 @@ bool Engine::optimize_blocks_device(int cap_mul) {
         prev = bb;
         blk_nl[(size_t)bb + 1] += 1;
         nnz_nl[(size_t)bb] += h_rowptr[r + 1] - h_rowptr[r];
+        if (h_rowkind[(size_t)r] == KTN_ROW_QUAD) {
+            if (k > 0 && h_nlrows[k - 1] >= r) return false;           // (the launch list is in row order: so must the slots be)
+            blk_qrow[(size_t)bb + 1] += 1;
+            blk_qent[(size_t)bb + 1] += h_rowptr[r + 1] - h_rowptr[r];
+        }
     }
-    for (int bb = 0; bb < nb; ++bb) { blk_lin[(size_t)bb + 1] += blk_lin[(size_t)bb]; blk_nl[(size_t)bb + 1] += blk_nl[(size_t)bb]; }
+    for (int bb = 0; bb < nb; ++bb) {
+        blk_lin[(size_t)bb + 1] += blk_lin[(size_t)bb]; blk_nl[(size_t)bb + 1] += blk_nl[(size_t)bb];
+        blk_qrow[(size_t)bb + 1] += blk_qrow[(size_t)bb]; blk_qent[(size_t)bb + 1] += blk_qent[(size_t)bb];
+    }
+    if (blk_qrow[(size_t)nb] != n_quad_nl || blk_qent[(size_t)nb] != n_quad_ent_nl) return false;
     // arenas
     std::vector<EcpArena> ar((size_t)nb);
     int64_t row_tot = 0, nnz_tot = 0;
@@ -80,6 +95,17 @@ bool Engine::optimize_blocks_device(int cap_mul) {
     B.c = lp_c.p; B.l = lp_l.p; B.u = lp_u.p;
     B.P = nlp_view(); B.nl_rows = d_nlrows.p;
     B.jac = d_jac.p; B.has_tape = n_tape_nl > 0 ? 1 : 0;      // every row owns its entries of the Jacobian buffer
+    B.has_quad = n_quad_nl > 0 ? 1 : 0;
+    B.quad_group = (dev.ecp_quad_group == 4 || dev.ecp_quad_group == 8 || dev.ecp_quad_group == 16 || dev.ecp_quad_group == 32 ||
+                    dev.ecp_quad_group == 64) ? dev.ecp_quad_group : grp_quad;
+    B.Q = QuadDev{d_qcol.p, d_qval.p, d_qptr.p, d_qjidx.p, d_qvterm.p};
+    B.q_rows = d_qrows_nl.p; B.q_slots = d_qslots_nl.p; B.q_tbase = d_qtbase_nl.p;
+    B.q_ent = n_quad_nl != n_quad ? d_qent_nl.p : nullptr;
+    B.blk_qrow = nullptr; B.blk_qent = nullptr;
+    if (B.has_quad) {
+        d_blkqrow.upload(blk_qrow, stream); d_blkqent.upload(blk_qent, stream);
+        B.blk_qrow = d_blkqrow.p; B.blk_qent = d_blkqent.p;
+    }
     B.arena = d_ar.p;
     B.rptr = e_rptr.p; B.rcol = e_rcol.p; B.rval = e_rval.p; B.rsval = e_rsval.p; B.lo = e_lo.p; B.hi = e_hi.p; B.y = e_y.p; B.dr = e_dr.p;
     B.loh = e_loh.p; B.hih = e_hih.p;
@@ -118,11 +144,18 @@ bool Engine::optimize_blocks_device(int cap_mul) {
         std::fprintf(stderr, "[ecp blocks] pdhg per instance: min %.0f median %.0f p90 %.0f p99 %.0f max %.0f (instance %d, %g ecp iterations, %g rows)\n",
                      v.front().first, v[v.size() / 2].first, v[v.size() * 9 / 10].first, v[v.size() * 99 / 100].first, v.back().first, v.back().second,
                      res[(size_t)v.back().second * 8 + 1], res[(size_t)v.back().second * 8 + 6]);
+        for (int bb = 0; bb < nb; ++bb) {                       // what sends the batch to the host-driven loop
+            const double* o = res.data() + (size_t)bb * 8;
+            if ((int)o[0] != KTN_STATUS_OPTIMAL)
+                std::fprintf(stderr, "[ecp blocks] instance %d not optimal: status %d, %g ecp iterations, %g pdhg iterations, %g rows, max violation %g%s\n",
+                             bb, (int)o[0], o[1], o[4], o[6], o[5], o[7] != 0.0 ? ", arena overflow" : "");
+        }
     }
     stats["ecp_blocks_launches"] += 1.0;
     stats["ecp_blocks_pdhg_sum"] += pd;
     stats["ecp_blocks_rows"] = rows;
     stats["ecp_blocks_tape_rows"] = (double)n_tape_nl;
+    stats["ecp_blocks_quad_rows"] = (double)n_quad_nl;
     if (!ok) { stats["ecp_blocks_fallbacks"] += 1.0; return false; }
     status = KTN_STATUS_OPTIMAL; lp_status = KTN_STATUS_OPTIMAL;
     iter = (int64_t)it_max; numcuts = (int64_t)cuts; objval = obj + c0; allsat = true;

@@ -71,6 +71,7 @@ struct DevParams {
                                    //                      every tape row, 1 = every class of >= 2 rows
     int quad_group = 0;            // KTN_QUAD_GROUP       lanes per Jacobian entry of k_quad_jac (0 = by mean segment length)
     int esh_quad_group = 0;        // KTN_ESH_QUAD_GROUP   lanes per row of k_esh_quad (0 = those of k_quad_stats, by mean row length)
+    int ecp_quad_group = 0;        // KTN_ECP_QUAD_GROUP   lanes per Jacobian entry of the QUAD pass of k_ecp_blocks (0 = those of k_quad_jac)
     int tiled_wg = 2;              // KTN_TILED_WG         workgroups per CU of k_spmv_tiled
     int ecp_power = 20;            // KTN_ECP_POWER        power passes of the device-side batch loop
     int grp_rows = 0, grp_cols = 0;// KTN_GRP_ROWS / COLS  lanes per LP row / column (0 = by average length)
@@ -99,6 +100,7 @@ struct DevParams {
         sweep_rows = geti("KTN_SWEEP_ROWS", sweep_rows); blk_cfg = geti("KTN_BLK_CFG", blk_cfg); sweep_blocked = geti("KTN_SWEEP_BLOCKED", sweep_blocked);
         sweep_batched = geti("KTN_SWEEP_BATCHED", sweep_batched); tape_classed = geti("KTN_TAPE_CLASSED", tape_classed);
         quad_group = geti("KTN_QUAD_GROUP", quad_group); esh_quad_group = geti("KTN_ESH_QUAD_GROUP", esh_quad_group);
+        ecp_quad_group = geti("KTN_ECP_QUAD_GROUP", ecp_quad_group);
         tiled_wg = geti("KTN_TILED_WG", tiled_wg); ecp_power = geti("KTN_ECP_POWER", ecp_power);
         grp_rows = geti("KTN_GRP_ROWS", grp_rows); grp_cols = geti("KTN_GRP_COLS", grp_cols); tiled = geti("KTN_TILED", tiled);
         smax_reuse = getd("KTN_SMAX_REUSE", smax_reuse); power_passes = geti("KTN_POWER_PASSES", power_passes);
@@ -329,7 +331,7 @@ struct Engine {
     void build_blocks();
     bool optimize_blocks_device(int cap_mul);
     DBuf<EcpArena> d_ar;                          // arenas of the device-side loop
-    DBuf<int64_t> d_blklin, d_blknl;
+    DBuf<int64_t> d_blklin, d_blknl, d_blkqrow, d_blkqent;
     DBuf<int32_t> e_rptr, e_cptr, e_last, e_prev;
     DBuf<uint16_t> e_rcol, e_crow;
     DBuf<double> e_xbest, e_ax, e_rval, e_rsval, e_lo, e_hi, e_y, e_dr, e_loh, e_hih, e_cval, e_csval, e_dc, e_ch, e_lh, e_uh, e_res;     // batch_ecp.hpp: the whole ECP loop of every instance in its own workgroup

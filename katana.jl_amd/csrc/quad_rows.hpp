@@ -41,6 +41,11 @@ struct QuadList {
     int64_t n_rows, n_ent;
 };
 
+// What one Jacobian entry contributes, from its linear coefficient a, its segment sum s and x_e: the coefficient J_e = a + s
+// and the value term x_e (a + 1/2 s).  Defined once: k_quad_jac and the device-side batch loop (batch_ecp.hpp) both end here.
+struct QuadEntry { double jac, vterm; };
+__device__ __forceinline__ QuadEntry quad_entry(double a, double s, double xe) { return QuadEntry{a + s, xe * (a + 0.5 * s)}; }
+
 template <int G>
 __global__ __launch_bounds__(kBlock) void k_quad_jac(NlpDev P, QuadDev Q, QuadList L, const double* __restrict__ x, SweepOut O) {
     const int64_t gid = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / G;
@@ -72,8 +77,9 @@ __global__ __launch_bounds__(kBlock) void k_quad_jac(NlpDev P, QuadDev Q, QuadLi
         const int64_t e = Q.jidx[t];
         const double a = P.pp[e].x;
         const double xe = x[P.col[e]];
-        O.jac[e] = a + s;
-        Q.vterm[t] = xe * (a + 0.5 * s);
+        const QuadEntry qe = quad_entry(a, s, xe);
+        O.jac[e] = qe.jac;
+        Q.vterm[t] = qe.vterm;
     }
 }
 

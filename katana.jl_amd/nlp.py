@@ -319,10 +319,14 @@ def _linear_objective(d, k):
     if isinstance(d, CallbackNLP) or d.obj_kind == L.ROW_HOST:
         raise ValueError("problem %d: host-evaluated rows or objective (CallbackNLP) cannot be fused" % k)
     if not d.obj_linear:
-        raise ValueError("problem %d: nonlinear objective; a fused batch needs linear objectives" % k)
+        raise ValueError("problem %d: nonlinear objective; a fused batch needs linear or KTN_ROW_QUAD objectives" % k)
     if d.obj_kind == L.ROW_SEP:
         if len(d.obj_atom_kind) and np.any(d.obj_atom_kind != L.ATOM_LIN):
             raise ValueError("problem %d: objective declared linear has nonlinear atoms" % k)
+        return d.obj_col.astype(np.int64), d.obj_p0.copy(), d.obj_const
+    if d.obj_kind == L.ROW_QUAD:                                        # what every QuadNLP with obj_Q=None produces
+        if d.obj_quad_val is not None and len(d.obj_quad_val):
+            raise ValueError("problem %d: KTN_ROW_QUAD objective declared linear has a non-empty Q" % k)
         return d.obj_col.astype(np.int64), d.obj_p0.copy(), d.obj_const
     aff = tape_affine(d.obj_tape_op, d.obj_tape_arg)
     if aff is None:
@@ -332,53 +336,116 @@ def _linear_objective(d, k):
     return np.asarray(js, dtype=np.int64), np.asarray([co[j] for j in js], dtype=np.float64), c0 + d.obj_const
 
 
-def fuse_problems(problems):
-    """Block-diagonal union of independent problems (Problem tuples of NLPDescriptions, any mix of separable and tape rows):
-    rows instance after instance, columns shifted by each instance's column offset, tapes copied with their VAR arguments
-    shifted.  Every objective must be linear; it enters the fused :Min objective as LIN atoms (negated for a :Max instance).
+def quad_objective_bound(d, l_var, u_var, k=0):
+    """R with |a'x + 1/2 x'Qx| <= R on the box, for the KTN_ROW_QUAD objective of description d:
+    R = sum_j |a_j| m_j + 1/2 sum_jk |q_jk| m_j m_k with m_j = max(|l_j|, |u_j|) over the objective's columns (interval
+    arithmetic term by term).  ValueError when a column the objective touches has an infinite bound."""
+    cols = d.obj_col.astype(np.int64)
+    m = np.maximum(np.abs(np.asarray(l_var, dtype=np.float64)), np.abs(np.asarray(u_var, dtype=np.float64)))
+    bad = cols[~np.isfinite(m[cols])]
+    if len(bad):
+        raise ValueError("problem %d: column %d of the quadratic objective has an infinite bound; the per-instance epigraph "
+                         "variable of a fused batch needs a finite interval" % (k, int(bad[0])))
+    seg = np.repeat(cols, np.diff(d.obj_quad_ptr))
+    return float(np.sum(np.abs(d.obj_p0) * m[cols]) + 0.5 * np.sum(np.abs(d.obj_quad_val) * m[seg] * m[d.obj_quad_col]))
+
+
+def fuse_problems(problems, allow_quad=False):
+    """Block-diagonal union of independent problems (Problem tuples of NLPDescriptions, any mix of separable, tape and
+    KTN_ROW_QUAD rows): rows instance after instance, columns shifted by each instance's column offset, tapes copied with their
+    VAR arguments shifted, Q segments concatenated with their pointers shifted by the running Q-entry count (a description
+    without quad arrays contributes empty segments; the fused description carries quad arrays only if some instance has QUAD
+    rows).  A linear objective (separable LIN atoms, an affine tape, or a KTN_ROW_QUAD objective declared linear) enters the
+    fused :Min objective as LIN atoms, negated for a :Max instance.  A QUADRATIC objective (KTN_ROW_QUAD, not linear) gets its
+    own epigraph at fusion -- the engine refuses a shared epigraph variable under ktn_set_blocks --: instance k gains one last
+    variable t_k in [-R, R] (quad_objective_bound) and one last QUAD row  a'x + 1/2 x'Qx - t_k <= 0  (a and Q negated for
+    :Max), and its objective becomes t_k + const.  Nonlinear separable or tape objectives are refused: no closed-form bound
+    for t exists there.
+    KTN_ROW_QUAD rows and objectives are taken with allow_quad=True only (FusedBatch passes it): a caller that hands the fused
+    problem to an engine without QUAD rows in its device-side batch loop relied on the ValueError, and the default keeps it.
     Returns (Problem, col_offsets[len + 1], objinfo) with objinfo[k] = (cols, coefs, constant) of instance k's objective in
-    ITS own sense and local columns: objval_k = coefs . x_k[cols] + constant."""
+    ITS own sense and local columns: objval_k = coefs . x_k[cols] + constant (an epigraph instance: ([n_k], [+-1], const);
+    its own variables are the first n_k of its column range)."""
     problems = list(problems)
     if not problems:
         raise ValueError("fuse_problems: no problems")
-    ds = []
+    i64, f64 = np.int64, np.float64
+    flat = lambda p, attr: np.asarray(getattr(p, attr), dtype=f64).reshape(-1)
+    ds, epi = [], []
     for k, p in enumerate(problems):
         d = p.d
         if isinstance(d, CallbackNLP) or np.any(d.row_kind == L.ROW_HOST) or d.obj_kind == L.ROW_HOST:
             raise ValueError("problem %d: host-evaluated rows or objective (CallbackNLP) cannot be fused" % k)
-        if np.any(d.row_kind == L.ROW_QUAD) or d.obj_kind == L.ROW_QUAD:
-            raise ValueError("problem %d: KTN_ROW_QUAD rows or objective (QuadNLP) cannot be fused: the device-side batch loop "
-                             "does not take them" % k)
+        if not allow_quad and (np.any(d.row_kind == L.ROW_QUAD) or d.obj_kind == L.ROW_QUAD):
+            raise ValueError("problem %d: KTN_ROW_QUAD rows or objective (QuadNLP) are fused with allow_quad=True only "
+                             "(FusedBatch passes it)" % k)
         if p.sense not in ("Min", "Max"):
             raise ValueError("problem %d: sense must be 'Min' or 'Max'" % k)
         if d.num_var != int(p.num_var) or d.num_constr != int(p.num_constr):
             raise ValueError("problem %d: num_var / num_constr do not match the description" % k)
         ds.append(d)
-    offs = np.concatenate([[0], np.cumsum([d.num_var for d in ds])]).astype(np.int64)
-    eoff = np.concatenate([[0], np.cumsum([len(d.col) for d in ds])]).astype(np.int64)
-    toff = np.concatenate([[0], np.cumsum([len(d.tape_op) for d in ds])]).astype(np.int64)
-    rowptr = np.concatenate([[0]] + [d.rowptr[1:] + e for d, e in zip(ds, eoff)]).astype(np.int64)
-    tape_ptr = np.concatenate([[0]] + [d.tape_ptr[1:] + t for d, t in zip(ds, toff)]).astype(np.int64)
-    col = np.concatenate([d.col + np.int32(o) for d, o in zip(ds, offs)]).astype(np.int32)
-    targs = []
-    for d, o in zip(ds, offs):
+        epi.append(d.obj_kind == L.ROW_QUAD and not d.obj_linear)
+    has_quad = any(epi) or any(np.any(d.row_kind == L.ROW_QUAD) for d in ds)
+    # per instance: extra entries / Q entries / rows / columns of its epigraph row
+    xe = [len(d.obj_col) + 1 if e else 0 for d, e in zip(ds, epi)]
+    own_q = [0 if d.quad_ptr is None else int(d.quad_ptr[-1] - d.quad_ptr[0]) for d in ds]
+    nq = [q + (len(d.obj_quad_val) if e else 0) for d, q, e in zip(ds, own_q, epi)]
+    offs = np.concatenate([[0], np.cumsum([d.num_var + int(e) for d, e in zip(ds, epi)])]).astype(i64)
+    eoff = np.concatenate([[0], np.cumsum([len(d.col) + x for d, x in zip(ds, xe)])]).astype(i64)
+    toff = np.concatenate([[0], np.cumsum([len(d.tape_op) for d in ds])]).astype(i64)
+    qoff = np.concatenate([[0], np.cumsum(nq)]).astype(i64)
+    rowptr, tape_ptr, col, targs = [np.zeros(1, dtype=i64)], [np.zeros(1, dtype=i64)], [], []
+    rkind, rlin, rconst, akind, p0, p1 = [], [], [], [], [], []
+    qptr, qcol, qval = [np.zeros(1, dtype=i64)], [], []
+    lv, uv, lc, uc = [], [], [], []
+    info, ocol, op0, oconst = [], [], [], 0.0
+    for k, (p, d, o) in enumerate(zip(problems, ds, offs)):
+        sgn = -1.0 if p.sense == "Max" else 1.0
+        rowptr.append(d.rowptr[1:] + eoff[k]); tape_ptr.append(d.tape_ptr[1:] + toff[k])
+        col.append(d.col + np.int32(o))
         a = d.tape_arg.copy()
         isvar = d.tape_op == L.OP_VAR
         a[isvar] = a[isvar] + float(o)                                  # every other argument bit for bit
         targs.append(a)
-    info, ocol, op0, oconst = [], [], [], 0.0
-    for k, (p, d, o) in enumerate(zip(problems, ds, offs)):
-        cols, coefs, c0 = _linear_objective(d, k)
-        info.append((cols, coefs, float(c0)))
-        sgn = -1.0 if p.sense == "Max" else 1.0
-        ocol.append(cols + o); op0.append(sgn * coefs); oconst += sgn * c0
+        rkind.append(d.row_kind); rlin.append(d.row_linear); rconst.append(d.rconst)
+        akind.append(d.atom_kind); p0.append(d.p0); p1.append(d.p1)
+        lv.append(flat(p, "l_var")); uv.append(flat(p, "u_var")); lc.append(flat(p, "l_constr")); uc.append(flat(p, "u_constr"))
+        if has_quad:
+            if d.quad_ptr is None:
+                qptr.append(np.full(len(d.col), qoff[k], dtype=i64))
+            else:
+                qptr.append(d.quad_ptr[1:] - d.quad_ptr[0] + qoff[k])
+                seg = slice(int(d.quad_ptr[0]), int(d.quad_ptr[-1]))
+                qcol.append(d.quad_col[seg] + np.int32(o)); qval.append(d.quad_val[seg])
+        if not epi[k]:
+            cols, coefs, c0 = _linear_objective(d, k)
+            info.append((cols, coefs, float(c0)))
+            ocol.append(cols + o); op0.append(sgn * coefs); oconst += sgn * c0
+            continue
+        # the instance's own epigraph: variable t (local index n_k) and the QUAD row  sgn (a'x + 1/2 x'Qx) - t <= 0
+        n_k, nob = d.num_var, len(d.obj_col)
+        R = quad_objective_bound(d, lv[-1], uv[-1], k)
+        qb = qoff[k] + own_q[k]                                         # the row's first Q entry
+        rowptr.append(np.asarray([eoff[k] + len(d.col) + nob + 1], dtype=i64)); tape_ptr.append(np.asarray([toff[k + 1]], dtype=i64))
+        col.append(np.concatenate([d.obj_col.astype(i64) + o, [o + n_k]]).astype(np.int32))
+        rkind.append(np.asarray([L.ROW_QUAD], dtype=np.uint8)); rlin.append(np.zeros(1, dtype=np.uint8)); rconst.append(np.zeros(1))
+        akind.append(np.zeros(nob + 1, dtype=np.uint8)); p0.append(np.concatenate([sgn * d.obj_p0, [-1.0]])); p1.append(np.zeros(nob + 1))
+        seg = d.obj_quad_ptr[1:] - d.obj_quad_ptr[0] + qb
+        qptr.append(np.concatenate([seg, seg[-1:] if nob else [qb]]).astype(i64))      # t: the empty segment
+        qcol.append(d.obj_quad_col + np.int32(o)); qval.append(sgn * d.obj_quad_val)
+        lv.append(np.asarray([-R])); uv.append(np.asarray([R])); lc.append(np.asarray([-np.inf])); uc.append(np.zeros(1))
+        info.append((np.asarray([n_k], dtype=i64), np.asarray([sgn]), float(d.obj_const)))
+        ocol.append(np.asarray([o + n_k], dtype=i64)); op0.append(np.ones(1)); oconst += sgn * d.obj_const
     cat = np.concatenate
+    nobj = int(sum(len(c) for c in ocol))
+    quad = {}
+    if has_quad:
+        quad = dict(quad_ptr=cat(qptr), quad_col=cat(qcol + [np.zeros(0, dtype=np.int32)]).astype(np.int32),
+                    quad_val=cat(qval + [np.zeros(0)]).astype(f64))
     fused = NLPDescription(
-        int(offs[-1]), rowptr, col, cat([d.row_kind for d in ds]), cat([d.row_linear for d in ds]), cat([d.rconst for d in ds]),
-        cat([d.atom_kind for d in ds]), cat([d.p0 for d in ds]), cat([d.p1 for d in ds]),
-        tape_ptr, cat([d.tape_op for d in ds]), cat(targs),
-        obj_linear=True, obj_kind=L.ROW_SEP, obj_col=cat(ocol).astype(np.int32), obj_atom_kind=np.zeros(int(sum(len(c) for c in ocol))),
-        obj_p0=cat(op0), obj_p1=np.zeros(int(sum(len(c) for c in ocol))), obj_const=oconst)
-    f64 = lambda attr: cat([np.asarray(getattr(p, attr), dtype=np.float64).reshape(-1) for p in problems])
-    big = Problem(fused.num_var, fused.num_constr, f64("l_var"), f64("u_var"), f64("l_constr"), f64("u_constr"), "Min", fused)
+        int(offs[-1]), cat(rowptr).astype(i64), cat(col).astype(np.int32), cat(rkind), cat(rlin), cat(rconst),
+        cat(akind), cat(p0), cat(p1), cat(tape_ptr).astype(i64), cat([d.tape_op for d in ds]), cat(targs),
+        obj_linear=True, obj_kind=L.ROW_SEP, obj_col=cat(ocol).astype(np.int32), obj_atom_kind=np.zeros(nobj),
+        obj_p0=cat(op0), obj_p1=np.zeros(nobj), obj_const=oconst, **quad)
+    big = Problem(fused.num_var, fused.num_constr, cat(lv), cat(uv), cat(lc), cat(uc), "Min", fused)
     return big, offs, info
