@@ -546,6 +546,9 @@ static __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B) {
         __syncthreads();
 
         // ============================================================ separator sweep over the instance's NL rows ======
+        // (The verdict is row_sat / row_violation of kernels.hpp at each of the three places, not one function of this file: as a
+        //  function -- by reference, by value, bounds passed or read inside -- it moved a thousand of this kernel's 14 100
+        //  instructions to other registers and spill slots; written out, the kernel's code is unchanged.)
         // precompute! + isconstrsat (src/separators.jl:111-120): 16 lanes per separable row, one lane per tape row, G lanes per
         // Jacobian entry and then 16 per row for QUAD rows; flags and row lengths into icnt
         double mv[1] = {0.0};
@@ -571,10 +574,10 @@ static __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B) {
                 if (lane == 0) {
                     g += B.P.rconst[gr];
                     const double lb = B.P.lb[gr], ub = B.P.ub[gr];
-                    const bool sat = (g >= lb - f_eff) && (g <= ub + f_eff);           // NaN -> violated
+                    const bool sat = row_sat(g, lb, ub, f_eff);
                     icnt[i] = sat ? 0 : (int)(end - beg);
                     yts[i] = g;                                                         // keep g for the emit pass (m_nl <= mmax)
-                    if (!sat) { double d = fmax(g - ub, lb - g); if (!(d == d)) d = __builtin_inf(); mv[0] = fmax(mv[0], d); }
+                    if (!sat) mv[0] = fmax(mv[0], row_violation(g, lb, ub));
                 }
             }
             // tape rows: the interpreter of k_tape_eval with x from LDS; node values and adjoints in the rows' own slices of
@@ -585,10 +588,10 @@ static __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B) {
                     if (B.P.row_kind[gr] != KTN_ROW_TAPE) continue;
                     const double g = ecp_tape_row(B.P, gr, xs, (int)c0, B.jac);
                     const double lb = B.P.lb[gr], ub = B.P.ub[gr];
-                    const bool sat = (g >= lb - f_eff) && (g <= ub + f_eff);           // NaN -> violated
+                    const bool sat = row_sat(g, lb, ub, f_eff);
                     icnt[i] = sat ? 0 : (int)(B.P.rowptr[gr + 1] - B.P.rowptr[gr]);
                     yts[i] = g;
-                    if (!sat) { double d = fmax(g - ub, lb - g); if (!(d == d)) d = __builtin_inf(); mv[0] = fmax(mv[0], d); }
+                    if (!sat) mv[0] = fmax(mv[0], row_violation(g, lb, ub));
                 }
             }
             // QUAD rows: the two passes of quad_rows.hpp inside the workgroup.  Entry-parallel first (a 1 000-entry row with a
@@ -614,10 +617,10 @@ static __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B) {
                     if (lane == 0) {
                         g += B.P.rconst[gr];
                         const double lb = B.P.lb[gr], ub = B.P.ub[gr];
-                        const bool sat = (g >= lb - f_eff) && (g <= ub + f_eff);       // NaN -> violated
+                        const bool sat = row_sat(g, lb, ub, f_eff);
                         icnt[i] = sat ? 0 : len;
                         yts[i] = g;
-                        if (!sat) { double d = fmax(g - ub, lb - g); if (!(d == d)) d = __builtin_inf(); mv[0] = fmax(mv[0], d); }
+                        if (!sat) mv[0] = fmax(mv[0], row_violation(g, lb, ub));
                     }
                 }
             }
@@ -701,7 +704,7 @@ static __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B) {
                 if (B.P.pad_zero[gr]) mx = nanmax(mx, 0.0);
                 for (int64_t e = beg + lane; e < end; e += 16) {                          // round_coefs (signed max)
                     const double der = rval[dst + (int)(e - beg)];
-                    if (der + B.cut_coef_rng < mx) rval[dst + (int)(e - beg)] = 0.0;
+                    if (round_coef(der, mx, B.cut_coef_rng)) rval[dst + (int)(e - beg)] = 0.0;
                 }
                 if (lane == 0) {
                     const double bconst = yts[i] - dot;

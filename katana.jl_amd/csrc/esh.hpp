@@ -78,8 +78,8 @@ __global__ __launch_bounds__(kBlock) void k_esh_sep(NlpDev P, const int32_t* __r
     for (int it = 0; it < A.iters; ++it) {
         if (__ballot(active) == 0ull) break;          // uniform trip count per wavefront; finished groups sit predicated off
         const double lam = S.lam;
-        double acc_g = 0.0, acc_d = 0.0, acc_dot = 0.0, mx = -__builtin_inf();
-        int nf = 0;
+        RowAcc acc;
+        double acc_d = 0.0;                            // the directional derivative sum der_c (x*_c - x_int_c), beside the row's statistics
         for (int64_t e = beg + lane; active && e < end; e += G) {
             const int ck = P.colk[e];
             const double2 q = P.pp[e];
@@ -88,22 +88,16 @@ __global__ __launch_bounds__(kBlock) void k_esh_sep(NlpDev P, const int32_t* __r
             const double xv = esh_point(xs, x0, lam);
             double val, der;
             atom_eval((unsigned)ck >> kKindShift, q.x, q.y, xv, val, der);
-            acc_g += val;
+            acc.add(val, der, xv);
             acc_d += der * (xs - x0);
-            acc_dot += xv * der;
-            mx = nanmax(mx, der);
-            nf |= !isfinite(der);
         }
-        acc_g = group_sum<G>(acc_g);
+        acc.template reduce<G>();
         acc_d = group_sum<G>(acc_d);
-        acc_dot = group_sum<G>(acc_dot);
-        mx = group_nanmax<G>(mx);
-        nf = group_or<G>(nf);
         if (active) {
-            const double g = acc_g + rc;
+            const double g = acc.g + rc;
             const double phi = sg * (g - bound), dphi = sg * acc_d;
             ++passes;
-            if (esh_step(S, phi, dphi, !nf && isfinite(phi), A.tol)) { gb = g; dotb = acc_dot; mxb = mx; }
+            if (esh_step(S, phi, dphi, !acc.nf && isfinite(phi), A.tol)) { gb = g; dotb = acc.dot; mxb = acc.mx; }
             if (S.done) active = false;
         }
     }
@@ -120,9 +114,7 @@ __global__ __launch_bounds__(kBlock) void k_esh_sep(NlpDev P, const int32_t* __r
     if (lane == 0 && sep) {
         if (S.have) {
             A.lam[r] = S.best;
-            O.bconst[r] = gb - dotb;
-            O.maxc[r] = P.pad_zero[r] ? nanmax(mxb, 0.0) : mxb;
-            O.nonfin[r] = 0;
+            row_store_cut(O, r, gb - dotb, mxb, 0, P.pad_zero[r]);
             atomicAdd(&A.cnt[0], 1ull);
         } else {
             A.lam[r] = 1.0;
@@ -144,9 +136,9 @@ static __global__ __launch_bounds__(1024) void k_esh_long(NlpDev P, const int32_
     const double bound = sg > 0 ? P.ub[r] : P.lb[r];
     const int wv = threadIdx.x >> 6;
     // one pass at lambda: every thread ends with the same totals (partials combined in wavefront order)
-    auto pass = [&](double lam, bool write, double& g, double& d, double& dot, double& mx, int& nf) {
-        double ag = 0.0, ad = 0.0, adot = 0.0, am = -__builtin_inf();
-        int an = 0;
+    auto pass = [&](double lam, bool write, RowAcc& t, double& d) {
+        RowAcc a;
+        double ad = 0.0;
         for (int64_t e = beg + threadIdx.x; e < end; e += 1024) {
             const int ck = P.colk[e];
             const double2 q = P.pp[e];
@@ -155,36 +147,34 @@ static __global__ __launch_bounds__(1024) void k_esh_long(NlpDev P, const int32_
             const double xv = esh_point(xs, x0, lam);
             double val, der;
             atom_eval((unsigned)ck >> kKindShift, q.x, q.y, xv, val, der);
-            ag += val; ad += der * (xs - x0); adot += xv * der; am = nanmax(am, der); an |= !isfinite(der);
+            a.add(val, der, xv); ad += der * (xs - x0);
             if (write) O.jac[e] = der;
         }
-        ag = group_sum<64>(ag); ad = group_sum<64>(ad); adot = group_sum<64>(adot); am = group_nanmax<64>(am); an = group_or<64>(an);
-        if ((threadIdx.x & 63) == 0) { sh[wv][0] = ag; sh[wv][1] = ad; sh[wv][2] = adot; sh[wv][3] = am; shn[wv] = an; }
+        a.reduce<64>(); ad = group_sum<64>(ad);
+        if ((threadIdx.x & 63) == 0) { sh[wv][0] = a.g; sh[wv][1] = ad; sh[wv][2] = a.dot; sh[wv][3] = a.mx; shn[wv] = a.nf; }
         __syncthreads();
-        g = sh[0][0]; d = sh[0][1]; dot = sh[0][2]; mx = sh[0][3]; nf = shn[0];
-        for (int k = 1; k < 16; ++k) { g += sh[k][0]; d += sh[k][1]; dot += sh[k][2]; mx = nanmax(mx, sh[k][3]); nf |= shn[k]; }
-        g += P.rconst[r];
+        t = RowAcc{sh[0][0], sh[0][2], sh[0][3], shn[0]}; d = sh[0][1];
+        for (int k = 1; k < 16; ++k) { t.merge(RowAcc{sh[k][0], sh[k][2], sh[k][3], shn[k]}); d += sh[k][1]; }
+        t.g += P.rconst[r];
         __syncthreads();                             // (the cells are reused by the next pass)
     };
     EshState S;
     esh_init(S);
     unsigned long long passes = 0;
     for (int it = 0; it < A.iters && !S.done; ++it) {
-        double g, d, dot, mx;
-        int nf;
-        pass(S.lam, false, g, d, dot, mx, nf);
+        RowAcc t;
+        double d;
+        pass(S.lam, false, t, d);
         ++passes;
-        esh_step(S, sg * (g - bound), sg * d, !nf && isfinite(g), A.tol);
+        esh_step(S, sg * (t.g - bound), sg * d, !t.nf && isfinite(t.g), A.tol);
     }
     if (S.have) {
-        double g, d, dot, mx;
-        int nf;
-        pass(S.best, true, g, d, dot, mx, nf);
+        RowAcc t;
+        double d;
+        pass(S.best, true, t, d);
         if (threadIdx.x == 0) {
             A.lam[r] = S.best;
-            O.bconst[r] = g - dot;
-            O.maxc[r] = P.pad_zero[r] ? nanmax(mx, 0.0) : mx;
-            O.nonfin[r] = nf;
+            row_store_cut(O, r, t.g - t.dot, t.mx, t.nf, P.pad_zero[r]);
             atomicAdd(&A.cnt[0], 1ull);
         }
     }
@@ -226,23 +216,14 @@ static __global__ __launch_bounds__(kBlock) void k_esh_tape(NlpDev P, const int3
     }
     const double lb = S.best;
     const double g = tape_row_eval(P, r, [&](int32_t c) { return esh_point(A.x[c], A.xi[c], lb); }, O.jac);
-    double b = g, mx = -__builtin_inf();
-    int nf = 0;
-    for (int64_t e = beg; e < end; ++e) {
-        const double der = O.jac[e];
-        b += -esh_point(A.x[P.col[e]], A.xi[P.col[e]], lb) * der;
-        mx = nanmax(mx, der);
-        nf |= !isfinite(der);
-    }
-    if (P.pad_zero[r]) mx = nanmax(mx, 0.0);
+    const RowJacStats st = row_jac_stats(g, beg, end, [&](int64_t e) { return O.jac[e]; },
+                                         [&](int64_t e) { return esh_point(A.x[P.col[e]], A.xi[P.col[e]], lb); });
     A.lam[r] = lb;
-    O.bconst[r] = b;
-    O.maxc[r] = mx;
-    O.nonfin[r] = nf;
+    row_store_cut(O, r, st.bconst, st.mx, st.nf, P.pad_zero[r]);
     atomicAdd(&A.cnt[0], 1ull);
 }
 
-// gencut + round_coefs + row append (k_emit) with the separable derivatives at x_b = x_int + lam[r] (x* - x_int); jint (the Jacobian
+// emit_rows (as k_emit) with the separable derivatives at x_b = x_int + lam[r] (x* - x_int); jint (the Jacobian
 // at x_int by Jacobian entry) is NULL unless QUAD rows take part
 template <int G>
 __global__ __launch_bounds__(kBlock) void k_emit_esh(NlpDev P, const int32_t* __restrict__ nl_rows,
@@ -251,26 +232,14 @@ __global__ __launch_bounds__(kBlock) void k_emit_esh(NlpDev P, const int32_t* __
                                                      const double* __restrict__ lam, const double* __restrict__ jac,
                                                      const double* __restrict__ jint, const double* __restrict__ maxc, double cut_coef_rng, int round_coefs,
                                                      int64_t base_row, LpRows L) {
-    const int64_t v = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / G;
-    const int lane = threadIdx.x & (G - 1);
-    if (v >= n_viol) return;
-    const int32_t r = nl_rows[viol_slots[v]];
-    const int64_t beg = P.rowptr[r], end = P.rowptr[r + 1];
-    const int64_t dst = L.rowptr[base_row + v];
-    const bool sep = P.row_kind[r] == KTN_ROW_SEP;
-    const bool quad = jint != nullptr && P.row_kind[r] == KTN_ROW_QUAD && lam[r] < 1.0;
-    const double lr = (sep || quad) ? lam[r] : 1.0;
-    const double mx = maxc[r];
-    for (int64_t e = beg + lane; e < end; e += G) {
-        const int c = P.col[e];
-        double der;
-        if (sep) { double val; const double2 q = P.pp[e]; atom_eval((unsigned)P.colk[e] >> kKindShift, q.x, q.y, esh_point(x[c], xi[c], lr), val, der); }
-        else if (quad) der = esh_quad_coef(lr, jac[e], jint[e]);
-        else der = jac[e];
-        if (round_coefs && (der + cut_coef_rng < mx)) der = 0.0;   // model.jl:202-206 (signed max)
-        L.col[dst + (e - beg)] = c;
-        L.val[dst + (e - beg)] = der;
-    }
+    emit_rows<G>(P, nl_rows, viol_slots, n_viol, maxc, cut_coef_rng, round_coefs, base_row, L, [&](int32_t r) {
+        const bool sep = P.row_kind[r] == KTN_ROW_SEP;
+        const bool quad = jint != nullptr && P.row_kind[r] == KTN_ROW_QUAD && lam[r] < 1.0;
+        const double lr = (sep || quad) ? lam[r] : 1.0;
+        return [&P, x, xi, jac, jint, sep, quad, lr](int64_t e, int c) {
+            return sep ? sep_entry_der(P, e, esh_point(x[c], xi[c], lr)) : quad ? esh_quad_coef(lr, jac[e], jint[e]) : jac[e];
+        };
+    });
 }
 
 }  // namespace ktn

@@ -11,6 +11,8 @@
 //                     == precompute! + isconstrsat + gencut(linear_oa_cut) + round_coefs
 //                        + _addcut   (src/separators.jl:111-120, src/algorithms.jl:3-18,
 //                                     src/model.jl:68-79,200-207,272-283)
+//                     (what they share is the section "the tail of a nonlinear row": RowAcc, row_jac_stats, row_store,
+//                      row_verdict, round_coef; emit_rows next to k_emit)
 //   LP (replaces GLPK) k_pdhg_x / k_pdhg_y / k_chk_* / scaling kernels
 #pragma once
 #include <hip/hip_runtime.h>
@@ -176,6 +178,80 @@ struct SweepOut {
     int32_t* any_nonfin;  // [1] some violated row has a non-finite coefficient
 };
 
+// ------------------------------------------------ the tail of a nonlinear row ----
+// What every way of evaluating an NL row ends in, written once: the row statistics (RowAcc, or row_jac_stats over a
+// materialised Jacobian row), their stores (row_store), the isconstrsat verdict (row_verdict) and the coefficient rounding of
+// gencut (round_coef; the emission body emit_rows sits with k_emit, behind LpRows).  The callers keep their loop shapes and
+// the way they publish the returned violation; the arithmetic, its order and the NaN rules are these.
+
+// The running statistics of one row: g = sum of the entry values, dot = sum x_c J_c, mx = signed maximum coefficient
+// (NaN-poisoned, model.jl:201), nf = some coefficient non-finite (model.jl:69).  The order of a lane's add()s and the xor
+// butterfly of reduce() fix every sum's bits.
+struct RowAcc {
+    double g = 0.0, dot = 0.0, mx = -__builtin_inf();
+    int nf = 0;
+    __device__ __forceinline__ void add(double val, double der, double xv) {
+        g += val; dot += xv * der; mx = nanmax(mx, der); nf |= !isfinite(der);
+    }
+    // another partial of the same row: a wavefront's cell, a (row, block) partial, one entry of a run
+    __device__ __forceinline__ void merge(const RowAcc& o) { g += o.g; dot += o.dot; mx = nanmax(mx, o.mx); nf |= o.nf; }
+    template <int G>
+    __device__ __forceinline__ void reduce() {
+        g = group_sum<G>(g); dot = group_sum<G>(dot); mx = group_nanmax<G>(mx); nf = group_or<G>(nf);
+    }
+};
+
+// The same statistics from a MATERIALISED Jacobian row, entries [k0, k1), by one thread in storage order (== the reference's
+// left-to-right order, algorithms.jl:8,15): der(k) is entry k's coefficient, xat(k) the point's coordinate of its column.
+// Not a RowAcc: the cut constant starts from g and takes -x_k J_k entry by entry, g - x_0 J_0 - x_1 J_1 ..., which rounds
+// differently from RowAcc's g - (x_0 J_0 + x_1 J_1 + ...); tape rows are tested against the reference's order.
+struct RowJacStats { double bconst, mx; int nf; };
+template <class N, class DER, class XAT>
+__device__ __forceinline__ RowJacStats row_jac_stats(double g, N k0, N k1, DER&& der, XAT&& xat) {
+    RowJacStats s{g, -__builtin_inf(), 0};
+    for (N k = k0; k < k1; ++k) {
+        const double d = der(k);
+        s.bconst += -xat(k) * d;
+        s.mx = nanmax(s.mx, d);
+        s.nf |= !isfinite(d);
+    }
+    return s;
+}
+
+// The stores of a cut's statistics; pad_zero: the row has implicit zero coefficients, which take part in the maximum.
+__device__ __forceinline__ void row_store_cut(const SweepOut& O, int32_t r, double bconst, double mx, int nf, bool pad_zero) {
+    O.bconst[r] = bconst;
+    O.maxc[r] = pad_zero ? nanmax(mx, 0.0) : mx;
+    O.nonfin[r] = nf;
+}
+__device__ __forceinline__ void row_store(const SweepOut& O, int32_t r, double g, double bconst, double mx, int nf, bool pad_zero) {
+    O.g[r] = g;
+    row_store_cut(O, r, bconst, mx, nf, pad_zero);
+}
+
+// isconstrsat (separators.jl:120): a NaN value fails both comparisons, so the row counts as violated ...
+__device__ __forceinline__ bool row_sat(double g, double lb, double ub, double f_tol) { return (g >= lb - f_tol) && (g <= ub + f_tol); }
+// ... and its violation depth max(g - ub, lb - g) as +inf
+__device__ __forceinline__ double row_violation(double g, double lb, double ub) {
+    const double v = fmax(g - ub, lb - g);
+    return !(v == v) ? __builtin_inf() : v;
+}
+// The verdict of the row in NL slot `slot`: flag and cnt (len: the row's structure length), any_nonfin for a violated row with
+// a non-finite coefficient (the plain load filters the atomics, as in atomic_max_nonneg).  Returns the violation, 0.0 for a
+// satisfied row; the caller publishes it with block_max_nonneg or atomic_max_nonneg.
+__device__ __forceinline__ double row_verdict(const SweepOut& O, int64_t slot, int64_t len, double g, double lb, double ub,
+                                              double f_tol, int nf) {
+    const bool sat = row_sat(g, lb, ub, f_tol);
+    O.flag[slot] = sat ? 0 : 1;
+    O.cnt[slot] = sat ? 0 : len;
+    if (sat) return 0.0;
+    if (nf) { if (*O.any_nonfin == 0) atomicOr(O.any_nonfin, 1); }
+    return row_violation(g, lb, ub);
+}
+
+// round_coefs (model.jl:202-206): true for a coefficient more than rng below the row's signed maximum -- it becomes zero
+__device__ __forceinline__ bool round_coef(double der, double mx, double rng) { return der + rng < mx; }
+
 // precompute! + isconstrsat for separable rows: G lanes per row.
 template <int G>
 __global__ __launch_bounds__(kBlock) void k_sep_eval(NlpDev P, const int32_t* __restrict__ nl_rows, int64_t m_nl,
@@ -187,8 +263,7 @@ __global__ __launch_bounds__(kBlock) void k_sep_eval(NlpDev P, const int32_t* __
     const int32_t r = gid < m_nl ? nl_rows[gid] : 0;
     const bool live = gid < m_nl && P.row_kind[r] == KTN_ROW_SEP;
     const int64_t beg = live ? P.rowptr[r] : 0, end = live ? P.rowptr[r + 1] : 0;
-    double acc_g = 0.0, acc_dot = 0.0, mx = -__builtin_inf();
-    int nf = 0;
+    RowAcc acc;
     // kU entries per lane and trip: all (colk, pp) loads and all x gathers of a trip are issued
     // before any arithmetic, so each wavefront keeps kU * G * 20 B (+ gathers) in flight
     constexpr int kU = 2;
@@ -210,37 +285,17 @@ __global__ __launch_bounds__(kBlock) void k_sep_eval(NlpDev P, const int32_t* __
             if (ck[u] >= 0) {
                 double val, der;
                 atom_eval((unsigned)ck[u] >> kKindShift, q[u].x, q[u].y, xv[u], val, der);
-                acc_g += val;
-                acc_dot += xv[u] * der;
-                mx = nanmax(mx, der);
-                nf |= !isfinite(der);
+                acc.add(val, der, xv[u]);
                 if (materialize) O.jac[e + (int64_t)u * G] = der;
             }
         }
     }
-    acc_g = group_sum<G>(acc_g);
-    acc_dot = group_sum<G>(acc_dot);
-    mx = group_nanmax<G>(mx);
-    nf = group_or<G>(nf);
+    acc.reduce<G>();
     double viol = 0.0;
     if (lane == 0 && live) {
-        const double g = acc_g + P.rconst[r];
-        if (P.pad_zero[r]) mx = nanmax(mx, 0.0);
-        O.g[r] = g;
-        O.bconst[r] = g - acc_dot;
-        O.maxc[r] = mx;
-        O.nonfin[r] = nf;
-        if (only_flagged_nl) {
-            const double lb = P.lb[r], ub = P.ub[r];
-            const bool sat = (g >= lb - f_tol) && (g <= ub + f_tol);   // separators.jl:120 (NaN -> violated)
-            O.flag[gid] = sat ? 0 : 1;
-            O.cnt[gid] = sat ? 0 : (end - beg);
-            if (!sat) {
-                viol = fmax(g - ub, lb - g);
-                if (viol != viol) viol = __builtin_inf();
-                if (nf) { if (*O.any_nonfin == 0) atomicOr(O.any_nonfin, 1); };
-            }
-        }
+        const double g = acc.g + P.rconst[r];
+        row_store(O, r, g, g - acc.dot, acc.mx, acc.nf, P.pad_zero[r]);
+        if (only_flagged_nl) viol = row_verdict(O, gid, end - beg, g, P.lb[r], P.ub[r], f_tol, acc.nf);
     }
     if (only_flagged_nl) block_max_nonneg(O.maxviol, viol);
 }
@@ -252,7 +307,11 @@ __global__ __launch_bounds__(kBlock) void k_sep_eval(NlpDev P, const int32_t* __
 // 4 % of the HBM peak; here the same four round trips serve R times as many entries.  Same arithmetic and the same
 // summation order per row as k_sep_eval (lane-strided partial sums, xor-butterfly), hence the same bits.
 // MAT = true is the literal precompute! (src/separators.jl:111-116) in the same form: the Jacobian values are stored, the
-// isconstrsat tail is left out (round 4: ktn_sep_precompute on 1e6 rows of 32 entries ran one row per group, 1.86 ms).
+// verdict is left out (round 4: ktn_sep_precompute on 1e6 rows of 32 entries ran one row per group, 1.86 ms).
+// This kernel keeps its OWN text of the row tail, per row j of the group: the per-entry lines are RowAcc::add, the four butterflies
+// RowAcc::reduce<G>, the stores row_store and the block under !MAT row_verdict.  Whoever changes one of those helpers changes this
+// text with it: the kernel must give the bits of k_sep_eval (tests/test_gpu_sep_kernels.py compares the forms, R = 1, 2, 4).
+// (Written with the helpers it was 0.4 % slower on 1e6 short rows, profiles/row_tail_ab.txt.)
 template <int G, int R, bool MAT = false>
 __global__ __launch_bounds__(kBlock) void k_sep_sweep(NlpDev P, const int32_t* __restrict__ nl_rows, int64_t m_nl,
                                                       const double* __restrict__ x, double f_tol, SweepOut O) {
@@ -361,39 +420,26 @@ static __global__ __launch_bounds__(1024) void k_sep_eval_long(NlpDev P, const i
     __shared__ int shn[16];
     const int32_t r = rows[blockIdx.x];
     const int64_t beg = P.rowptr[r], end = P.rowptr[r + 1];
-    double acc_g = 0.0, acc_dot = 0.0, mx = -__builtin_inf();
-    int nf = 0;
+    RowAcc acc;
     for (int64_t e = beg + threadIdx.x; e < end; e += 1024) {
         const int ck = P.colk[e];
         const double2 q = P.pp[e];
         const double xv = x[ck & kColMask];
         double val, der;
         atom_eval((unsigned)ck >> kKindShift, q.x, q.y, xv, val, der);
-        acc_g += val; acc_dot += xv * der; mx = nanmax(mx, der); nf |= !isfinite(der);
+        acc.add(val, der, xv);
         O.jac[e] = der;
     }
-    acc_g = group_sum<64>(acc_g); acc_dot = group_sum<64>(acc_dot); mx = group_nanmax<64>(mx); nf = group_or<64>(nf);
+    acc.reduce<64>();
     const int wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { sh[wv][0] = acc_g; sh[wv][1] = acc_dot; sh[wv][2] = mx; shn[wv] = nf; }
+    if ((threadIdx.x & 63) == 0) { sh[wv][0] = acc.g; sh[wv][1] = acc.dot; sh[wv][2] = acc.mx; shn[wv] = acc.nf; }
     __syncthreads();
     if (threadIdx.x != 0) return;
-    for (int k = 1; k < 16; ++k) { acc_g += sh[k][0]; acc_dot += sh[k][1]; mx = nanmax(mx, sh[k][2]); nf |= shn[k]; }
-    const double g = acc_g + P.rconst[r];
-    if (P.pad_zero[r]) mx = nanmax(mx, 0.0);
-    O.g[r] = g; O.bconst[r] = g - acc_dot; O.maxc[r] = mx; O.nonfin[r] = nf;
+    for (int k = 1; k < 16; ++k) acc.merge(RowAcc{sh[k][0], sh[k][1], sh[k][2], shn[k]});
+    const double g = acc.g + P.rconst[r];
+    row_store(O, r, g, g - acc.dot, acc.mx, acc.nf, P.pad_zero[r]);
     const int64_t slot = slots[blockIdx.x];
-    if (flags_on && slot >= 0) {
-        const double lb = P.lb[r], ub = P.ub[r];
-        const bool sat = (g >= lb - f_tol) && (g <= ub + f_tol);   // separators.jl:120 (NaN -> violated)
-        O.flag[slot] = sat ? 0 : 1;
-        O.cnt[slot] = sat ? 0 : (end - beg);
-        if (!sat) {
-            double v = fmax(g - ub, lb - g);
-            if (v != v) v = __builtin_inf();
-            atomicMax(reinterpret_cast<unsigned long long*>(O.maxviol), (unsigned long long)__double_as_longlong(v));
-            if (nf) atomicOr(O.any_nonfin, 1);
-        }
-    }
+    if (flags_on && slot >= 0) atomic_max_nonneg(O.maxviol, row_verdict(O, slot, end - beg, g, P.lb[r], P.ub[r], f_tol, acc.nf));
 }
 
 // ---- batch-blocked sweep for MANY SHORT rows (round 4; cfg4: 1e6 rows of 32 entries) ---------------
@@ -504,40 +550,23 @@ static __global__ __launch_bounds__(kSbThreads) void k_sep_sweep_batch(SbView V,
         sval[tid] = val; sxd[tid] = xv * der; sder[tid] = der; srow[tid] = rw;
         __syncthreads();
         if (live && (tid == 0 || srow[tid - 1] != rw)) {            // head of a run of equal rows: add the run up in storage order
-            double g = 0.0, d = 0.0, mx = -__builtin_inf();
-            int nf = 0;
-            for (int j = tid; j < kSbThreads && srow[j] == rw; ++j) {
-                g += sval[j]; d += sxd[j]; mx = nanmax(mx, sder[j]); nf |= !isfinite(sder[j]);
-            }
-            acc_g[rw] += g; acc_d[rw] += d; acc_m[rw] = nanmax(acc_m[rw], mx); acc_nf[rw] |= nf;
+            RowAcc run;
+            for (int j = tid; j < kSbThreads && srow[j] == rw; ++j) run.merge(RowAcc{sval[j], sxd[j], sder[j], !isfinite(sder[j])});
+            acc_g[rw] += run.g; acc_d[rw] += run.dot; acc_m[rw] = nanmax(acc_m[rw], run.mx); acc_nf[rw] |= run.nf;
         }
         __syncthreads();
         cur = nxt;
     }
     __syncthreads();
-    // the isconstrsat tail of k_sep_sweep, one thread per row of the batch
+    // the row tail (row_store, row_verdict), one thread per row of the batch
     double viol = 0.0;
     for (int i = tid; i < nrows; i += kSbThreads) {
         const int32_t rr = nl_rows[s0 + i];
         if (P.row_kind[rr] != KTN_ROW_SEP) continue;
         const double g = acc_g[i] + P.rconst[rr];
-        double m = acc_m[i];
-        if (P.pad_zero[rr]) m = nanmax(m, 0.0);
         const int nf = acc_nf[i];
-        O.g[rr] = g;
-        O.bconst[rr] = g - acc_d[i];
-        O.maxc[rr] = m;
-        O.nonfin[rr] = nf;
-        const double lb = P.lb[rr], ub = P.ub[rr];
-        const bool sat = (g >= lb - f_tol) && (g <= ub + f_tol);   // separators.jl:120 (NaN -> violated)
-        O.flag[s0 + i] = sat ? 0 : 1;
-        O.cnt[s0 + i] = sat ? 0 : (P.rowptr[rr + 1] - P.rowptr[rr]);
-        if (!sat) {
-            double v = fmax(g - ub, lb - g);
-            if (v != v) v = __builtin_inf();
-            viol = fmax(viol, v);
-            if (nf) { if (*O.any_nonfin == 0) atomicOr(O.any_nonfin, 1); };
-        }
+        row_store(O, rr, g, g - acc_d[i], acc_m[i], nf, P.pad_zero[rr]);
+        viol = fmax(viol, row_verdict(O, s0 + i, P.rowptr[rr + 1] - P.rowptr[rr], g, P.lb[rr], P.ub[rr], f_tol, nf));
     }
     block_max_nonneg(O.maxviol, viol);
 }
@@ -554,8 +583,7 @@ struct SepPartial { double g, dot, mx, nf; };
 // one kind-uniform run [beg, end) of a (row, block) segment; x* comes from the LDS copy of the block
 template <int G, int KIND, int kU>
 __device__ __forceinline__ void blk_run(const int32_t* __restrict__ bcolk, const double2* __restrict__ bpp, int64_t beg,
-                                        int64_t end, int lane, const double* xs, int64_t c0, double& acc_g, double& acc_dot,
-                                        double& mx, int& nf) {
+                                        int64_t end, int lane, const double* xs, int64_t c0, RowAcc& acc) {
     for (int64_t e = beg + lane; e < end; e += kU * G) {
         int ck[kU];
         double2 q[kU];
@@ -572,10 +600,7 @@ __device__ __forceinline__ void blk_run(const int32_t* __restrict__ bcolk, const
                 const double xv = xs[(ck[u] & kColMask) - c0];
                 double val, der;
                 atom_eval(KIND, q[u].x, q[u].y, xv, val, der);
-                acc_g += val;
-                acc_dot += xv * der;
-                mx = nanmax(mx, der);
-                nf |= !isfinite(der);
+                acc.add(val, der, xv);
             }
         }
     }
@@ -613,25 +638,17 @@ __global__ __launch_bounds__(BS) void k_sep_eval_blk(const int32_t* __restrict__
         const int64_t* sp = bseg + (int64_t)b * (m_nl + 1);
         const int64_t beg = sp[s], end = sp[s + 1];
         const int4 kb = bkind[(int64_t)b * (m_nl + 1) + s];   // the segment is sorted by atom kind: starts of the QUAD / EXP / NEGLOG runs
-        double acc_g = 0.0, acc_dot = 0.0, mx = -__builtin_inf();
-        int nf = 0;
-        blk_run<G, KTN_ATOM_LIN, kU>(bcolk, bpp, beg, beg + kb.x, lane, xs, c0, acc_g, acc_dot, mx, nf);
-        blk_run<G, KTN_ATOM_QUAD, kU>(bcolk, bpp, beg + kb.x, beg + kb.y, lane, xs, c0, acc_g, acc_dot, mx, nf);
-        blk_run<G, KTN_ATOM_EXP, kU>(bcolk, bpp, beg + kb.y, beg + kb.z, lane, xs, c0, acc_g, acc_dot, mx, nf);
-        blk_run<G, KTN_ATOM_NEGLOG, kU>(bcolk, bpp, beg + kb.z, end, lane, xs, c0, acc_g, acc_dot, mx, nf);
-        acc_g = group_sum<G>(acc_g);
-        acc_dot = group_sum<G>(acc_dot);
-        mx = group_nanmax<G>(mx);
-        nf = group_or<G>(nf);
-        if (lane == 0) {
-            SepPartial o;
-            o.g = acc_g; o.dot = acc_dot; o.mx = mx; o.nf = nf ? 1.0 : 0.0;
-            part[(int64_t)b * m_nl + s] = o;             // [block][row]: k_sep_combine reads it coalesced
-        }
+        RowAcc acc;
+        blk_run<G, KTN_ATOM_LIN, kU>(bcolk, bpp, beg, beg + kb.x, lane, xs, c0, acc);
+        blk_run<G, KTN_ATOM_QUAD, kU>(bcolk, bpp, beg + kb.x, beg + kb.y, lane, xs, c0, acc);
+        blk_run<G, KTN_ATOM_EXP, kU>(bcolk, bpp, beg + kb.y, beg + kb.z, lane, xs, c0, acc);
+        blk_run<G, KTN_ATOM_NEGLOG, kU>(bcolk, bpp, beg + kb.z, end, lane, xs, c0, acc);
+        acc.template reduce<G>();
+        if (lane == 0) part[(int64_t)b * m_nl + s] = SepPartial{acc.g, acc.dot, acc.mx, acc.nf ? 1.0 : 0.0};   // [block][row]: k_sep_combine reads it coalesced
     }
 }
 
-// block-order combination of the partials + the isconstrsat tail of k_sep_eval.  Everything a slot needs sits in one
+// block-order combination of the partials + the row tail (row_store, row_verdict).  Everything a slot needs sits in one
 // 32-byte record (no nl_rows -> row_kind -> bounds pointer chase: the kernel is 10 000 threads of pure latency).
 struct SepSlot { double rconst, lb, ub; int32_t row; int32_t len_pad; };   // len_pad = row length << 1 | pad_zero; row < 0: not separable
 
@@ -641,30 +658,15 @@ static __global__ __launch_bounds__(kBlock) void k_sep_combine(const SepSlot* __
     if (s >= m_nl) return;
     const SepSlot sl = slots[s];
     if (sl.row < 0) return;
-    double acc_g = 0.0, acc_dot = 0.0, mx = -__builtin_inf();
-    int nf = 0;
+    RowAcc acc;
 #pragma unroll 8
     for (int b = 0; b < NB; ++b) {
         const SepPartial q = part[(int64_t)b * m_nl + s];
-        acc_g += q.g;
-        acc_dot += q.dot;
-        mx = nanmax(mx, q.mx);
-        nf |= (q.nf != 0.0);
+        acc.merge(RowAcc{q.g, q.dot, q.mx, q.nf != 0.0});
     }
-    const int32_t r = sl.row;
-    const double g = acc_g + sl.rconst;
-    if (sl.len_pad & 1) mx = nanmax(mx, 0.0);
-    O.g[r] = g;
-    O.bconst[r] = g - acc_dot;
-    O.maxc[r] = mx;
-    O.nonfin[r] = nf;
-    const bool sat = (g >= sl.lb - f_tol) && (g <= sl.ub + f_tol);   // separators.jl:120 (NaN -> violated)
-    O.flag[s] = sat ? 0 : 1;
-    O.cnt[s] = sat ? 0 : (int64_t)(sl.len_pad >> 1);
-    if (!sat) {
-        atomic_max_nonneg(O.maxviol, fmax(g - sl.ub, sl.lb - g));
-        if (nf) { if (*O.any_nonfin == 0) atomicOr(O.any_nonfin, 1); };
-    }
+    const double g = acc.g + sl.rconst;
+    row_store(O, sl.row, g, g - acc.dot, acc.mx, acc.nf, sl.len_pad & 1);
+    atomic_max_nonneg(O.maxviol, row_verdict(O, s, sl.len_pad >> 1, g, sl.lb, sl.ub, f_tol, acc.nf));
 }
 
 // ---- deepest-cut selection (cut_cap): depth keys of the violated rows, then re-flagging against the threshold ----
@@ -678,8 +680,7 @@ static __global__ __launch_bounds__(kBlock) void k_depth_keys(NlpDev P, const in
     uint64_t k = 0;
     if (flag[s]) {
         const int32_t r = nl_rows[s];
-        double d = fmax(g[r] - P.ub[r], P.lb[r] - g[r]);
-        if (!(d == d)) d = __builtin_inf();
+        const double d = row_violation(g[r], P.lb[r], P.ub[r]);
         k = (d > 0.0) ? (uint64_t)__double_as_longlong(d) : 1ULL;     // violated within f_tol slack only: smallest key
     }
     keys[s] = k;
@@ -796,26 +797,9 @@ static __global__ __launch_bounds__(kBlock) void k_gj_stats(NlpDev P, const int3
     if (classed && classed[r]) return;                                                        // k_tape_classed has done this row's part
     const int64_t beg = P.rowptr[r], end = P.rowptr[r + 1];
     const double g = O.g[r];
-    double b = g, mx = -__builtin_inf();
-    int nf = 0;
-    for (int64_t e = beg; e < end; ++e) {
-        const double der = O.jac[e];
-        b += -x[P.col[e]] * der;
-        mx = nanmax(mx, der);
-        nf |= !isfinite(der);
-    }
-    if (P.pad_zero[r]) mx = nanmax(mx, 0.0);
-    O.bconst[r] = b;
-    O.maxc[r] = mx;
-    O.nonfin[r] = nf;
-    const double lb = P.lb[r], ub = P.ub[r];
-    const bool sat = (g >= lb - f_tol) && (g <= ub + f_tol);
-    O.flag[gid] = sat ? 0 : 1;
-    O.cnt[gid] = sat ? 0 : (end - beg);
-    if (!sat) {
-        atomic_max_nonneg(O.maxviol, fmax(g - ub, lb - g));
-        if (nf) { if (*O.any_nonfin == 0) atomicOr(O.any_nonfin, 1); };
-    }
+    const RowJacStats s = row_jac_stats(g, beg, end, [&](int64_t e) { return O.jac[e]; }, [&](int64_t e) { return x[P.col[e]]; });
+    row_store_cut(O, r, s.bconst, s.mx, s.nf, P.pad_zero[r]);
+    atomic_max_nonneg(O.maxviol, row_verdict(O, gid, end - beg, g, P.lb[r], P.ub[r], f_tol, s.nf));
 }
 
 // KTN_ROW_HOST rows: values and Jacobian entries computed by the caller's evaluator, staged in (gh, jh)
@@ -1069,30 +1053,46 @@ static __global__ __launch_bounds__(kBlock) void k_purge_relink(int64_t m_nl, in
     last_cut[s] = head;
 }
 
-// gencut + round_coefs + row append: G lanes per violated row.
-template <int G>
-__global__ __launch_bounds__(kBlock) void k_emit(NlpDev P, const int32_t* __restrict__ nl_rows,
-                                                 const int32_t* __restrict__ viol_slots, int64_t n_viol,
-                                                 const double* __restrict__ x, const double* __restrict__ jac,
-                                                 const double* __restrict__ maxc, double cut_coef_rng, int round_coefs,
-                                                 int64_t base_row, LpRows L) {
+// gencut + round_coefs + row append, G lanes per violated row: the body of k_emit and k_emit_esh (esh.hpp).  row_der(r) looks at
+// row r once and returns the callable that gives entry e (column c) its coefficient.
+template <int G, class ROWDER>
+__device__ __forceinline__ void emit_rows(const NlpDev& P, const int32_t* __restrict__ nl_rows, const int32_t* __restrict__ viol_slots,
+                                          int64_t n_viol, const double* __restrict__ maxc, double cut_coef_rng, int round_coefs,
+                                          int64_t base_row, const LpRows& L, ROWDER&& row_der) {
     const int64_t v = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / G;
     const int lane = threadIdx.x & (G - 1);
     if (v >= n_viol) return;
     const int32_t r = nl_rows[viol_slots[v]];
     const int64_t beg = P.rowptr[r], end = P.rowptr[r + 1];
     const int64_t dst = L.rowptr[base_row + v];
-    const bool sep = P.row_kind[r] == KTN_ROW_SEP;
+    auto der_of = row_der(r);
     const double mx = maxc[r];
     for (int64_t e = beg + lane; e < end; e += G) {
         const int c = P.col[e];
-        double der;
-        if (sep) { double val; const double2 q = P.pp[e]; atom_eval((unsigned)P.colk[e] >> kKindShift, q.x, q.y, x[c], val, der); }
-        else der = jac[e];
-        if (round_coefs && (der + cut_coef_rng < mx)) der = 0.0;   // model.jl:202-206 (signed max)
+        double der = der_of(e, c);
+        if (round_coefs && round_coef(der, mx, cut_coef_rng)) der = 0.0;
         L.col[dst + (e - beg)] = c;
         L.val[dst + (e - beg)] = der;
     }
+}
+// the coefficient of separable entry e at the coordinate xv of its column
+__device__ __forceinline__ double sep_entry_der(const NlpDev& P, int64_t e, double xv) {
+    double val, der;
+    const double2 q = P.pp[e];
+    atom_eval((unsigned)P.colk[e] >> kKindShift, q.x, q.y, xv, val, der);
+    return der;
+}
+// Kelley's cut: the separable derivatives at x*, every other row's from its materialised Jacobian
+template <int G>
+__global__ __launch_bounds__(kBlock) void k_emit(NlpDev P, const int32_t* __restrict__ nl_rows,
+                                                 const int32_t* __restrict__ viol_slots, int64_t n_viol,
+                                                 const double* __restrict__ x, const double* __restrict__ jac,
+                                                 const double* __restrict__ maxc, double cut_coef_rng, int round_coefs,
+                                                 int64_t base_row, LpRows L) {
+    emit_rows<G>(P, nl_rows, viol_slots, n_viol, maxc, cut_coef_rng, round_coefs, base_row, L, [&](int32_t r) {
+        const bool sep = P.row_kind[r] == KTN_ROW_SEP;
+        return [&P, x, jac, sep](int64_t e, int c) { return sep ? sep_entry_der(P, e, x[c]) : jac[e]; };
+    });
 }
 
 // ================================================================ LP: PDHG ========

@@ -15,9 +15,8 @@
 //
 //   k_quad_jac<G>     G lanes per entry: lane-strided partial sums over the segment (consecutive lanes, consecutive Q entries),
 //                     xor-butterfly, lane 0 writes jac[e] = a_e + s_e and vterm[t].  An empty segment gives jac[e] = a_e.
-//   k_quad_stats<G2>  G2 lanes per row: the tail k_sep_eval / k_gj_stats produce -- g = rconst + sum vterm (lane-strided, butterfly),
-//                     bconst = g - sum x_c J_c, signed max coefficient (pad_zero), non-finite flag; with flags on also
-//                     flag / cnt / maxviol / any_nonfin by NL slot.
+//   k_quad_stats<G2>  G2 lanes per row: the row tail of kernels.hpp -- a RowAcc over (vterm, jac), g = rconst + sum vterm,
+//                     row_store; with flags on also row_verdict by NL slot.
 // No atomics on values and a summation order fixed by (G, G2): run-to-run identical.  Rows beyond 8 192 structure entries are
 // correct (a lane group just loops) but not specially optimised.
 #pragma once
@@ -93,40 +92,18 @@ __global__ __launch_bounds__(kBlock) void k_quad_stats(NlpDev P, QuadDev Q, Quad
     const int32_t r = live ? L.rows[gid] : 0;
     const int64_t beg = live ? P.rowptr[r] : 0, end = live ? P.rowptr[r + 1] : 0;
     const int64_t tb = live ? L.tbase[gid] : 0;
-    double acc_g = 0.0, acc_dot = 0.0, mx = -__builtin_inf();
-    int nf = 0;
+    RowAcc acc;
     for (int64_t e = beg + lane; e < end; e += G) {
         const double der = O.jac[e];
         const double xv = x[P.col[e]];
-        acc_g += Q.vterm[tb + (e - beg)];
-        acc_dot += xv * der;
-        mx = nanmax(mx, der);
-        nf |= !isfinite(der);
+        acc.add(Q.vterm[tb + (e - beg)], der, xv);
     }
-    acc_g = group_sum<G>(acc_g);
-    acc_dot = group_sum<G>(acc_dot);
-    mx = group_nanmax<G>(mx);
-    nf = group_or<G>(nf);
+    acc.template reduce<G>();
     double viol = 0.0;
     if (lane == 0 && live) {
-        const double g = acc_g + P.rconst[r];
-        if (P.pad_zero[r]) mx = nanmax(mx, 0.0);
-        O.g[r] = g;
-        O.bconst[r] = g - acc_dot;
-        O.maxc[r] = mx;
-        O.nonfin[r] = nf;
-        if (flags_on) {
-            const int64_t slot = L.slots[gid];
-            const double lb = P.lb[r], ub = P.ub[r];
-            const bool sat = (g >= lb - f_tol) && (g <= ub + f_tol);   // separators.jl:120 (NaN -> violated)
-            O.flag[slot] = sat ? 0 : 1;
-            O.cnt[slot] = sat ? 0 : (end - beg);
-            if (!sat) {
-                viol = fmax(g - ub, lb - g);
-                if (viol != viol) viol = __builtin_inf();
-                if (nf) { if (*O.any_nonfin == 0) atomicOr(O.any_nonfin, 1); };
-            }
-        }
+        const double g = acc.g + P.rconst[r];
+        row_store(O, r, g, g - acc.dot, acc.mx, acc.nf, P.pad_zero[r]);
+        if (flags_on) viol = row_verdict(O, L.slots[gid], end - beg, g, P.lb[r], P.ub[r], f_tol, acc.nf);
     }
     if (flags_on) block_max_nonneg(O.maxviol, viol);
 }

@@ -43,7 +43,7 @@ struct TapeClassDev {
     const int32_t* mrow;         // member row ids, ascending inside a class
 };
 
-// precompute! + the k_gj_stats part of the rows of the classed classes.  One wavefront per workgroup; `mslot` gives the
+// precompute! + the row tail (k_gj_stats' part) of the rows of the classed classes.  One wavefront per workgroup; `mslot` gives the
 // index under which a member's flag / cnt are stored: its NL slot in the sweep, its row in precompute_all (k_gj_stats over
 // all rows does the same there).  wave_cls / wave_first point at the launch's first wavefront.  Dynamic LDS: (2 nnodes + nslots) * 512 B
 // of the largest launched class.
@@ -96,31 +96,12 @@ static __global__ __launch_bounds__(kTapeClassWave) void k_tape_classed(NlpDev P
             }
             g = val[(N - 1) * kTapeClassWave] + P.rconst[r];
         }
-        O.g[r] = g;
-        // k_gj_stats for this row, entries in storage order; each Jacobian entry is stored once
+        // the row tail of k_gj_stats, entries in storage order; each Jacobian entry is stored once, as it is read
         const int64_t beg = P.rowptr[r];
-        double b = g, mx = -__builtin_inf();
-        int nf = 0;
-        for (int s = 0; s < S; ++s) {
-            const double der = jl[s * kTapeClassWave];
-            O.jac[beg + s] = der;
-            b += -x[col[(int64_t)s * M.count]] * der;
-            mx = nanmax(mx, der);
-            nf |= !isfinite(der);
-        }
-        if (P.pad_zero[r]) mx = nanmax(mx, 0.0);
-        O.bconst[r] = b;
-        O.maxc[r] = mx;
-        O.nonfin[r] = nf;
-        const double lb = P.lb[r], ub = P.ub[r];
-        const bool sat = (g >= lb - f_tol) && (g <= ub + f_tol);
-        O.flag[gid] = sat ? 0 : 1;
-        O.cnt[gid] = sat ? 0 : (int64_t)S;
-        if (!sat) {
-            viol = fmax(g - ub, lb - g);
-            if (viol != viol) viol = __builtin_inf();
-            if (nf) { if (*O.any_nonfin == 0) atomicOr(O.any_nonfin, 1); };
-        }
+        const RowJacStats st = row_jac_stats(g, 0, S, [&](int s) { const double der = jl[s * kTapeClassWave]; O.jac[beg + s] = der; return der; },
+                                             [&](int s) { return x[col[(int64_t)s * M.count]]; });
+        row_store(O, r, g, st.bconst, st.mx, st.nf, P.pad_zero[r]);
+        viol = row_verdict(O, gid, S, g, P.lb[r], P.ub[r], f_tol, st.nf);
     }
     block_max_nonneg(O.maxviol, viol);
 }

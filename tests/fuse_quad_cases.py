@@ -9,6 +9,8 @@ with W = sum_uv w_uv (e_u - e_v)(e_u - e_v)', w_uv in U(0.1, 0.5), a weighted gr
 term 1/2 (x - xhat)' W (x - xhat) is convex with value 0 and gradient 0 at xhat, so the KKT point, its multipliers, `opt_obj`
 and `planted_obj_bound` carry over unchanged.  `quad_objective_problem` does the same to the separable objective
 sum 1/2 d_j (x_j - x0_j)^2 of `make_instance(objective="quad")`."""
+import math
+
 import numpy as np
 
 import katana_jl_amd as ktn
@@ -139,3 +141,23 @@ def quad_row_values(d, x):
 
 def quad_objective_value(d, x):
     return quad_row_value(d.obj_col, d.obj_p0, d.obj_quad_ptr, d.obj_quad_col, d.obj_quad_val, d.obj_const, x)
+
+
+def cone_problem(rng, cones=1):
+    """Katana.jl's documentation example (test_gpu_batch_tapes.cone_model), `cones` times in one block: the cone
+    sqrt(x^2 + y^2) <= z - 0.25 a tape row, the paraboloid x^2 + y^2 + z <= 1 a QUAD row, a linear row that never binds;
+    optimum -1/2 sum hypot(a, b)"""
+    rows, ocol, oval, ub, best = [], [], [], [], 0.0
+    for c in range(cones):
+        j = 3 * c
+        x, y, z = ktn.var(j), ktn.var(j + 1), ktn.var(j + 2)
+        a, b = rng.uniform(0.5, 2.0, 2) * rng.choice([-1.0, 1.0], 2)
+        rows += [("tape", ktn.sqrt(x * x + y * y) - z),
+                 ("quad", [j + 2], [1.0], [j, j + 1], [j, j + 1], [2.0, 2.0], 0.0, False),
+                 ("sep", [j, j + 1, j + 2], np.zeros(3, dtype=np.uint8), np.ones(3), np.zeros(3), 0.0, True)]
+        ocol += [j, j + 1]; oval += [a, b]; ub += [-0.25, 1.0, 3.0]
+        best -= 0.5 * math.hypot(a, b)
+    n = 3 * cones
+    d, _ = QC.assemble(n, rows, ("lin", ocol, oval))
+    assert list(d.row_kind) == [ktn._lib.ROW_TAPE, ktn._lib.ROW_QUAD, ktn._lib.ROW_SEP] * cones
+    return ktn.Problem(n, 3 * cones, np.full(n, -2.0), np.full(n, 2.0), [-math.inf] * (3 * cones), ub, "Min", d), best

@@ -9,7 +9,7 @@ import pytest
 import katana_jl_amd as ktn
 from katana_jl_amd.batch import FusedBatch
 import fuse_quad_cases as FQ
-import quad_cases as QC
+from fuse_quad_cases import cone_problem
 from helpers import assert_planted_objective
 
 pytestmark = pytest.mark.gpu
@@ -72,26 +72,6 @@ def test_segment_length_edges_at_forced_lane_counts(monkeypatch, G):
     res = fb.solve(cut_capacity=48)
     assert_device_loop(res, 8 * 12)
     check_planted(res, ordinary(probs), insts)
-
-
-def cone_problem(rng, cones=1):
-    """Katana.jl's documentation example (test_gpu_batch_tapes.cone_model), `cones` times in one block: the cone
-    sqrt(x^2 + y^2) <= z - 0.25 a tape row, the paraboloid x^2 + y^2 + z <= 1 a QUAD row, a linear row that never binds;
-    optimum -1/2 sum hypot(a, b)"""
-    rows, ocol, oval, ub, best = [], [], [], [], 0.0
-    for c in range(cones):
-        j = 3 * c
-        x, y, z = ktn.var(j), ktn.var(j + 1), ktn.var(j + 2)
-        a, b = rng.uniform(0.5, 2.0, 2) * rng.choice([-1.0, 1.0], 2)
-        rows += [("tape", ktn.sqrt(x * x + y * y) - z),
-                 ("quad", [j + 2], [1.0], [j, j + 1], [j, j + 1], [2.0, 2.0], 0.0, False),
-                 ("sep", [j, j + 1, j + 2], np.zeros(3, dtype=np.uint8), np.ones(3), np.zeros(3), 0.0, True)]
-        ocol += [j, j + 1]; oval += [a, b]; ub += [-0.25, 1.0, 3.0]
-        best -= 0.5 * math.hypot(a, b)
-    n = 3 * cones
-    d, _ = QC.assemble(n, rows, ("lin", ocol, oval))
-    assert list(d.row_kind) == [ktn._lib.ROW_TAPE, ktn._lib.ROW_QUAD, ktn._lib.ROW_SEP] * cones
-    return ktn.Problem(n, 3 * cones, np.full(n, -2.0), np.full(n, 2.0), [-INF] * (3 * cones), ub, "Min", d), best
 
 
 def check_cones(res, probs, cases):
