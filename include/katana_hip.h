@@ -186,7 +186,8 @@ typedef struct {
        violated row at the LP point x* (linear_oa_cut, src/algorithms.jl:3-18); KTN_CUT_SUPPORTING searches, row by row, the
        segment from an interior point x_int to x* for the point where the row reaches its bound and cuts there (supporting
        hyperplanes).  x_int is the caller's (ktn_set_interior_point) or found once per loaded problem
-       by the engine on the auxiliary min-max problem.  Not with ktn_optimize_blocks, a row-sharded handle or a cut exchange. */
+       by the engine on the auxiliary min-max problem.  Not with ktn_optimize_blocks (ktn_optimize_blocks_ex with KTN_BLOCKS_SUPPORTING
+       runs it inside the device-side loop), a row-sharded handle or a cut exchange. */
     int32_t cut_algo;          /* 0 (KTN_CUT_KELLEY), 1 (KTN_CUT_SUPPORTING) or 2 (KTN_CUT_SUPPORTING_QUAD)                      */
     int32_t esh_root_iters;    /* 20    Newton / bisection steps of a row's root search                                    */
     double  esh_root_tol;      /* 0.1   the search stops once 0 <= phi <= esh_root_tol * f_tol                            */
@@ -477,6 +478,40 @@ int ktn_set_blocks(ktn_handle h, int64_t nblocks, const int64_t* col_offsets);
  * "ecp_blocks_launches", "ecp_blocks_fallbacks" (cumulative), "ecp_blocks_tape_rows", "ecp_blocks_quad_rows" (tape / QUAD NL rows the
  * last device loop served). */
 int ktn_optimize_blocks(ktn_handle h, int32_t cut_capacity);
+/* ktn_optimize_blocks with options.  flags = 0 is ktn_optimize_blocks itself.
+ *   KTN_BLOCKS_SUPPORTING   cut_algo = KTN_CUT_SUPPORTING / _QUAD runs INSIDE the device-side loop (k_ecp_blocks<1>, csrc/batch_ecp.hpp;
+ *       DESIGN.md section 11 "In the device-side loop"): the interior point is found or taken first if that has not happened yet --
+ *       ktn_set_interior_point on the fused problem (the concatenation of the instances' points), or the engine's auxiliary problem
+ *       on the fused problem --, then every violated separable row that takes part is cut where the segment x_int -> x* leaves it
+ *       (the bracketed Newton of csrc/esh.hpp, 16 lanes per row, no launch and no read-back per round) and, under
+ *       KTN_CUT_SUPPORTING_QUAD, every such KTN_ROW_QUAD row at its closed-form boundary point (csrc/esh_quad.hpp).  TAPE ROWS KEEP
+ *       KELLEY'S CUT in the device loop and count as fallback rows.  With no interior point the launch is Kelley's (k_ecp_blocks<0>).
+ *       A batch that falls back runs the ordinary loop with the handle's cut_algo.  Without this flag a handle with cut_algo != 0 is
+ *       refused (KTN_E_UNSUPPORTED), as by ktn_optimize_blocks.
+ *   KTN_BLOCKS_NO_FALLBACK  return after the device launch: the status is :Optimal only if every instance's is, otherwise the first
+ *       other instance's status; ktn_get_solution returns the x the launch wrote; "ecp_blocks_fallbacks" does not count the call; a
+ *       batch that does not qualify for the device loop returns KTN_E_UNSUPPORTED.
+ * Stats: "esh_rows" "esh_fallback_rows" "esh_newton_steps" "esh_quad_rows" accumulate the instances' counters of a k_ecp_blocks<1>
+ * launch; "ecp_blocks_esh_rows" rows moved by the last launch (0 after a Kelley launch).  ktn_last_sweep_lambdas keeps describing
+ * the sweeps of the host-driven loop only: the lambdas of a device launch come from ktn_blocks_get_cuts. */
+#define KTN_BLOCKS_SUPPORTING  1   /* cut_algo 1 / 2 run inside the device loop (without it: refused, as ktn_optimize_blocks does) */
+#define KTN_BLOCKS_NO_FALLBACK 2   /* do not run the ordinary loop when the batch does not qualify or an instance does not end :Optimal */
+int ktn_optimize_blocks_ex(ktn_handle h, int32_t cut_capacity, int32_t flags);
+/* The records of the last device launch on the loaded problem, [n_blocks x 8] doubles, instance after instance:
+ *   0 status (KTN_STATUS_*)   1 cutting-plane iterations   2 objective (without the loaded problem's constant)
+ *   3 cuts (numcuts: the instance's linear rows counted, as the reference does)   4 PDHG iterations
+ *   5 largest violation of the last sweep   6 LP rows at the end (linear rows + cut rows)   7 arena overflow (0 / 1)
+ * Size convention of ktn_last_sweep_lambdas: *count is always set; with out == NULL nothing else happens, otherwise cap >= *count.
+ * KTN_E_INVALID before any device launch on the loaded problem (a batch that did not qualify launched nothing). */
+int ktn_blocks_get_results(ktn_handle h, double* out, int64_t cap, int64_t* count);
+/* The cut rows of instance `block` in its arena after the last device launch: the rows beyond its linear rows, in LP row order.
+ * rowptr [n_rows + 1] (from 0), col [n_nnz] GLOBAL column indices, val [n_nnz] (coefficients after round_coefs), lo / hi [n_rows],
+ * nl_slot [n_rows] the position of the cut's row in the engine's NL row list (ktn_last_sweep_slots numbering; from the arena's
+ * last_cut / cut_prev lists), lambda [n_rows] where the cut was taken on the segment x_int -> x* (1: at x* itself, everywhere after a
+ * Kelley launch).  *n_rows and *n_nnz are always set; with rowptr == NULL nothing else happens, otherwise every buffer is needed with
+ * cap_rows >= *n_rows (rowptr: cap_rows + 1) and cap_nnz >= *n_nnz.  KTN_E_INVALID before any device launch on the loaded problem. */
+int ktn_blocks_get_cuts(ktn_handle h, int64_t block, int64_t* rowptr, int32_t* col, double* val, double* lo, double* hi,
+                        int64_t* nl_slot, double* lambda, int64_t cap_rows, int64_t cap_nnz, int64_t* n_rows, int64_t* n_nnz);
 
 /* ---- row-sharded LP over several GPUs (no reference counterpart: it splits the LP re-solve of
  * src/model.jl:259 and the cut loop of :272-283 over the ranks) -------------------------------------------------------

@@ -68,6 +68,23 @@ def solve_batch(solver, instances, threads=16, describe=SeparableNLP, fused=Fals
     return out, time.perf_counter() - t0
 
 
+def fuse_points(points, offs, nvar=None):
+    """Per-instance vectors -> one vector in the fused column layout of instances.fuse_instances / nlp.fuse_problems: instance k's
+    entries start at offs[k].  nvar[k] = the instance's own number of variables where fusion appended a column to it (the epigraph
+    variable of a quadratic objective), which is padded with 0; None: every instance fills its whole range."""
+    import numpy as np
+    if len(points) != len(offs) - 1:
+        raise ValueError("one point per instance: %d points for %d instances" % (len(points), len(offs) - 1))
+    out = np.zeros(int(offs[-1]))
+    for k, pt in enumerate(points):
+        pt = np.asarray(pt, dtype=np.float64).reshape(-1)
+        own = int(nvar[k]) if nvar is not None else int(offs[k + 1] - offs[k])
+        if len(pt) != own or own > int(offs[k + 1] - offs[k]):
+            raise ValueError("instance %d has %d variables, its point %d entries" % (k, own, len(pt)))
+        out[int(offs[k]):int(offs[k]) + own] = pt
+    return out
+
+
 class FusedBatch:
     """A batch loaded ONCE as one block-diagonal problem (instances.fuse_instances + ktn_loadproblem [+ ktn_set_blocks]); solve()
     can then be called repeatedly -- every call after the first starts from the loaded state (ktn_reset) -- with the batch's
@@ -104,21 +121,40 @@ class FusedBatch:
         self._solved = False
         return self
 
-    def solve(self, cut_capacity=0):
+    def set_interior_points(self, points):
+        """Interior points of the instances, one per instance (each with the instance's own num_var entries), concatenated into
+        the fused layout and handed to the engine (ktn_set_interior_point).  Where fusion gave an instance an epigraph variable
+        (a quadratic objective, nlp.fuse_problems) that column is padded with 0: no row that takes part reads it.  None clears
+        the point: the engine then solves the auxiliary problem of the fused batch -- ONE problem over every instance, by the
+        host-driven loop -- when it next needs a point."""
+        if points is None:
+            self.m.set_interior_point(None)
+            return None
+        xi = fuse_points(points, self.offs, self._nvar if self._objinfo is not None else None)
+        self.m.set_interior_point(xi)
+        return xi
+
+    def solve(self, cut_capacity=0, supporting=None):
         """cut_capacity: cuts per NL row an instance's arena has room for in the device-side loop (0: the engine's default, 12);
-        an instance that outgrows it sends the batch to the host-driven loop (stat ecp_blocks_fallbacks)"""
+        an instance that outgrows it sends the batch to the host-driven loop (stat ecp_blocks_fallbacks).
+        supporting: supporting-hyperplane cuts inside the device-side loop (ktn_optimize_blocks_ex, KTN_BLOCKS_SUPPORTING); None =
+        on when the solver's cut_algo is not Kelley's and device_loop is set.  (m.last_sweep_lambdas() describes host-loop sweeps
+        only; the cuts of a device launch and their lambdas are m.blocks_cuts(k).)"""
         import numpy as np
         from .instances import atom_value_deriv
         m, big, offs = self.m, self.big, self.offs
+        if supporting is None:
+            supporting = bool(self.device_loop) and int(m.params.cut_algo) != 0
         if self._solved:
             m.reset()
         self._solved = True
-        status = m.optimize_blocks(cut_capacity) if self.device_loop else m.optimize()
+        status = m.optimize_blocks(cut_capacity, supporting=bool(supporting)) if self.device_loop else m.optimize()
         x = m.getsolution()
         common = dict(status=status, iters=m.numiters(), numcuts=None, pdhg_iters=m.stat("pdhg_iters"),
                       blk_lp_launches=m.stat("blk_lp_launches"), blk_lp_fallbacks=m.stat("blk_lp_fallbacks"),
                       blk_pdhg_iters_sum=m.stat("blk_pdhg_iters_sum"), ecp_blocks_launches=m.stat("ecp_blocks_launches"),
-                      ecp_blocks_fallbacks=m.stat("ecp_blocks_fallbacks"), ecp_blocks_pdhg_sum=m.stat("ecp_blocks_pdhg_sum"))
+                      ecp_blocks_fallbacks=m.stat("ecp_blocks_fallbacks"), ecp_blocks_pdhg_sum=m.stat("ecp_blocks_pdhg_sum"),
+                      ecp_blocks_esh_rows=m.stat("ecp_blocks_esh_rows"))
         if self._objinfo is not None:
             # each instance's objective in its own sense, from its own LIN coefficients and constant on its slice of x
             common["ecp_blocks_tape_rows"] = m.stat("ecp_blocks_tape_rows")

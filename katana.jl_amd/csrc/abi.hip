@@ -510,6 +510,16 @@ int ktn_set_blocks(ktn_handle h, int64_t nblocks, const int64_t* col_offsets) {
     })
 }
 
+// the ordinary loop from the loaded state (what a batch the device loop could not finish falls back to)
+static int ordinary_loop(Engine* e) {
+    e->reset();
+    e->begin();
+    int32_t done = (e->status == KTN_STATUS_ERROR || e->status == KTN_STATUS_UNBOUNDED) ? 1 : 0;
+    while (!done) e->step(&done);
+    e->end();
+    return e->status;
+}
+
 int ktn_optimize_blocks(ktn_handle h, int32_t cut_capacity) {
     KTN_TRY(h, {
         Engine* e = h->eng;
@@ -517,14 +527,66 @@ int ktn_optimize_blocks(ktn_handle h, int32_t cut_capacity) {
         if (e->esh_mode())
             throw ktn::Error(KTN_E_UNSUPPORTED, "ktn_optimize_blocks: not available with cut_algo = KTN_CUT_SUPPORTING");
         if (e->M != e->M_base || e->iter != 0) e->reset();
-        if (e->optimize_blocks_device(cut_capacity > 0 ? cut_capacity : 12)) return e->status;
+        if (e->optimize_blocks_device(cut_capacity > 0 ? cut_capacity : 12, 0) == Engine::kBlocksDone) return e->status;
         // an instance did not finish on the device (or the problem does not qualify): the ordinary loop, from the loaded state
-        e->reset();
-        e->begin();
-        int32_t done = (e->status == KTN_STATUS_ERROR || e->status == KTN_STATUS_UNBOUNDED) ? 1 : 0;
-        while (!done) e->step(&done);
-        e->end();
-        return e->status;
+        return ordinary_loop(e);
+    })
+}
+
+int ktn_optimize_blocks_ex(ktn_handle h, int32_t cut_capacity, int32_t flags) {
+    KTN_TRY(h, {
+        Engine* e = h->eng;
+        KTN_REQUIRE(e->loaded && e->n_blocks > 0, "ktn_optimize_blocks_ex: after ktn_loadproblem and ktn_set_blocks");
+        KTN_REQUIRE((flags & ~(KTN_BLOCKS_SUPPORTING | KTN_BLOCKS_NO_FALLBACK)) == 0, "ktn_optimize_blocks_ex: unknown flag");
+        if (e->esh_mode() && !(flags & KTN_BLOCKS_SUPPORTING))
+            throw ktn::Error(KTN_E_UNSUPPORTED, "ktn_optimize_blocks_ex: cut_algo = KTN_CUT_SUPPORTING needs KTN_BLOCKS_SUPPORTING");
+        if (e->M != e->M_base || e->iter != 0) e->reset();
+        if (e->esh_mode() && !e->esh_ready) e->esh_prepare();          // x_int: the caller's, or the auxiliary problem of the fused batch
+        const int r = e->optimize_blocks_device(cut_capacity > 0 ? cut_capacity : 12, flags);
+        if (r == Engine::kBlocksDone) return e->status;
+        if (flags & KTN_BLOCKS_NO_FALLBACK) {
+            if (r == Engine::kBlocksUnfit) throw ktn::Error(KTN_E_UNSUPPORTED, "ktn_optimize_blocks_ex: the batch does not qualify for the device-side loop");
+            return e->status;                                         // the first instance's status that is not :Optimal
+        }
+        return ordinary_loop(e);
+    })
+}
+
+// two-call size convention: out == NULL (or cap too small with out == NULL) only reports *count
+int ktn_blocks_get_results(ktn_handle h, double* out, int64_t cap, int64_t* count) {
+    KTN_TRY(h, {
+        Engine* e = h->eng;
+        KTN_REQUIRE(e->loaded && count && e->blocks_launched, "ktn_blocks_get_results: after a device launch of ktn_optimize_blocks[_ex] on the loaded problem");
+        *count = (int64_t)e->h_blkres.size();
+        if (out) {
+            KTN_REQUIRE(cap >= *count, "ktn_blocks_get_results: buffer too small");
+            std::memcpy(out, e->h_blkres.data(), e->h_blkres.size() * sizeof(double));
+        }
+        return KTN_OK;
+    })
+}
+int ktn_blocks_get_cuts(ktn_handle h, int64_t block, int64_t* rowptr, int32_t* col, double* val, double* lo, double* hi,
+                        int64_t* nl_slot, double* lambda, int64_t cap_rows, int64_t cap_nnz, int64_t* n_rows, int64_t* n_nnz) {
+    KTN_TRY(h, {
+        Engine* e = h->eng;
+        KTN_REQUIRE(e->loaded && n_rows && n_nnz && e->blocks_launched, "ktn_blocks_get_cuts: after a device launch of ktn_optimize_blocks[_ex] on the loaded problem");
+        KTN_REQUIRE(block >= 0 && block < (int64_t)e->h_ar_row0.size(), "ktn_blocks_get_cuts: no such instance");
+        std::vector<int64_t> rp, sl;
+        std::vector<int32_t> c;
+        std::vector<double> v, l, u, lm;
+        e->blocks_cuts(block, rp, c, v, l, u, sl, lm);
+        *n_rows = (int64_t)l.size();
+        *n_nnz = (int64_t)c.size();
+        if (rowptr) {
+            KTN_REQUIRE(col && val && lo && hi && nl_slot && lambda && cap_rows >= *n_rows && cap_nnz >= *n_nnz, "ktn_blocks_get_cuts: buffers missing or too small");
+            std::memcpy(rowptr, rp.data(), rp.size() * sizeof(int64_t));
+            if (!c.empty()) { std::memcpy(col, c.data(), c.size() * sizeof(int32_t)); std::memcpy(val, v.data(), v.size() * sizeof(double)); }
+            if (!l.empty()) {
+                std::memcpy(lo, l.data(), l.size() * sizeof(double)); std::memcpy(hi, u.data(), u.size() * sizeof(double));
+                std::memcpy(nl_slot, sl.data(), sl.size() * sizeof(int64_t)); std::memcpy(lambda, lm.data(), lm.size() * sizeof(double));
+            }
+        }
+        return KTN_OK;
     })
 }
 

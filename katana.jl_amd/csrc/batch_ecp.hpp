@@ -12,9 +12,20 @@
 // mirror (unscaled + scaled), row bounds, duals, diagonal scalings, scaled problem vectors.  The PDHG iterates live in
 // LDS; matrix entries stream from L2 / Infinity Cache.  Everything is deterministic: sums have a fixed order, the column
 // mirror is sorted by row after the counting-sort scatter.
+//
+// k_ecp_blocks<ESH>: ESH = 0 is Kelley's method (every cut at x*).  ESH = 1 (ktn_optimize_blocks_ex with KTN_BLOCKS_SUPPORTING;
+// DESIGN.md section 11 "In the device-side loop") moves the cut of every violated row that takes part to the point where the
+// segment from the interior point x_int to x* leaves the row: separable rows by the bracketed Newton of esh.hpp (esh_init /
+// esh_step / esh_point, 16 lanes per row), KTN_ROW_QUAD rows by the closed form of esh_quad.hpp (esh_quad_root).  TAPE ROWS KEEP
+// KELLEY'S CUT, bit for bit, and are counted as fallback rows: a search pass there is a whole interpreter run by a single lane.
+// The stop rule, the largest violation, yts[i], the objective certificate and the refinement passes keep the values at x*; a row
+// with sig == 0 or without a finite phi >= 0 below lambda = 1 stores exactly what ESH = 0 stores.  The switch is a template
+// parameter, not a field of EcpBatch: the kernel is sensitive to register allocation (see the note at the sweep), and
+// k_ecp_blocks<0> is the code and the kernel argument that were there before the switch existed.
 #pragma once
 #include "kernels.hpp"
 #include "quad_rows.hpp"
+#include "esh_quad.hpp"
 
 namespace ktn {
 
@@ -60,6 +71,21 @@ struct EcpBatch {
     double cert_tol;                 // obj_cert_tol: per-instance objective certificate (below); 0 = stop at the reference's rule alone
     int iter_cap, lp_max_iter, check_every, near_chunk, ruiz_iters, power_passes, nmax, mmax, polish_max_iter;
 };
+// EcpBatch::res, eight slots per instance: 0 status, 1 cutting-plane iterations, 2 objective, 3 cuts (linear rows counted), 4 PDHG
+// iterations, 5 largest violation of the last sweep, 6 LP rows at the end, 7 arena overflow (0 / 1)  (include/katana_hip.h,
+// ktn_blocks_get_results)
+
+// What k_ecp_blocks<1> takes beside the batch
+struct EcpEsh {
+    const double* xint;              // [ncols_total] x_int (global column indexing: the engine's d_xint)
+    const int8_t* sig;               // per global row: the side of a row that takes part, else 0 (d_esh_sig)
+    const double* jint;              // Jacobian at x_int by Jacobian entry (d_jint); NULL: no QUAD row takes part
+    double* lam;                     // arena, per row slot: lambda of the cut row (1: Kelley's cut)
+    double* res;                     // [nb * 4] out: rows moved, fallback rows, search passes, QUAD rows moved
+    double root_tol;                 // esh_root_tol: a search stops at 0 <= phi <= root_tol * (the sweep's f_tol)
+    int iters;                       // esh_root_iters
+};
+__device__ __forceinline__ const EcpEsh& ecp_esh_arg(const EcpEsh& e) { return e; }
 
 // ---------------------------------------------------------------------------------------------------------------------
 template <int NQ>
@@ -157,7 +183,11 @@ static __device__ __forceinline__ void ecp_quad_entries(const EcpBatch& B, int64
     }
 }
 
-static __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B) {
+// k_ecp_blocks<0>(EcpBatch) and k_ecp_blocks<1, EcpEsh>(EcpBatch, EcpEsh): the second argument exists only for ESH = 1 (wrapping
+// both into one struct changed the code of <0>: 40 bytes and three more SGPR spills; the empty pack leaves it as it was)
+template <int ESH, class... EshArg>
+__global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B, EshArg... esh_arg) {
+    static_assert(sizeof...(EshArg) == (ESH != 0 ? 1 : 0), "k_ecp_blocks<0>(EcpBatch) or k_ecp_blocks<1, EcpEsh>(EcpBatch, EcpEsh)");
     extern __shared__ double sm[];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int64_t c0 = B.blk_col[b];
@@ -222,6 +252,7 @@ static __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B) {
     double f_eff = B.f_tol, gap_cert = 1e300, best_viol = 1e300, best_obj = 0.0;
     int passes = 0;
     bool refining = false;
+    int esh_cnt[4] = {0, 0, 0, 0};                // (ESH) lane 0 of a row's group: rows moved, fallback rows, search passes, QUAD rows moved
   for (;;) {
     const double floor_p = B.tol_floor * f_eff;
 
@@ -679,12 +710,94 @@ static __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B) {
                 const int dst = rptr[rnew];
                 // (tape and QUAD rows: the eval pass left their entries in B.jac)
                 const bool in_jac = (B.has_tape && B.P.row_kind[gr] == KTN_ROW_TAPE) || (B.has_quad && B.P.row_kind[gr] == KTN_ROW_QUAD);
+                // (ESH) the cut point x_int + lamc (x* - x_int) and g there; lamc == 1: Kelley's cut, the loop below as it ever was.
+                // gr, sg and the row's kind are uniform within the 16 lanes, and so is every trip count below.
+                double lamc = 1.0, gcut = 0.0;
+                bool qmoved = false;
+                if constexpr (ESH != 0) {
+                    const EcpEsh& E = ecp_esh_arg(esh_arg...);
+                    const int sg = (int)E.sig[gr];
+                    const double* xi = E.xint + c0;
+                    const double tol = E.root_tol * f_eff;
+                    if (sg != 0 && !in_jac) {
+                        // separable row: the bracketed Newton of esh.hpp on phi(lambda) = sg (g(x_int + lambda (x* - x_int)) - bound)
+                        const double bound = sg > 0 ? B.P.ub[gr] : B.P.lb[gr];
+                        const double rc = B.P.rconst[gr];
+                        EshState S;
+                        esh_init(S);
+                        int np = 0;
+                        for (int it = 0; it < E.iters && !S.done; ++it) {
+                            const double lam = S.lam;
+                            RowAcc acc;
+                            double acc_d = 0.0;
+                            for (int64_t e = beg + lane; e < end; e += 16) {
+                                const int ck = B.P.colk[e];
+                                const double2 pp = B.P.pp[e];
+                                const int cl = (ck & kColMask) - (int)c0;
+                                const double xv = xs[cl], x0 = xi[cl];
+                                const double xp = esh_point(xv, x0, lam);
+                                double val, der;
+                                atom_eval((unsigned)ck >> kKindShift, pp.x, pp.y, xp, val, der);
+                                acc.add(val, der, xp);
+                                acc_d += der * (xv - x0);
+                            }
+                            acc.template reduce<16>();
+                            acc_d = group_sum<16>(acc_d);
+                            const double g = acc.g + rc;
+                            const double phi = sg * (g - bound);
+                            ++np;
+                            if (esh_step(S, phi, sg * acc_d, !acc.nf && isfinite(phi), tol)) gcut = g;
+                        }
+                        if (S.have) lamc = S.best;
+                        if (lane == 0) esh_cnt[2] += np;
+                    } else if (sg != 0 && E.jint != nullptr && B.has_quad && B.P.row_kind[gr] == KTN_ROW_QUAD) {
+                        // QUAD row: the closed form of esh_quad.hpp from J* (B.jac, ecp_quad_entries), J0 (jint) and g* (yts[i])
+                        double p1 = 0.0, p0 = 0.0;
+                        int nfq = 0;
+                        for (int64_t e = beg + lane; e < end; e += 16) {
+                            const int cl = (B.P.colk[e] & kColMask) - (int)c0;
+                            const double js = B.jac[e], j0 = E.jint[e];
+                            const double d = xs[cl] - xi[cl];
+                            p1 += js * d;
+                            p0 += j0 * d;
+                            nfq |= !(isfinite(js) && isfinite(j0) && isfinite(d));
+                        }
+                        p1 = group_sum<16>(p1);
+                        p0 = group_sum<16>(p0);
+                        nfq = group_or<16>(nfq);
+                        const double gs = yts[i];
+                        const EshQuadRoot R = esh_quad_root(true, sg, gs, sg > 0 ? B.P.ub[gr] : B.P.lb[gr], tol, p1, p0, nfq);
+                        if (R.moved) { lamc = R.lam; gcut = esh_quad_gb(gs, R.lam, p1, R.q); qmoved = true; }
+                        if (lane == 0) esh_cnt[2] += 1;
+                    }
+                    if (lane == 0) { esh_cnt[lamc < 1.0 ? 0 : 1] += 1; if (qmoved) esh_cnt[3] += 1; }
+                }
+                const bool moved = ESH != 0 && lamc < 1.0;
                 double dot = 0.0, mx = -__builtin_inf();
                 int nf = 0;
                 for (int64_t e = beg + lane; e < end; e += 16) {
                     const int ck = B.P.colk[e];
                     const int cl = (ck & kColMask) - (int)c0;
                     double der;
+                    if constexpr (ESH != 0) {
+                        if (moved) {
+                            const EcpEsh& E = ecp_esh_arg(esh_arg...);
+                            const double xp = esh_point(xs[cl], E.xint[c0 + cl], lamc);
+                            if (qmoved) {
+                                der = esh_quad_coef(lamc, B.jac[e], E.jint[e]);
+                            } else {
+                                const double2 pp = B.P.pp[e];
+                                double val;
+                                atom_eval((unsigned)ck >> kKindShift, pp.x, pp.y, xp, val, der);
+                            }
+                            dot += xp * der;
+                            mx = nanmax(mx, der);
+                            nf |= !isfinite(der);
+                            rcol[dst + (int)(e - beg)] = (uint16_t)cl;
+                            rval[dst + (int)(e - beg)] = der;
+                            continue;
+                        }
+                    }
                     if (in_jac) {
                         der = B.jac[e];
                     } else {
@@ -707,7 +820,8 @@ static __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B) {
                     if (round_coef(der, mx, B.cut_coef_rng)) rval[dst + (int)(e - beg)] = 0.0;
                 }
                 if (lane == 0) {
-                    const double bconst = yts[i] - dot;
+                    const double bconst = (moved ? gcut : yts[i]) - dot;
+                    if constexpr (ESH != 0) ecp_esh_arg(esh_arg...).lam[A.row0 + rnew] = lamc;
                     lo[rnew] = B.P.lb[gr] - bconst;
                     hi[rnew] = B.P.ub[gr] - bconst;
                     const int prev = last_cut[i];
@@ -780,6 +894,12 @@ static __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B) {
         double* o = B.res + (int64_t)b * 8;
         o[0] = (double)status; o[1] = (double)iter; o[2] = objval; o[3] = (double)numcuts; o[4] = (double)pdhg_total;
         o[5] = last_maxviol; o[6] = (double)M; o[7] = overflow ? 1.0 : 0.0;
+    }
+    if constexpr (ESH != 0) {                                                       // each workgroup owns its four counters
+        double c4[4] = {(double)esh_cnt[0], (double)esh_cnt[1], (double)esh_cnt[2], (double)esh_cnt[3]};
+        __syncthreads();
+        ecp_reduce<4>(c4, 4, red, q);
+        if (tid < 4) ecp_esh_arg(esh_arg...).res[(int64_t)b * 4 + tid] = q[tid];
     }
 }
 

@@ -7,16 +7,21 @@
 
 namespace ktn {
 
-// Throughput mode, device-side loop (batch_ecp.hpp).  Returns false when the problem does not qualify or an instance
-// could not finish (arena overflow, LP status): the caller then runs the ordinary loop.
-bool Engine::optimize_blocks_device(int cap_mul) {
+// Throughput mode, device-side loop (batch_ecp.hpp).  Returns kBlocksUnfit when the problem does not qualify (nothing launched),
+// kBlocksOpen when an instance could not finish (arena overflow, LP status) -- the caller then runs the ordinary loop, or with
+// KTN_BLOCKS_NO_FALLBACK reports the first such instance's status -- and kBlocksDone when every instance ended :Optimal.
+// KTN_BLOCKS_SUPPORTING with an interior point in hand launches k_ecp_blocks<1> (the root search inside the emit pass), everything
+// else k_ecp_blocks<0>.
+int Engine::optimize_blocks_device(int cap_mul, int flags) {
+    const bool keep = (flags & KTN_BLOCKS_NO_FALLBACK) != 0;
+    const bool esh = (flags & KTN_BLOCKS_SUPPORTING) != 0 && esh_mode() && xint_found != 0;
     // (rows: separable, tape or QUAD, linear or not; k_ecp_blocks evaluates tape rows with the interpreter of k_tape_eval and QUAD
     //  rows with the two passes of quad_rows.hpp.  A handle whose OBJECTIVE row is KTN_ROW_QUAD -- a hand-fused QuadNLP; nlp.fuse_problems
     //  always emits a separable objective of LIN atoms -- keeps the ordinary loop: include/katana_hip.h, ktn_optimize_blocks)
-    if (n_blocks <= 0 || !obj_linear || sense != KTN_MIN || has_inf_bound || n_host > 0 || prm.vis_data) return false;
-    if (h_rowkind[(size_t)(m_ext - 1)] == KTN_ROW_QUAD) return false;
+    if (n_blocks <= 0 || !obj_linear || sense != KTN_MIN || has_inf_bound || n_host > 0 || prm.vis_data) return kBlocksUnfit;
+    if (h_rowkind[(size_t)(m_ext - 1)] == KTN_ROW_QUAD) return kBlocksUnfit;
     for (int64_t i = 0; i < m_ext - 1; ++i)
-        if (h_rowkind[(size_t)i] != KTN_ROW_SEP && h_rowkind[(size_t)i] != KTN_ROW_TAPE && h_rowkind[(size_t)i] != KTN_ROW_QUAD) return false;
+        if (h_rowkind[(size_t)i] != KTN_ROW_SEP && h_rowkind[(size_t)i] != KTN_ROW_TAPE && h_rowkind[(size_t)i] != KTN_ROW_QUAD) return kBlocksUnfit;
     const int nb = (int)n_blocks;
     auto block_of_col = [&](int64_t c) { return (int)(std::upper_bound(h_blkcol.begin(), h_blkcol.end(), c) - h_blkcol.begin()) - 1; };
     // linear rows of the loaded LP (in original row order) and NL slots must be grouped by instance, instance after instance
@@ -28,14 +33,14 @@ bool Engine::optimize_blocks_device(int cap_mul) {
         for (auto r : h_nlrows) if (r < m0) is_nl[(size_t)r] = 1;
         for (int64_t i = 0; i < m0; ++i) if (!is_nl[(size_t)i]) lin_rows.push_back(i);
     }
-    if ((int64_t)lin_rows.size() != M_base) return false;
+    if ((int64_t)lin_rows.size() != M_base) return kBlocksUnfit;
     int prev = 0;
     for (size_t k = 0; k < lin_rows.size(); ++k) {
         const int64_t r = lin_rows[k];
-        if (h_rowptr[r + 1] == h_rowptr[r]) return false;
+        if (h_rowptr[r + 1] == h_rowptr[r]) return kBlocksUnfit;
         const int bb = block_of_col(h_col[(size_t)h_rowptr[r]]);
-        if (bb < prev || bb >= nb) return false;
-        for (int64_t e = h_rowptr[r]; e < h_rowptr[r + 1]; ++e) if (block_of_col(h_col[(size_t)e]) != bb) return false;
+        if (bb < prev || bb >= nb) return kBlocksUnfit;
+        for (int64_t e = h_rowptr[r]; e < h_rowptr[r + 1]; ++e) if (block_of_col(h_col[(size_t)e]) != bb) return kBlocksUnfit;
         prev = bb;
         blk_lin[(size_t)bb + 1] += 1;
         nnz_lin[(size_t)bb] += h_rowptr[r + 1] - h_rowptr[r];
@@ -43,15 +48,15 @@ bool Engine::optimize_blocks_device(int cap_mul) {
     prev = 0;
     for (size_t k = 0; k < h_nlrows.size(); ++k) {
         const int64_t r = h_nlrows[k];
-        if (h_rowptr[r + 1] == h_rowptr[r]) return false;
+        if (h_rowptr[r + 1] == h_rowptr[r]) return kBlocksUnfit;
         const int bb = block_of_col(h_col[(size_t)h_rowptr[r]]);
-        if (bb < prev || bb >= nb) return false;
-        for (int64_t e = h_rowptr[r]; e < h_rowptr[r + 1]; ++e) if (block_of_col(h_col[(size_t)e]) != bb) return false;
+        if (bb < prev || bb >= nb) return kBlocksUnfit;
+        for (int64_t e = h_rowptr[r]; e < h_rowptr[r + 1]; ++e) if (block_of_col(h_col[(size_t)e]) != bb) return kBlocksUnfit;
         prev = bb;
         blk_nl[(size_t)bb + 1] += 1;
         nnz_nl[(size_t)bb] += h_rowptr[r + 1] - h_rowptr[r];
         if (h_rowkind[(size_t)r] == KTN_ROW_QUAD) {
-            if (k > 0 && h_nlrows[k - 1] >= r) return false;           // (the launch list is in row order: so must the slots be)
+            if (k > 0 && h_nlrows[k - 1] >= r) return kBlocksUnfit;           // (the launch list is in row order: so must the slots be)
             blk_qrow[(size_t)bb + 1] += 1;
             blk_qent[(size_t)bb + 1] += h_rowptr[r + 1] - h_rowptr[r];
         }
@@ -60,7 +65,7 @@ bool Engine::optimize_blocks_device(int cap_mul) {
         blk_lin[(size_t)bb + 1] += blk_lin[(size_t)bb]; blk_nl[(size_t)bb + 1] += blk_nl[(size_t)bb];
         blk_qrow[(size_t)bb + 1] += blk_qrow[(size_t)bb]; blk_qent[(size_t)bb + 1] += blk_qent[(size_t)bb];
     }
-    if (blk_qrow[(size_t)nb] != n_quad_nl || blk_qent[(size_t)nb] != n_quad_ent_nl) return false;
+    if (blk_qrow[(size_t)nb] != n_quad_nl || blk_qent[(size_t)nb] != n_quad_ent_nl) return kBlocksUnfit;
     // arenas
     std::vector<EcpArena> ar((size_t)nb);
     int64_t row_tot = 0, nnz_tot = 0;
@@ -77,7 +82,7 @@ bool Engine::optimize_blocks_device(int cap_mul) {
     }
     const size_t lds = (size_t)(3 * blk_nmax + 3 * mmax + (kEcpThreads / 64) * kEcpQ + kEcpQ + 8 + 16) * sizeof(double) +
                        (size_t)(std::max(blk_nmax, mmax) + 4) * sizeof(int32_t);
-    if (lds > 158 * 1024 || blk_nmax > 65535 || mmax > 65535) return false;      // 16-bit local indices in the arenas
+    if (lds > 158 * 1024 || blk_nmax > 65535 || mmax > 65535) return kBlocksUnfit;      // 16-bit local indices in the arenas
     t_start = std::chrono::steady_clock::now();
     d_ar.upload(ar, stream); d_blklin.upload(blk_lin, stream); d_blknl.upload(blk_nl, stream);
     e_rptr.resize((size_t)row_tot + nb + 1, stream);
@@ -89,6 +94,18 @@ bool Engine::optimize_blocks_device(int cap_mul) {
     e_last.resize((size_t)std::max<int64_t>(m_nl, 1), stream);
     e_prev.resize((size_t)row_tot + 1, stream); e_ax.resize((size_t)row_tot + 1, stream);
     e_res.resize((size_t)nb * 8, stream);
+    h_ar_row0.resize((size_t)nb); h_ar_nnz0.resize((size_t)nb); h_ar_rows.resize((size_t)nb);      // (ktn_blocks_get_cuts reads the arenas of this launch)
+    for (int bb = 0; bb < nb; ++bb) { h_ar_row0[(size_t)bb] = ar[(size_t)bb].row0; h_ar_nnz0[(size_t)bb] = ar[(size_t)bb].nnz0; h_ar_rows[(size_t)bb] = ar[(size_t)bb].cap_rows; }
+    h_blklin = blk_lin; h_blknl = blk_nl;
+    blocks_launched = false; blocks_last_esh = esh;
+    EcpEsh E{};
+    if (esh) {
+        e_lam.resize((size_t)row_tot + 1, stream);
+        e_res2.resize((size_t)nb * 4, stream);
+        E.xint = d_xint.p; E.sig = d_esh_sig.p; E.jint = esh_n_quad_part > 0 ? d_jint.p : nullptr;
+        E.lam = e_lam.p; E.res = e_res2.p;
+        E.root_tol = prm.esh_root_tol; E.iters = prm.esh_root_iters;
+    }
     EcpBatch B;
     B.blk_col = d_blkcol.p; B.blk_lin = d_blklin.p; B.blk_nl = d_blknl.p;
     B.lp_rowptr = lp_rowptr.p; B.lp_col = lp_col.p; B.lp_val = lp_val.p; B.lp_lo = lp_lo.p; B.lp_hi = lp_hi.p;
@@ -122,19 +139,38 @@ bool Engine::optimize_blocks_device(int cap_mul) {
     B.check_every = std::min(B.check_every, 24);
     B.near_chunk = prm.lp_near_check; B.ruiz_iters = prm.lp_ruiz_iters; B.nmax = blk_nmax; B.mmax = mmax;
     B.power_passes = dev.ecp_power;
-    if (lds > lds_set_ecp) {
-        KTN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ecp_blocks), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        lds_set_ecp = lds;
-    }
     // the loaded state: M == M_base rows (the linear rows), as after reset()
-    hipLaunchKernelGGL(k_ecp_blocks, dim3((unsigned)nb), dim3(kEcpThreads), lds, stream, B);
+    if (esh) {
+        if (lds > lds_set_ecp_esh) {
+            KTN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ecp_blocks<1, EcpEsh>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            lds_set_ecp_esh = lds;
+        }
+        hipLaunchKernelGGL((k_ecp_blocks<1, EcpEsh>), dim3((unsigned)nb), dim3(kEcpThreads), lds, stream, B, E);
+    } else {
+        if (lds > lds_set_ecp) {
+            KTN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ecp_blocks<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            lds_set_ecp = lds;
+        }
+        hipLaunchKernelGGL(k_ecp_blocks<0>, dim3((unsigned)nb), dim3(kEcpThreads), lds, stream, B);
+    }
     check_launch();
     std::vector<double> res = e_res.to_host(stream);
+    blocks_launched = true;
+    h_blkres = res;
+    stats["ecp_blocks_esh_rows"] = 0.0;
+    if (esh) {                                                  // the instances' counters: rows moved, fallback rows, passes, QUAD rows moved
+        const std::vector<double> r2 = e_res2.to_host(stream);
+        double c[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int bb = 0; bb < nb; ++bb) for (int k = 0; k < 4; ++k) c[k] += r2[(size_t)bb * 4 + k];
+        stats["esh_rows"] += c[0]; stats["esh_fallback_rows"] += c[1]; stats["esh_newton_steps"] += c[2]; stats["esh_quad_rows"] += c[3];
+        stats["ecp_blocks_esh_rows"] = c[0];
+    }
     bool ok = true;
+    int first_open = KTN_STATUS_OPTIMAL;
     double obj = 0.0, it_max = 0.0, cuts = 0.0, pd = 0.0, rows = 0.0;
     for (int bb = 0; bb < nb; ++bb) {
         const double* o = res.data() + (size_t)bb * 8;
-        if ((int)o[0] != KTN_STATUS_OPTIMAL) ok = false;
+        if ((int)o[0] != KTN_STATUS_OPTIMAL) { if (ok) first_open = (int)o[0]; ok = false; }
         obj += o[2]; it_max = std::max(it_max, o[1]); cuts += o[3]; pd += o[4]; rows += o[6];
     }
     if (dev.debug_blocks) {
@@ -156,11 +192,49 @@ bool Engine::optimize_blocks_device(int cap_mul) {
     stats["ecp_blocks_rows"] = rows;
     stats["ecp_blocks_tape_rows"] = (double)n_tape_nl;
     stats["ecp_blocks_quad_rows"] = (double)n_quad_nl;
-    if (!ok) { stats["ecp_blocks_fallbacks"] += 1.0; return false; }
-    status = KTN_STATUS_OPTIMAL; lp_status = KTN_STATUS_OPTIMAL;
-    iter = (int64_t)it_max; numcuts = (int64_t)cuts; objval = obj + c0; allsat = true;
+    if (!ok && !keep) { stats["ecp_blocks_fallbacks"] += 1.0; return kBlocksOpen; }
+    status = ok ? KTN_STATUS_OPTIMAL : first_open; lp_status = KTN_STATUS_OPTIMAL;
+    iter = (int64_t)it_max; numcuts = (int64_t)cuts; objval = obj + c0; allsat = ok;
     soltime = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
-    return true;
+    return ok ? kBlocksDone : kBlocksOpen;
+}
+
+// ktn_blocks_get_cuts: the cut rows of instance `block` in the arenas of the last device launch
+void Engine::blocks_cuts(int64_t block, std::vector<int64_t>& rowptr, std::vector<int32_t>& col, std::vector<double>& val,
+                         std::vector<double>& lo, std::vector<double>& hi, std::vector<int64_t>& slot, std::vector<double>& lam) {
+    struct { int64_t row0, nnz0, cap_rows; } a{h_ar_row0[(size_t)block], h_ar_nnz0[(size_t)block], h_ar_rows[(size_t)block]};
+    const int64_t c0 = h_blkcol[(size_t)block];
+    const int64_t m_lin = h_blklin[(size_t)block + 1] - h_blklin[(size_t)block];
+    const int64_t nl0 = h_blknl[(size_t)block], m_nl = h_blknl[(size_t)block + 1] - nl0;
+    const int64_t Mb = std::min<int64_t>((int64_t)h_blkres[(size_t)block * 8 + 6], a.cap_rows);
+    const int64_t nc = std::max<int64_t>(Mb - m_lin, 0);
+    rowptr.assign((size_t)nc + 1, 0); lo.assign((size_t)nc, 0.0); hi.assign((size_t)nc, 0.0); slot.assign((size_t)nc, -1); lam.assign((size_t)nc, 1.0);
+    col.clear(); val.clear();
+    if (nc == 0) return;
+    std::vector<int32_t> rp((size_t)nc + 1), prev((size_t)nc), last((size_t)std::max<int64_t>(m_nl, 1), -1);
+    auto fetch = [&](auto* host, const auto* devp, size_t count) {
+        if (count) KTN_HIP(hipMemcpyAsync(host, devp, count * sizeof(*host), hipMemcpyDeviceToHost, stream));
+    };
+    fetch(rp.data(), e_rptr.p + (a.row0 + block + m_lin), rp.size());
+    fetch(lo.data(), e_lo.p + (a.row0 + m_lin), (size_t)nc);
+    fetch(hi.data(), e_hi.p + (a.row0 + m_lin), (size_t)nc);
+    fetch(prev.data(), e_prev.p + (a.row0 + m_lin), (size_t)nc);
+    if (m_nl > 0) fetch(last.data(), e_last.p + nl0, (size_t)m_nl);
+    if (blocks_last_esh) fetch(lam.data(), e_lam.p + (a.row0 + m_lin), (size_t)nc);
+    sync();
+    const int64_t e0 = rp[0], ne = rp[(size_t)nc] - e0;
+    std::vector<uint16_t> lc((size_t)std::max<int64_t>(ne, 1));
+    val.assign((size_t)ne, 0.0); col.assign((size_t)ne, 0);
+    if (ne > 0) {
+        fetch(lc.data(), e_rcol.p + (a.nnz0 + e0), (size_t)ne);
+        fetch(val.data(), e_rval.p + (a.nnz0 + e0), (size_t)ne);
+        sync();
+    }
+    for (int64_t k = 0; k <= nc; ++k) rowptr[(size_t)k] = rp[(size_t)k] - e0;
+    for (int64_t k = 0; k < ne; ++k) col[(size_t)k] = (int32_t)(c0 + lc[(size_t)k]);
+    // the NL slot of every cut: walk each slot's list (newest first) through last_cut / cut_prev
+    for (int64_t i = 0; i < m_nl; ++i)
+        for (int32_t r = last[(size_t)i]; r >= m_lin && r < Mb; r = prev[(size_t)(r - m_lin)]) slot[(size_t)(r - m_lin)] = nl0 + i;
 }
 
 // boundroutine  src/model.jl:175-197 with the ray in d_ray

@@ -329,7 +329,16 @@ struct Engine {
     DBuf<double> d_blkomega, d_blkres;
     int blk_nmax = 0, blk_mmax = 0;
     void build_blocks();
-    bool optimize_blocks_device(int cap_mul);
+    enum { kBlocksUnfit = 0, kBlocksDone = 1, kBlocksOpen = 2 };      // optimize_blocks_device: not launched / all :Optimal / some instance not
+    int optimize_blocks_device(int cap_mul, int flags);
+    // the last device launch on the loaded problem, for ktn_blocks_get_results / ktn_blocks_get_cuts
+    bool blocks_launched = false, blocks_last_esh = false;
+    std::vector<int64_t> h_ar_row0, h_ar_nnz0, h_ar_rows, h_blklin, h_blknl;      // arena offsets and row capacities, offsets of linear rows / NL slots
+    std::vector<double> h_blkres;
+    DBuf<double> e_lam, e_res2;                   // k_ecp_blocks<1>: lambda per arena row slot, four counters per instance
+    size_t lds_set_ecp_esh = 0;
+    void blocks_cuts(int64_t block, std::vector<int64_t>& rowptr, std::vector<int32_t>& col, std::vector<double>& val,
+                     std::vector<double>& lo, std::vector<double>& hi, std::vector<int64_t>& slot, std::vector<double>& lam);
     DBuf<EcpArena> d_ar;                          // arenas of the device-side loop
     DBuf<int64_t> d_blklin, d_blknl, d_blkqrow, d_blkqent;
     DBuf<int32_t> e_rptr, e_cptr, e_last, e_prev;

@@ -23,6 +23,26 @@
 
 namespace ktn {
 
+// The scalar part, shared by k_esh_quad and the device-side batch loop (k_ecp_blocks<1> of batch_ecp.hpp): the root from the row's
+// two directional derivatives, the move conditions, and g at the cut point.  Every lane of a row's group runs it on the same numbers.
+struct EshQuadRoot { double lam, q; bool moved; };
+__device__ __forceinline__ EshQuadRoot esh_quad_root(bool live, int sg, double gs, double bound, double tol, double p1, double p0, int nf) {
+    const double q = p1 - p0;
+    const double phi1 = sg * (gs - bound);
+    const double c = phi1 - 0.5 * tol;
+    const double sp1 = sg * p1, sq = sg * q;
+    const double disc = sp1 * sp1 - 2.0 * sq * c;
+    const double mu = 2.0 * c / (sp1 + sqrt(disc));
+    const double lam = 1.0 - mu;
+    const bool fin = !nf && isfinite(p1) && isfinite(p0) && isfinite(gs) && isfinite(c) && isfinite(disc) && isfinite(mu);
+    const bool moved = live && fin && sq >= 0.0 && sp1 > 0.0 && disc >= 0.0 && c > 0.0 && lam > 0.0 && lam < 1.0;
+    return EshQuadRoot{lam, q, moved};
+}
+__device__ __forceinline__ double esh_quad_gb(double gs, double lam, double p1, double q) {
+    const double m2 = 1.0 - lam;
+    return gs - m2 * p1 + 0.5 * (m2 * m2) * q;
+}
+
 template <int G>
 __global__ __launch_bounds__(kBlock) void k_esh_quad(NlpDev P, QuadList L, const int64_t* __restrict__ flag,
                                                      const double* __restrict__ jint, EshArgs A, SweepOut O) {
@@ -50,17 +70,11 @@ __global__ __launch_bounds__(kBlock) void k_esh_quad(NlpDev P, QuadList L, const
     p0 = group_sum<G>(p0);
     nf = group_or<G>(nf);
     // the root, in registers (every lane of the group on the same numbers)
-    const double q = p1 - p0;
     const double gs = live ? O.g[r] : 0.0;
     const double bound = sg > 0 ? P.ub[r] : (sg < 0 ? P.lb[r] : 0.0);
-    const double phi1 = sg * (gs - bound);
-    const double c = phi1 - 0.5 * A.tol;
-    const double sp1 = sg * p1, sq = sg * q;
-    const double disc = sp1 * sp1 - 2.0 * sq * c;
-    const double mu = 2.0 * c / (sp1 + sqrt(disc));
-    const double lam = 1.0 - mu;
-    const bool fin = !nf && isfinite(p1) && isfinite(p0) && isfinite(gs) && isfinite(c) && isfinite(disc) && isfinite(mu);
-    const bool moved = live && fin && sq >= 0.0 && sp1 > 0.0 && disc >= 0.0 && c > 0.0 && lam > 0.0 && lam < 1.0;
+    const EshQuadRoot R = esh_quad_root(live, sg, gs, bound, A.tol, p1, p0, nf);
+    const double lam = R.lam;
+    const bool moved = R.moved;
     // pass 2 (moved rows; the others run an empty range): the cut at x_b
     const int64_t beg2 = moved ? beg : 0, end2 = moved ? end : 0;
     double dot = 0.0, mx = -__builtin_inf();
@@ -76,8 +90,7 @@ __global__ __launch_bounds__(kBlock) void k_esh_quad(NlpDev P, QuadList L, const
     mx = group_nanmax<G>(mx);
     if (lane == 0 && live) {
         if (moved) {
-            const double m2 = 1.0 - lam;
-            const double gb = gs - m2 * p1 + 0.5 * (m2 * m2) * q;
+            const double gb = esh_quad_gb(gs, lam, p1, R.q);
             A.lam[r] = lam;
             O.bconst[r] = gb - dot;
             O.maxc[r] = P.pad_zero[r] ? nanmax(mx, 0.0) : mx;

@@ -200,9 +200,43 @@ class KatanaNonlinearModel:
         off = np.ascontiguousarray(col_offsets, dtype=np.int64)
         L.check(self._h, self._lib.ktn_set_blocks(self._h, len(off) - 1, _p(off, C.c_int64)))
 
-    def optimize_blocks(self, cut_capacity=0):
-        """optimize! of a block-diagonal batch with every instance's whole loop in its own workgroup (ktn_optimize_blocks)"""
-        return STATUS_SYMBOLS[L.check(self._h, self._lib.ktn_optimize_blocks(self._h, int(cut_capacity)))]
+    def optimize_blocks(self, cut_capacity=0, supporting=False, fallback=True):
+        """optimize! of a block-diagonal batch with every instance's whole loop in its own workgroup (ktn_optimize_blocks).
+        supporting: cut_algo "supporting_hyperplane[_quad]" runs inside the device-side loop (KTN_BLOCKS_SUPPORTING; tape rows keep
+        Kelley's cut there); without it such a handle is refused.  fallback=False (KTN_BLOCKS_NO_FALLBACK): return after the device
+        launch with the first status that is not "Optimal" instead of running the ordinary loop.  With both keywords at their
+        defaults the call is ktn_optimize_blocks itself, otherwise ktn_optimize_blocks_ex.  last_sweep_lambdas() keeps describing the
+        sweeps of the host-driven loop only; the lambdas of a device launch come from blocks_cuts()."""
+        if not supporting and fallback:
+            return STATUS_SYMBOLS[L.check(self._h, self._lib.ktn_optimize_blocks(self._h, int(cut_capacity)))]
+        flags = (L.BLOCKS_SUPPORTING if supporting else 0) | (0 if fallback else L.BLOCKS_NO_FALLBACK)
+        return STATUS_SYMBOLS[L.check(self._h, self._lib.ktn_optimize_blocks_ex(self._h, int(cut_capacity), flags))]
+
+    BLOCKS_RESULT_FIELDS = ("status", "iters", "objval", "numcuts", "pdhg_iters", "max_viol", "lp_rows", "overflow")
+
+    def blocks_results(self):
+        """[n_blocks, 8] records of the last device launch (ktn_blocks_get_results; columns: BLOCKS_RESULT_FIELDS, the status as its
+        KTN_STATUS_* code)"""
+        n = C.c_int64(0)
+        L.check(self._h, self._lib.ktn_blocks_get_results(self._h, C.POINTER(C.c_double)(), 0, C.byref(n)))
+        out = np.zeros(max(n.value, 1))
+        L.check(self._h, self._lib.ktn_blocks_get_results(self._h, _p(out), len(out), C.byref(n)))
+        return out[:n.value].reshape(-1, 8)
+
+    def blocks_cuts(self, block):
+        """the cut rows of instance `block` in its arena after the last device launch (ktn_blocks_get_cuts): dict(rowptr, col --
+        global columns --, val, lo, hi, slot -- position in the engine's NL row list --, lam -- 1 for a cut at x* itself)"""
+        nr, nz = C.c_int64(0), C.c_int64(0)
+        null = lambda t: C.POINTER(t)()
+        L.check(self._h, self._lib.ktn_blocks_get_cuts(self._h, int(block), null(C.c_int64), null(C.c_int32), null(C.c_double), null(C.c_double),
+                                                       null(C.c_double), null(C.c_int64), null(C.c_double), 0, 0, C.byref(nr), C.byref(nz)))
+        rows, nnz = nr.value, nz.value
+        rowptr, col, val = np.zeros(rows + 1, dtype=np.int64), np.zeros(max(nnz, 1), dtype=np.int32), np.zeros(max(nnz, 1))
+        lo, hi, lam = np.zeros(max(rows, 1)), np.zeros(max(rows, 1)), np.zeros(max(rows, 1))
+        slot = np.zeros(max(rows, 1), dtype=np.int64)
+        L.check(self._h, self._lib.ktn_blocks_get_cuts(self._h, int(block), _p(rowptr, C.c_int64), _p(col, C.c_int32), _p(val), _p(lo), _p(hi),
+                                                       _p(slot, C.c_int64), _p(lam), rows, nnz, C.byref(nr), C.byref(nz)))
+        return dict(rowptr=rowptr, col=col[:nnz], val=val[:nnz], lo=lo[:rows], hi=hi[:rows], slot=slot[:rows], lam=lam[:rows])
 
     def stat(self, name):
         return float(self._lib.ktn_get_stat(self._h, name.encode()))

@@ -8,9 +8,17 @@
                   (where its auxiliary problem finds one), and one QCQP of 200 rows 1/2 x'Q_i x <= 1 on 16 of 2 000 columns each
                   (the rows of tools/quad_bench.py), interior point 0, against the Kelley run's objective
 
+  batch           throughput mode (only when asked for by name): 512 x make_config("cfg5_one", seed = s) as ONE fused batch in the
+                  device-side loop (FusedBatch), Kelley against supporting hyperplanes inside the loop -- once with the engine's own
+                  interior point (the auxiliary problem of the fused batch, solved by the host-driven loop) and once with a caller's
+                  point (the point the engine found, read back and handed over per instance: what a caller who solves the same
+                  constraint sets again would keep).  solve() after a warm-up solve, `reps` times per variant, the variants alternating;
+                  per line: solve seconds (median, min, max), seconds to find x_int, per-instance rounds (median, max), PDHG iterations
+                  (sum, max), ecp_blocks_fallbacks, the worst objective error against the planted values
+
 Each line: status, ECP rounds, PDHG iterations, solve seconds (or the stated round budget), objective error against the
 planted value, and the interior-point and root-search seconds and counts of the supporting-hyperplane run.
-Usage: python tools/esh_bench.py [iter_cap=300] [cases=all|vertex|off|ball|quad]"""
+Usage: python tools/esh_bench.py [iter_cap=300] [cases=all|vertex|off|ball|quad|batch] [instances=512] [reps=7]"""
 import json
 import math
 import os
@@ -132,3 +140,51 @@ if which in ("all", "quad"):
     for n in (8, 16, 40):
         ellipsoid_case(n)
     qcqp_case()
+
+
+def batch_case(nb, reps):
+    from katana_jl_amd.batch import FusedBatch
+    insts = [ktn.instances.make_config("cfg5_one", seed=s) for s in range(nb)]
+
+    def handle(algo, points=None):
+        fb = FusedBatch(ktn.KatanaSolver(log_level=0, lp_max_iter=400000, cut_algo=algo), insts)
+        if points is not None:
+            fb.set_interior_points(points)
+        return fb
+    variants = [("kelley", handle("kelley"))]
+    own = handle("supporting_hyperplane")
+    variants.append(("supporting_engine_point", own))
+    for _, fb in variants:
+        fb.solve()                                                  # warm-up (the engine's own point is found here, once per load)
+    xi = own.m.interior_point()
+    find_s = own.m.stat("esh_interior_time_s")
+    if xi is not None:
+        given = handle("supporting_hyperplane", [xi[own.offs[k]:own.offs[k + 1]] for k in range(nb)])
+        given.solve()
+        variants.append(("supporting_caller_point", given))
+    times = {name: [] for name, _ in variants}
+    last = {}
+    for _ in range(reps):                                           # alternate the variants: other work shares the host
+        for name, fb in variants:
+            t0 = time.perf_counter()
+            res = fb.solve()                                        # (getsolution() inside: ends in a device synchronise)
+            times[name].append(time.perf_counter() - t0)
+            last[name] = res
+    for name, fb in variants:
+        res, t = last[name], sorted(times[name])
+        rec = fb.m.blocks_results()
+        err = max(abs(r["objval"] - i.opt_obj) / max(1.0, abs(i.opt_obj)) for r, i in zip(res, insts))
+        line = {"case": "batch_%dx_cfg5_one" % nb, "variant": name, "status": res[0]["status"], "reps": reps,
+                "solve_s_median": t[len(t) // 2], "solve_s_min": t[0], "solve_s_max": t[-1],
+                "xint_find_s": (find_s if name == "supporting_engine_point" else 0.0),
+                "xint_found": (None if name == "kelley" else fb.m.stat("esh_interior_found")),
+                "rounds_median": float(np.median(rec[:, 1])), "rounds_max": float(rec[:, 1].max()), "rounds_sum": float(rec[:, 1].sum()),
+                "pdhg_sum": float(rec[:, 4].sum()), "pdhg_max": float(rec[:, 4].max()), "lp_rows_max": float(rec[:, 6].max()),
+                "ecp_blocks_fallbacks": res[0]["ecp_blocks_fallbacks"], "ecp_blocks_launches": res[0]["ecp_blocks_launches"],
+                "ecp_blocks_esh_rows": res[0]["ecp_blocks_esh_rows"], "esh_fallback_rows_cumulative": fb.m.stat("esh_fallback_rows"),
+                "obj_err_max": err}
+        print(json.dumps(line), flush=True)
+
+
+if which == "batch":
+    batch_case(int(sys.argv[3]) if len(sys.argv) > 3 else 512, int(sys.argv[4]) if len(sys.argv) > 4 else 7)
