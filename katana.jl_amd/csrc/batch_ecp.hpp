@@ -11,7 +11,8 @@
 // global memory (the instance's LP in local indices with room for its cuts): CSR rows (unscaled + scaled values), CSC
 // mirror (unscaled + scaled), row bounds, duals, diagonal scalings, scaled problem vectors.  The PDHG iterates live in
 // LDS; matrix entries stream from L2 / Infinity Cache.  Everything is deterministic: sums have a fixed order, the column
-// mirror is sorted by row after the counting-sort scatter.
+// mirror is sorted by row after the counting-sort scatter.  What a check of the PDHG decides is pdhg_stop / pdhg_next of
+// pdhg_check.hpp, the functions the host loop of Engine::lp_solve_core calls, under this loop's own PdhgRules.
 //
 // k_ecp_blocks<ESH>: ESH = 0 is Kelley's method (every cut at x*).  ESH = 1 (ktn_optimize_blocks_ex with KTN_BLOCKS_SUPPORTING;
 // DESIGN.md section 11 "In the device-side loop") moves the cut of every violated row that takes part to the point where the
@@ -24,6 +25,7 @@
 // k_ecp_blocks<0> is the code and the kernel argument that were there before the switch existed.
 #pragma once
 #include "kernels.hpp"
+#include "pdhg_check.hpp"
 #include "quad_rows.hpp"
 #include "esh_quad.hpp"
 
@@ -88,24 +90,6 @@ struct EcpEsh {
 __device__ __forceinline__ const EcpEsh& ecp_esh_arg(const EcpEsh& e) { return e; }
 
 // ---------------------------------------------------------------------------------------------------------------------
-template <int NQ>
-__device__ __forceinline__ void ecp_reduce(double (&v)[NQ], int nsum, double* red, double* out) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-        const double s = (q < nsum) ? group_sum<64>(v[q]) : group_max<64>(v[q]);
-        if (lane == 0) red[wv * NQ + q] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < NQ) {
-        const int q = threadIdx.x;
-        double s = red[q];
-        for (int k = 1; k < kEcpThreads / 64; ++k) s = (q < nsum) ? s + red[k * NQ + q] : fmax(s, red[k * NQ + q]);
-        out[q] = s;
-    }
-    __syncthreads();
-}
-
 // sparse dot products of the block's outputs (rows or columns) with an LDS vector: out(o, acc) called by lane 0 of each
 // group.  T outputs per lane group and pass: the entry ranges of all T, then the first two entries per lane of all T, are
 // requested before anything is used -- a pass costs two memory latencies instead of two per output (a lone workgroup, the
@@ -346,7 +330,7 @@ __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B, EshArg..
                 const double v = 0.25 + (double)(h >> 11) * (1.0 / 9007199254740992.0);
                 xts[j] = v; a1[0] += v * v;
             }
-            ecp_reduce<1>(a1, 1, red, q);
+            wg_reduce<kEcpThreads, 1>(a1, 1, red, q);
             double nrm = sqrt(q[0]);
             __syncthreads();
             for (int j = tid; j < nb; j += kEcpThreads) xts[j] = nrm > 0.0 ? xts[j] / nrm : 0.0;
@@ -356,11 +340,10 @@ __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B, EshArg..
                 ecp_spmv<4, 4>(M, rptr, rcol, rsval, xts, [&](int) { return EcpPre{0.0, 0.0, 0.0}; }, [&](int r, double acc, const EcpPre&) { yts[r] = acc; });
                 __syncthreads();
                 a1[0] = 0.0;
-                // A'(A v) into icnt-free scratch: reuse ch? no -- write into x0s? x0s holds the anchor: use the LDS vector xts after the
-                // products are taken from yts only (columns read yts, write xts: no hazard)
+                // A'(A v) into xts: the columns read yts and write xts, no hazard
                 ecp_spmv<4, 4>(nb, cptr, crow, csval, yts, [&](int) { return EcpPre{0.0, 0.0, 0.0}; },
                                [&](int j, double acc, const EcpPre&) { xts[j] = acc; a1[0] += acc * acc; });
-                ecp_reduce<1>(a1, 1, red, q);
+                wg_reduce<kEcpThreads, 1>(a1, 1, red, q);
                 nrm = sqrt(q[0]);
                 __syncthreads();
                 if (pass < npow - 1) for (int j = tid; j < nb; j += kEcpThreads) xts[j] = nrm > 0.0 ? xts[j] / nrm : 0.0;
@@ -379,16 +362,14 @@ __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B, EshArg..
         double v2[2] = {0.0, 0.0};
         for (int j = tid; j < nb; j += kEcpThreads) v2[0] += ch[j] * ch[j];
         for (int r = tid; r < M; r += kEcpThreads) { const double a = loh[r], bb = hih[r]; if (isfinite(a)) v2[1] += a * a; if (isfinite(bb)) v2[1] += bb * bb; }
-        ecp_reduce<2>(v2, 2, red, q);
+        wg_reduce<kEcpThreads, 2>(v2, 2, red, q);
         const double nc2 = q[0], nb2 = q[1];
         __syncthreads();
         const double omega_ref = (nc2 > 0.0 && nb2 > 0.0) ? sqrt(nc2 / nb2) : 1.0;
         const double dres_scale = 1.0 + sqrt(nc2);
         double om = om_keep > 0.0 ? om_keep : omega_ref;
         int k = 0, it = 0;
-        // st: 0 rr0, 1 r_prev, 2 r_last, 3-5 primal objective history, 6-8 row violation history, 9 stall, 10 flat_rows, 11 consolidations
-        if (tid == 0) { st[0] = 0.0; st[1] = 0.0; st[2] = 0.0; st[3] = 1e300; st[4] = -1e300; st[5] = 1e300; st[6] = 1e300; st[7] = -1e300; st[8] = 1e300;
-                        st[9] = 0.0; st[10] = 0.0; st[11] = 0.0; }
+        if (tid == 0) *reinterpret_cast<PdhgCtl*>(st) = pdhg_start();          // (st: the PdhgCtl of this LP solve)
         bool plain_next = false, near_conv = false;
         int lp_status = KTN_STATUS_USERLIMIT;
         double pobj = 0.0;
@@ -440,84 +421,35 @@ __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B, EshArg..
                         const double ytv = prox_y(y1, sigma, 2.0 * axt - axk, loi, hii);
                         yts[r] = ytv;
                         axv[r] = axt;
-                        const double dy = ytv - y1;
-                        a[0] += dy * (axt - axk); a[1] += dy * dy;
-                        if (ytv > 0.0) { if (loi > -__builtin_inf()) a[2] += loi * ytv; }
-                        else if (ytv < 0.0) { if (hii < __builtin_inf()) a[2] += hii * ytv; }
-                        const double d0 = ytv - y0s[r];
-                        a[3] += d0 * d0; a[9] += ytv * ytv;
-                        a[10] = fmax(a[10], fmax(fmax(loi - axt, axt - hii), 0.0) / dr[r]);
+                        const ChkRowTerms t = chk_row_terms(ytv, y1, y0s[r], axt, axk, loi, hii, dr[r]);
+                        a[0] += t.dyAdx; a[1] += t.dy2; a[2] += t.dobj; a[3] += t.dy0sq; a[9] += t.yt2;
+                        a[10] = fmax(a[10], t.viol);
                     }
                 }
             }
             __syncthreads();
             ecp_spmv<4, 4>(nb, cptr, crow, csval, yts, [&](int j) { return EcpPre{ch[j], lh[j], uh[j]}; },
                            [&](int j, double aty, const EcpPre& p) {
-                const double xtv = xts[j], cj = p.a, lj = p.b, uj = p.c;
-                const double dx = xtv - xs[j];
-                a[4] += dx * dx; a[5] += cj * xtv;
-                const double rc = cj - aty;
-                double bad = 0.0;
-                if (rc > 0.0) { if (isfinite(lj)) a[6] += lj * rc; else bad = rc; }
-                else if (rc < 0.0) { if (isfinite(uj)) a[6] += uj * rc; else bad = -rc; }
-                const double d0 = xtv - x0s[j];
-                a[7] += d0 * d0; a[8] += xtv * xtv;
-                a[11] = fmax(a[11], bad / dc[j]);
+                const ChkColTerms t = chk_col_terms(xts[j], xs[j], x0s[j], aty, p.a, p.b, p.c, dc[j]);
+                a[4] += t.dx2; a[5] += t.pobj; a[6] += t.dobj; a[7] += t.dx0sq; a[8] += t.xt2;
+                a[11] = fmax(a[11], t.dres);
             });
-            ecp_reduce<kEcpQ>(a, 10, red, q);
+            wg_reduce<kEcpThreads, kEcpQ>(a, 10, red, q);
             if (tid == 0) {
-                const double dyAdx = q[0], dy2 = q[1], dy0sq = q[3], dx2 = q[4], dx0sq = q[7], xt2 = q[8], yt2 = q[9];
-                const double po = q[5], dobj = q[2] + q[6], pviol = q[10], dres = q[11];
+                const PdhgSums S{q[0], q[1], q[3], q[4], q[7], q[8], q[9], q[5], q[2] + q[6], q[10], q[11]};
+                const PdhgRules rules{tol_p, tol_g, dres_scale, B.stag_factor, 0.1, 3, stall_accept, eta_safe, false, false, M > m_lin,
+                                      omega_ref, true, 0.0, 0.0, 0.0, 0.0};
+                PdhgCtl& pc = *reinterpret_cast<PdhgCtl*>(st);
+                const PdhgStop t = pdhg_stop(S, rules, pc, om, eta, k);
+                int action = 0;                               // 0 continue, 1 restart, 2 done, 3 give up, 4 consolidate and restart
                 double om1 = om, eta1 = eta;
-                const double r2 = om1 / eta1 * dx2 - 2.0 * dyAdx + dy2 / (eta1 * om1);
-                const double r = sqrt(fmax(r2, 0.0));
-                const double gap = fabs(po - dobj) / (1.0 + fabs(po) + fabs(dobj));
-                if (k == 0) { st[0] = r; st[1] = r; }
-                const bool dres_ok = dres <= tol_g * dres_scale;
-                bool done = (pviol <= tol_p) && (gap <= tol_g) && dres_ok;
-                const bool near = (pviol <= 4.0 * tol_p) && (gap <= 4.0 * tol_g) && (dres <= 4.0 * tol_g * dres_scale);
-                if (B.stag_factor > 0.0 && !done) {
-                    const double f = 0.1 * tol_g * (1.0 + fabs(po));
-                    const bool flat = fabs(po - st[3]) <= f && fabs(po - st[4]) <= f && fabs(po - st[5]) <= f;
-                    const bool plateau = pviol <= stall_accept * tol_p && fabs(pviol - st[6]) <= 0.02 * pviol &&
-                                         fabs(pviol - st[7]) <= 0.02 * pviol && fabs(pviol - st[8]) <= 0.02 * pviol;
-                    if (flat && (pviol <= tol_p || plateau) && gap <= B.stag_factor * tol_g && dres_ok) done = true;
-                    if (!done && gap <= tol_g && dres_ok && plateau) done = true;
-                }
-                st[8] = st[7]; st[7] = st[6]; st[6] = pviol; st[5] = st[4]; st[4] = st[3]; st[3] = po;
-                int action = 0;
-                if (done) action = 2;
-                else if (!(r == r)) action = 3;
+                if (t.exit != PDHG_EXIT_NONE) action = t.exit == PDHG_EXIT_NAN ? 3 : 2;
                 else {
-                    const double rr0 = st[0], r_prev = st[1], r_last = st[2];
-                    bool restart = k > 0 && (r <= 0.2 * rr0 || (r <= 0.8 * rr0 && r > r_prev) || (double)k >= 0.36 * (double)(it + 1));
-                    if (k > 0 && eta1 > eta_safe * (1.0 + 1e-12)) {
-                        const int stall = (r2 < 0.0 || (r_last > 0.0 && r > 0.97 * r_last && r < 1.03 * r_last)) ? (int)st[9] + 1 : 0;
-                        st[9] = (double)stall;
-                        if (stall >= 3 || r2 < 0.0) { eta1 = fmax(eta_safe, 0.85 * eta1); st[9] = 0.0; restart = true; }
-                    }
-                    // objective converged, rows not, residual flat: multiplier mass idles between near-parallel cuts of one NL
-                    // row (kernels.hpp k_consolidate): move it onto the tightest cut and restart there
-                    bool consolidate = false;
-                    if (k > 0 && M > m_lin && gap <= tol_g && dres_ok && pviol > tol_p) {
-                        const int flat_rows = (r_last > 0.0 && r > 0.98 * r_last) ? (int)st[10] + 1 : 0;
-                        st[10] = (double)flat_rows;
-                        if (flat_rows >= 3 && st[11] < 8.0) { st[10] = 0.0; st[11] += 1.0; consolidate = true; }
-                    } else {
-                        st[10] = 0.0;
-                    }
-                    st[2] = r; st[1] = r;
-                    if (consolidate) { action = 4; st[2] = 0.0; }
-                    else if (restart) {
-                        const double dx = sqrt(dx0sq), dy = sqrt(dy0sq);
-                        if (dx > 1e-8 * (1.0 + sqrt(xt2)) && dy > 1e-8 * (1.0 + sqrt(yt2))) {
-                            om1 = exp(0.5 * log(dy / dx) + 0.5 * log(om1));
-                            om1 = fmin(fmax(om1, omega_ref * 1e-3), omega_ref * 1e3);
-                        }
-                        action = 1;
-                    }
+                    const PdhgNext nx = pdhg_next(S, rules, pc, t, om, eta, k, it);
+                    om1 = nx.om; eta1 = nx.eta;
+                    action = nx.action == PDHG_CONSOLIDATE ? 4 : (nx.action == PDHG_RESTART ? 1 : 0);
                 }
-                ctl[0] = (double)action; ctl[1] = om1; ctl[2] = eta1; ctl[3] = near ? 1.0 : 0.0; ctl[4] = po;
+                ctl[0] = (double)action; ctl[1] = om1; ctl[2] = eta1; ctl[3] = t.near ? 1.0 : 0.0; ctl[4] = S.pobj;
             }
             __syncthreads();
             const int action = (int)ctl[0];
@@ -659,17 +591,16 @@ __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B, EshArg..
         __syncthreads();
         {
             double t1[1] = {mv[0]};
-            ecp_reduce<1>(t1, 0, red, q);
+            wg_reduce<kEcpThreads, 1>(t1, 0, red, q);
             mv[0] = q[0];
         }
         __syncthreads();
         // ranks of the violated rows (serial scan over m_nl ~ 1e2 slots)
         if (tid == 0) {
-            int rows = 0, nz = 0;
+            int rows = 0;
             for (int i = 0; i < m_nl; ++i) { const int len = icnt[i]; icnt[i] = len > 0 ? ((rows << 1) | 1) : 0; if (len > 0) { ++rows; } }
             // second pass for the entry offsets (row lengths come from the structure again)
             ctl[5] = (double)rows;
-            (void)nz;
         }
         __syncthreads();
         const int V = (int)ctl[5];
@@ -835,7 +766,7 @@ __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B, EshArg..
             }
             {
                 double t1[1] = {(double)bad_nf};
-                ecp_reduce<1>(t1, 0, red, q);
+                wg_reduce<kEcpThreads, 1>(t1, 0, red, q);
                 if (q[0] != 0.0) { status = KTN_STATUS_ERROR; __syncthreads(); break; }    // model.jl:69-73
             }
             M += V; NNZ += nnzV; numcuts += V;
@@ -866,7 +797,7 @@ __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B, EshArg..
             if (isfinite(lb)) v = fmax(v, lb - g);
             if (v >= -10.0 * B.f_tol) d1[0] += lam * v;
         }
-        ecp_reduce<1>(d1, 1, red, q);
+        wg_reduce<kEcpThreads, 1>(d1, 1, red, q);
         const double D = (q[0] == q[0]) ? fmax(q[0], 0.0) : __builtin_inf();
         const double target = B.cert_tol * fmax(1.0, fabs(objval));
         __syncthreads();
@@ -898,7 +829,7 @@ __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B, EshArg..
     if constexpr (ESH != 0) {                                                       // each workgroup owns its four counters
         double c4[4] = {(double)esh_cnt[0], (double)esh_cnt[1], (double)esh_cnt[2], (double)esh_cnt[3]};
         __syncthreads();
-        ecp_reduce<4>(c4, 4, red, q);
+        wg_reduce<kEcpThreads, 4>(c4, 4, red, q);
         if (tid < 4) ecp_esh_arg(esh_arg...).res[(int64_t)b * 4 + tid] = q[tid];
     }
 }

@@ -8,10 +8,10 @@
 // order).  Its iterates x, x0, xt|xbar, y, y0, yt live in LDS (6 vectors of ~1e3 doubles: 50 KB, three instances per CU);
 // the matrix entries stream from L2 / Infinity Cache (24 B per non-zero and iteration for the two products -- a cfg5 LP is
 // ~3e5 B, the 512 of them are 150 MB: they do not fit the 160 KB of LDS next to the vectors).
-// The control logic is the host loop of Engine::lp_solve_core restated per block (termination, primal-stagnation exit,
-// stalled-row acceptance, the three restart rules, the guarded primal-weight update, the step-size back-off); what a
-// block cannot do here -- dual-mass consolidation, infeasibility certificates -- makes it report USERLIMIT, and the
-// engine then finishes the solve with the ordinary loop from the point reached.
+// What a check decides is defined by pdhg_stop / pdhg_next of pdhg_check.hpp under this loop's rule set (DESIGN.md section 5,
+// the column "k_pdhg_blocks"); thread 0 keeps its own text of it, see there.  What a block cannot do here -- dual-mass
+// consolidation, infeasibility certificates -- makes it report USERLIMIT, and the engine then finishes the solve with the
+// ordinary loop from the point reached.
 //
 // Replaces, per instance, the loop of src/model.jl:257-309 around solve(m.linear_model) (:259).
 #pragma once
@@ -39,26 +39,6 @@ struct BlkLp {
     double tol_p, tol_g, eta0, eta_safe, stag_factor, stall_accept;
     int check_every, first_chunk, near_chunk, max_iter, nmax, mmax;
 };
-
-template <int NQ>
-__device__ __forceinline__ void blk_reduce(double (&v)[NQ], int nsum, double* red, double* out) {
-    // v[0..nsum) are summed, v[nsum..NQ) maximised; fixed shape: butterfly per wavefront, wavefronts in order
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-        double s = (q < nsum) ? group_sum<64>(v[q]) : group_max<64>(v[q]);
-        if (lane == 0) red[wv * NQ + q] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < NQ) {
-        const int q = threadIdx.x;
-        double s = red[q];
-        for (int k = 1; k < kBlkThreads / 64; ++k) s = (q < nsum) ? s + red[k * NQ + q] : fmax(s, red[k * NQ + q]);
-        out[q] = s;
-    }
-    __syncthreads();
-}
-
 
 // Sparse dot products of up to T consecutive "trips" of a thread (trip t serves output o0 + t * stride), G lanes per
 // output, with ALL first-level loads (entry ranges), then ALL second-level loads (the first two entries per lane of every
@@ -136,7 +116,7 @@ static __global__ __launch_bounds__(kBlkThreads) void k_pdhg_blocks(BlkLp P) {
         if (isfinite(bb)) v2[1] += bb * bb;
     }
     __syncthreads();
-    blk_reduce<2>(v2, 2, red, q);
+    wg_reduce<kBlkThreads, 2>(v2, 2, red, q);
     const double nc2 = q[0], nb2 = q[1];
     __syncthreads();
     const double omega_ref = (nc2 > 0.0 && nb2 > 0.0) ? sqrt(nc2 / nb2) : 1.0;
@@ -254,15 +234,9 @@ static __global__ __launch_bounds__(kBlkThreads) void k_pdhg_blocks(BlkLp P) {
                 const double loi = P.lo[gi], hii = P.hi[gi], yv = ys[r];
                 const double ytv = prox_y(yv, sigma, 2.0 * axt - axk, loi, hii);
                 yts[r] = ytv;
-                const double dy = ytv - yv;
-                a[0] += dy * (axt - axk);
-                a[1] += dy * dy;
-                if (ytv > 0.0) { if (loi > -__builtin_inf()) a[2] += loi * ytv; }
-                else if (ytv < 0.0) { if (hii < __builtin_inf()) a[2] += hii * ytv; }
-                const double d0 = ytv - y0s[r];
-                a[3] += d0 * d0;
-                a[9] += ytv * ytv;
-                a[10] = fmax(a[10], fmax(fmax(loi - axt, axt - hii), 0.0) / P.dr[gi]);
+                const ChkRowTerms t = chk_row_terms(ytv, yv, y0s[r], axt, axk, loi, hii, P.dr[gi]);
+                a[0] += t.dyAdx; a[1] += t.dy2; a[2] += t.dobj; a[3] += t.dy0sq; a[9] += t.yt2;
+                a[10] = fmax(a[10], t.viol);
             }
         }
         __syncthreads();
@@ -274,21 +248,16 @@ static __global__ __launch_bounds__(kBlkThreads) void k_pdhg_blocks(BlkLp P) {
             for (int64_t e = beg + lane; e < end; e += GX) aty += P.cval[e] * yts[P.crowl[e]];
             aty = group_sum<GX>(aty);
             if (lane == 0) {
-                const double xtv = xts[j], cj = P.c[gj], lj = P.l[gj], uj = P.u[gj];
-                const double dx = xtv - xs[j];
-                a[4] += dx * dx;
-                a[5] += cj * xtv;
-                const double rc = cj - aty;
-                double bad = 0.0;
-                if (rc > 0.0) { if (isfinite(lj)) a[6] += lj * rc; else bad = rc; }
-                else if (rc < 0.0) { if (isfinite(uj)) a[6] += uj * rc; else bad = -rc; }
-                const double d0 = xtv - x0s[j];
-                a[7] += d0 * d0;
-                a[8] += xtv * xtv;
-                a[11] = fmax(a[11], bad / P.dc[gj]);
+                const ChkColTerms t = chk_col_terms(xts[j], xs[j], x0s[j], aty, P.c[gj], P.l[gj], P.u[gj], P.dc[gj]);
+                a[4] += t.dx2; a[5] += t.pobj; a[6] += t.dobj; a[7] += t.dx0sq; a[8] += t.xt2;
+                a[11] = fmax(a[11], t.dres);
             }
         }
-        blk_reduce<kBlkQ>(a, 10, red, q);
+        wg_reduce<kBlkThreads, kBlkQ>(a, 10, red, q);
+        // The decision below must follow pdhg_stop / pdhg_next (pdhg_check.hpp) with the rules {stag_factor, flat window 0.1 over 3
+        // checks, stall_accept, dres scale 1 + sqrt(nc2), eta_safe, no NaN exit, no growing-residual back-off, no consolidation, plain
+        // weight update}: tests/c/pdhg_rules.cpp runs that rule set.  Its text stays here because calling the two functions costs
+        // this kernel 4 bytes of scratch per lane in every form tried (profiles/pdhg_check_resources.txt).
         if (tid == 0) {
             const double dyAdx = q[0], dy2 = q[1], dy0sq = q[3], dx2 = q[4], dx0sq = q[7], xt2 = q[8], yt2 = q[9];
             pobj = q[5]; dobj = q[2] + q[6]; pviol = q[10]; dres = q[11];

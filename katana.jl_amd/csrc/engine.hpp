@@ -627,6 +627,7 @@ struct Engine {
     void pdhg_raw(const double* x0, const double* y0, double eta, double omega_, int64_t iters, double* x_out,
                   double* y_out);
     // pieces of lp_solve_core that the scripted test hook shares with it (lp.hip)
+    void lp_resize_iterates();
     void lp_pick_groups();
     void lp_choose_tiled(bool same_matrix);
     void lp_set_anchors(bool want_packed);

@@ -119,6 +119,26 @@ __device__ __forceinline__ double block_sum(double v, double (&sh)[BLOCK / 64]) 
     block_sum<BLOCK>(a, &sh);
     return a[0];
 }
+// Workgroup-wide reduction of NQ values per thread into out[0..NQ), readable by every thread afterwards: v[0..nsum) are summed,
+// v[nsum..NQ) maximised.  Fixed shape: butterfly per wavefront, then thread q takes quantity q over the wavefronts in order.
+// red: [THREADS / 64][NQ] cells of the caller.  Every thread of the workgroup reaches the call.
+template <int THREADS, int NQ>
+__device__ __forceinline__ void wg_reduce(double (&v)[NQ], int nsum, double* red, double* out) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        double s = (q < nsum) ? group_sum<64>(v[q]) : group_max<64>(v[q]);
+        if (lane == 0) red[wv * NQ + q] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < NQ) {
+        const int q = threadIdx.x;
+        double s = red[q];
+        for (int k = 1; k < THREADS / 64; ++k) s = (q < nsum) ? s + red[k * NQ + q] : fmax(s, red[k * NQ + q]);
+        out[q] = s;
+    }
+    __syncthreads();
+}
 
 // Six scalars a sweep / a purge hands back to the host -- the last elements of two (flag, exclusive scan) pairs, the
 // largest violation and two int flags -- written by ONE thread into pinned, device-mapped host memory instead of six
@@ -1380,21 +1400,38 @@ __global__ __launch_bounds__(kBlock) void k_pdhg_y_packed(int64_t m, const int32
 // KKT / fixed-point quantities, row side, accumulated by the check form of the y-step.
 //  s0 sum dy*(A dx)   s1 sum dy^2      s2 dual objective (rows)  s3 sum (yt-y0)^2  s4 sum yt^2
 //  s10 abs terms of the dual objective   m12 max unscaled row violation
-__device__ __forceinline__ void chk_row_accumulate(ChkAcc& a, double ytv, double yv, double y0v, double axt, double axk,
-                                                   double lo, double hi, double dri) {
+// One row's contribution to a check, written once for the check kernels (16 slots, chk_row_accumulate) and the two batch loops
+// (12 slots, batch_lp.hpp / batch_ecp.hpp).  (The sums start at +0.0 and can never become -0.0, so a row without a dual-objective
+// term adds its +0.0 without changing a bit.)
+struct ChkRowTerms { double dyAdx, dy2, dobj, dy0sq, yt2, viol; };
+__device__ __forceinline__ ChkRowTerms chk_row_terms(double ytv, double yv, double y0v, double axt, double axk, double lo, double hi,
+                                                     double dri) {
+    ChkRowTerms t;
     const double dy = ytv - yv;
-    a.s[0] += dy * (axt - axk);
-    a.s[1] += dy * dy;
+    t.dyAdx = dy * (axt - axk);
+    t.dy2 = dy * dy;
     // The projection makes yt sign-feasible (yt > 0 only where lo is finite) up to ROUNDING: v + sigma * (-v / sigma) can
     // leave a residue of a few 1e-17 with the wrong sign, and -inf * 1e-17 = -inf would void the duality gap of this
     // check (seen at every second check of a slowly converging solve).  Such residues carry no dual objective.
-    if (ytv > 0.0) { if (lo > -__builtin_inf()) { a.s[2] += lo * ytv; a.s[10] += fabs(lo * ytv); } }
-    else if (ytv < 0.0) { if (hi < __builtin_inf()) { a.s[2] += hi * ytv; a.s[10] += fabs(hi * ytv); } }
+    t.dobj = 0.0;
+    if (ytv > 0.0) { if (lo > -__builtin_inf()) t.dobj = lo * ytv; }
+    else if (ytv < 0.0) { if (hi < __builtin_inf()) t.dobj = hi * ytv; }
     const double d0 = ytv - y0v;
-    a.s[3] += d0 * d0;
-    a.s[4] += ytv * ytv;
-    const double viol = fmax(fmax(lo - axt, axt - hi), 0.0) / dri;
-    a.s[12] = fmax(a.s[12], viol);
+    t.dy0sq = d0 * d0;
+    t.yt2 = ytv * ytv;
+    t.viol = fmax(fmax(lo - axt, axt - hi), 0.0) / dri;
+    return t;
+}
+__device__ __forceinline__ void chk_row_accumulate(ChkAcc& a, double ytv, double yv, double y0v, double axt, double axk,
+                                                   double lo, double hi, double dri) {
+    const ChkRowTerms t = chk_row_terms(ytv, yv, y0v, axt, axk, lo, hi, dri);
+    a.s[0] += t.dyAdx;
+    a.s[1] += t.dy2;
+    a.s[2] += t.dobj;
+    a.s[10] += fabs(t.dobj);
+    a.s[3] += t.dy0sq;
+    a.s[4] += t.yt2;
+    a.s[12] = fmax(a.s[12], t.viol);
 }
 
 // y-step + reflected Halpern update.  One group per row (CSR gather of xbar).
@@ -1565,19 +1602,34 @@ static __global__ __launch_bounds__(kRedBlocks) void k_chk_final(const double* _
 //  s5 sum dx^2  s6 primal objective  s7 dual objective (bounds)  s8 sum (xt-x0)^2  s9 sum xt^2
 //  s10 Farkas value (bounds part)  s11 its absolute terms  m14 max reduced cost of the c=0 problem on an infinite bound
 //  m13 max unscaled dual residual (reduced cost not absorbable by a finite bound)
-__device__ __forceinline__ void chk_col_accumulate(ChkAcc& a, double xtv, double xv, double x0v, double aty, double cj, double lj,
-                                                   double uj, double dcj) {
+// one column's contribution, as chk_row_terms: dres is the reduced cost that no finite bound absorbs, unscaled
+struct ChkColTerms { double dx2, pobj, dobj, dx0sq, xt2, dres; };
+__device__ __forceinline__ ChkColTerms chk_col_terms(double xtv, double xv, double x0v, double aty, double cj, double lj, double uj,
+                                                     double dcj) {
+    ChkColTerms t;
     const double dx = xtv - xv;
-    a.s[5] += dx * dx;
-    a.s[6] += cj * xtv;
+    t.dx2 = dx * dx;
+    t.pobj = cj * xtv;
     const double r = cj - aty;
     double bad = 0.0;
-    if (r > 0.0) { if (isfinite(lj)) a.s[7] += lj * r; else bad = r; }
-    else if (r < 0.0) { if (isfinite(uj)) a.s[7] += uj * r; else bad = -r; }
+    t.dobj = 0.0;
+    if (r > 0.0) { if (isfinite(lj)) t.dobj = lj * r; else bad = r; }
+    else if (r < 0.0) { if (isfinite(uj)) t.dobj = uj * r; else bad = -r; }
     const double d0 = xtv - x0v;
-    a.s[8] += d0 * d0;
-    a.s[9] += xtv * xtv;
-    a.s[13] = fmax(a.s[13], bad / dcj);
+    t.dx0sq = d0 * d0;
+    t.xt2 = xtv * xtv;
+    t.dres = bad / dcj;
+    return t;
+}
+__device__ __forceinline__ void chk_col_accumulate(ChkAcc& a, double xtv, double xv, double x0v, double aty, double cj, double lj,
+                                                   double uj, double dcj) {
+    const ChkColTerms t = chk_col_terms(xtv, xv, x0v, aty, cj, lj, uj, dcj);
+    a.s[5] += t.dx2;
+    a.s[6] += t.pobj;
+    a.s[7] += t.dobj;
+    a.s[8] += t.dx0sq;
+    a.s[9] += t.xt2;
+    a.s[13] = fmax(a.s[13], t.dres);
     // Farkas value of yt: the dual objective with c = 0 (positive <=> the rows + bounds are infeasible)
     const double r0 = -aty;
     if (r0 > 0.0) { if (isfinite(lj)) { a.s[10] += lj * r0; a.s[11] += fabs(lj * r0); } else a.s[14] = fmax(a.s[14], r0); }

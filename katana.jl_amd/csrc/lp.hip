@@ -2,6 +2,7 @@
 #include "engine.hpp"
 #include "launch.hpp"
 #include "kernels.hpp"
+#include "pdhg_check.hpp"
 #include "dense_lp.hpp"
 #include "mid_lp.hpp"
 #include "batch_lp.hpp"
@@ -724,6 +725,15 @@ void Engine::lp_choose_tiled(bool same_matrix) {
     }
 }
 
+// the scaled problem vectors and the PDHG iterates (xbar, pv, pw: work vectors of the steps and of the power iteration)
+void Engine::lp_resize_iterates() {
+    const size_t n = (size_t)n_lp, mm = (size_t)std::max<int64_t>(M, 1);
+    ch.resize(n, stream); lh.resize(n, stream); uh.resize(n, stream); xh.resize(n, stream);
+    x0h.resize(n, stream); xth.resize(n, stream); xbar.resize(n, stream); pv.resize(n, stream);
+    loh.resize(mm, stream); hih.resize(mm, stream); yh.resize(mm, stream); y0h.resize(mm, stream);
+    yth.resize(mm, stream); pw.resize(mm, stream);
+}
+
 // anchors z0 = z; with the packed records of the plain steps when asked for (not for the tiled / row-sharded forms, whose
 // steps are split into SpMV + element-wise kernels)
 void Engine::lp_set_anchors(bool want_packed) {
@@ -792,11 +802,7 @@ LpResult Engine::lp_solve_core(double tol_p, double tol_g, int mode, bool identi
     else stats["lp_setup_reuses"] += 1.0;
     lap("lp_scaling_time_s", tp);
     const int64_t n = n_lp, m = M;
-    const size_t mm = (size_t)std::max<int64_t>(m, 1);
-    ch.resize(n, stream); lh.resize(n, stream); uh.resize(n, stream); xh.resize(n, stream);
-    x0h.resize(n, stream); xth.resize(n, stream); xbar.resize(n, stream); pv.resize(n, stream);
-    loh.resize(mm, stream); hih.resize(mm, stream); yh.resize(mm, stream); y0h.resize(mm, stream);
-    yth.resize(mm, stream); pw.resize(mm, stream);
+    lp_resize_iterates();
     const double sgn = (sense == KTN_MAX) ? -1.0 : 1.0;
     LAUNCH_1(k_prep_both, std::max(n, m), stream,
              PrepCols{n, Wc(), lp_l.p, lp_u.p, dc.p, lp_x.p, (mode == 1 ? box.p : (const double*)nullptr), sgn, mode, ch.p, lh.p, uh.p, xh.p},
@@ -926,9 +932,8 @@ LpResult Engine::lp_solve_core(double tol_p, double tol_g, int mode, bool identi
     if (!(smax > 0.0)) smax = fro;
     const double eta_safe = 0.998 / std::max(identity_scaling ? fro : std::min(1.0, fro), 1e-12);
     double eta = std::max(0.998 / std::max(smax, 1e-12), eta_safe);
-    int stall = 0, grow = 0, flat_rows = 0, consolidations = 0, infeas_hits = 0;
-    double pobj_h[3] = {1e300, -1e300, 1e300}, pviol_h[3] = {1e300, -1e300, 1e300};
-    double r_last_check = 0.0;
+    int infeas_hits = 0;
+    PdhgCtl pc = pdhg_start();
     stats["lp_setup_time_s"] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     const double nc2 = hs[3];
     const double nc2_tol = w_shift ? hs[6] : nc2;       // (the working cost carries a_ref: not the scale the dual residual is judged on)
@@ -941,7 +946,43 @@ LpResult Engine::lp_solve_core(double tol_p, double tol_g, int mode, bool identi
     }
     double om = (have_omega && mode == 0) ? omega : omega_ref;
     const double rho = 1.0;
-    const double cinf_scale = 1.0;
+    // The rules of this loop's checks (pdhg_check.hpp; DESIGN.md section 5 sets them beside the device-side loops').
+    PdhgRules rules{};
+    rules.tol_p = tol_p; rules.tol_g = tol_g;
+    rules.dres_scale = 1.0 + std::sqrt(nc2_tol);
+    // Primal-stagnation exit (lp_stag_factor).  On LPs with degenerate duals the primal part converges within a few hundred
+    // iterations while the duality gap crawls for 10 000 more.  "Flat" is within 0.4 tol_g over the last TWO
+    // checks (KTN_FLAT_FACTOR, KTN_STAG_CHECKS; 0.1 and three until round 3: -12 % and -5 ... -7 % PDHG iterations on the BASELINE
+    // shapes, objective errors, reference models, fuzz set and shape matrix unchanged).
+    // A model with free variables runs inside the box the presolve put around it (boundroutine, model.jl:175-197): a loosely solved
+    // LP can then sit ANYWHERE in that box, and cuts taken at |x| ~ 1e13 have constants of 1e31 that no first-order LP survives (fuzz
+    // model 2/109: primal weight 1e-30, objective 6e26, :Error).  Such models keep the conservative rules of round 2 and 3: three
+    // flat checks within 0.1 of the gap tolerance, gap certified to 100 tolerances, the undamped weight update.
+    rules.stag_factor = mode != 0 ? 0.0 : (has_inf_bound ? std::min(prm.lp_stag_factor, 100.0) : prm.lp_stag_factor);
+    rules.flat_factor = has_inf_bound ? std::min(dev.flat_factor, 0.1) : dev.flat_factor;
+    rules.flat_checks = has_inf_bound ? 3 : dev.stag_checks;
+    // Stalled-row allowance.  tol_p's floor is 0.3 f_tol -- a safety factor, the stop rule itself is the sweep at f_tol -- so a
+    // violation that has not moved by 2 % over three checks is accepted up to 3 tol_p (0.9 f_tol; seen: 3.47e-7 against 3.0e-7 for
+    // 2.1e6 iterations).  An INTERMEDIATE solve (tol_p above its floor: its x* only has to be a useful separation point, cuts are
+    // valid anywhere) accepts up to 10 tol_p -- the new cuts of the next sweep are what ends such a stall.
+    rules.stall_accept = (tol_p > prm.lp_tol_floor * prm.f_tol * (1.0 + 1e-9)) ? 10.0 : 3.0;
+    rules.eta_safe = eta_safe;
+    rules.nan_exit = true;
+    rules.grow_backoff = true;          // (seen on cfg3 seeds 28/29: r0 = 6 -> 87 -> 530 -> 1e5 until the flat-residual rule fired)
+    // (row-sharded: the decision to consolidate must not depend on what THIS rank holds -- a rank that consolidated while another did
+    //  not would leave the sequence of collectives -- so the local conditions are dropped; k_consolidate on a rank without cuts is a no-op)
+    rules.consolidate = mode == 0 && (row_sharded() ? (prm.lp_dual_inherit != 0) : (prm.lp_dual_inherit && lists_ok() && list_count() > 0 && m > M_base));
+    rules.omega_ref = omega_ref;
+    // Unearned restarts carry little information about the weight (round 4; profiles/r04_omega_ab.txt).  A solve's first restarts
+    // come "by the clock" (k >= 0.36 it), whether or not the residual has moved; after a warm start whose primal part is already
+    // converged x moves by 1e-6 of its norm in such a period, and the ratio of that movement to the dual's sent the weight
+    // 603 -> 0.16 in four restarts (cfg2 seed 92: 44 000 iterations to earn it back).  So the weight of the new ratio in the geometric
+    // mean grows with the length of the period it was measured over: theta = 0.5 min(1, k / K), K = KTN_OMEGA_ART_K.
+    rules.om_art = dev.omega_art != 0;
+    rules.om_art_k = has_inf_bound ? 0.0 : dev.omega_art_k;
+    rules.om_art_clamp = dev.omega_art_clamp;
+    rules.om_clamp = dev.omega_clamp;
+    rules.om_clamp_down = dev.omega_clamp_down;
     if (dev.debug_lp)
         std::fprintf(stderr, "[lp setup mode %d] m %lld n %lld nnz %lld smax %.4g fro %.4g nc2 %.4g nc2_tol %.4g nb2 %.4g omega_ref %.4g om0 %.4g shift %d b_ref %.9g n_long %lld tol_p %.3g tol_g %.3g\n",
                      mode, (long long)m, (long long)n, (long long)NNZ, smax, fro, nc2, nc2_tol, nb2, omega_ref, om, (int)w_shift, epi_b, (long long)n_long, tol_p, tol_g);
@@ -953,7 +994,6 @@ LpResult Engine::lp_solve_core(double tol_p, double tol_g, int mode, bool identi
     const double ky_bytes = (double)NNZ * 12 + 8.0 * (m + 1) + 8.0 * 5 * m + 8.0 * n;
     const double kx_bytes = (double)NNZ * 12 + 8.0 * (n + 1) + 8.0 * 7 * n + 8.0 * m;
     int64_t k = 0, it = 0;
-    double r0 = 0.0, r_prev = 0.0;
     const bool dbg_lp = dev.debug_lp;
     R.status = KTN_STATUS_USERLIMIT;
     const int64_t max_it = lp_iter_budget > 0 ? std::min<int64_t>(lp_iter_budget, prm.lp_max_iter) : prm.lp_max_iter;
@@ -1007,88 +1047,29 @@ LpResult Engine::lp_solve_core(double tol_p, double tol_g, int mode, bool identi
         double q[2 * kChkQ];
         lp_read_check(q);
         if (prm.profile) ev_flush();
-        const double dyAdx = q[0], dy2 = q[1], dobj_rows = q[2], dy0sq = q[3], yt2 = q[4], pviol = q[12];
-        const double dx2 = q[kChkQ + 5], pobj = q[kChkQ + 6] + obj_shift, dobj_cols = q[kChkQ + 7], dx0sq = q[kChkQ + 8],
-                     xt2 = q[kChkQ + 9], dres = q[kChkQ + 13];
-        const double dobj = dobj_rows + dobj_cols + obj_shift;
-        const double r2 = om / eta * dx2 - 2.0 * dyAdx + dy2 / (eta * om);
-        const double r = std::sqrt(std::max(r2, 0.0));
-        const double gap = std::fabs(pobj - dobj) / (1.0 + std::fabs(pobj) + std::fabs(dobj));
-        if (k == 0) { r0 = r; r_prev = r; }
+        const double dobj_rows = q[2], yt2 = q[4];
+        const PdhgSums S{q[0], q[1], q[3], q[kChkQ + 5], q[kChkQ + 8], q[kChkQ + 9], yt2,
+                         q[kChkQ + 6] + obj_shift, dobj_rows + q[kChkQ + 7] + obj_shift, q[12], q[kChkQ + 13]};
+        const PdhgStop t = pdhg_stop(S, rules, pc, om, eta, k);
         if (dbg_lp) std::fprintf(stderr, "[lp mode %d] it %7lld k %6lld r %.3e pviol %.3e dres %.3e gap %.3e pobj %.10g dobj %.10g om %.3g eta %.3g\n",
-                                 mode, (long long)it, (long long)k, r, pviol, dres, gap, pobj, dobj, om, eta);
-        R.pobj = pobj; R.dobj = dobj; R.row_viol = pviol; R.gap = gap;
-        R.dres_rel = dres * cinf_scale / (1.0 + std::sqrt(nc2_tol));
-        bool done = (pviol <= tol_p) && (gap <= tol_g) && (dres * cinf_scale <= tol_g * (1.0 + std::sqrt(nc2_tol)));
-        near_conv = (pviol <= 4.0 * tol_p) && (gap <= 4.0 * tol_g) && (dres * cinf_scale <= 4.0 * tol_g * (1.0 + std::sqrt(nc2_tol)));
-        primal_ok = (pviol <= tol_p) && (dres * cinf_scale <= tol_g * (1.0 + std::sqrt(nc2_tol)));
-        // Primal-stagnation exit (lp_stag_factor).  On LPs with degenerate duals the primal part converges within a few
-        // hundred iterations while the duality gap crawls for 10 000 more: stop when the rows are
-        // feasible to tol_p, the dual residual is converged, the primal objective has not moved by more than 0.4 tol_g
-        // over the last two checks, and the gap is certified to lp_stag_factor * tol_g.
-        {
-            // A model with free variables runs inside the box the presolve put around it (boundroutine, model.jl:175-197): a
-            // loosely solved LP can then sit ANYWHERE in that box, and cuts taken at |x| ~ 1e13 have constants of 1e31 that no
-            // first-order LP survives (fuzz model 2/109: primal weight 1e-30, objective 6e26, :Error).  Such models keep the
-            // conservative exit of round 2: three flat checks within 0.1 of the gap tolerance, gap certified to 100 tolerances.
-            const bool boxed_free = has_inf_bound;
-            const double stag = boxed_free ? std::min(prm.lp_stag_factor, 100.0) : prm.lp_stag_factor;
-            if (stag > 0.0 && mode == 0 && !done) {
-                const double scale = 1.0 + std::fabs(pobj);
-                // (flat over the last TWO checks; round 2 asked for three.  Most loose solves of the BASELINE shapes end here, and
-                //  the third confirmation was 64 more iterations each: -5 ... -7 % PDHG iterations on cfg3 / cfg2 / cfg4 over
-                //  96 / 32 / 8 seeds, objective errors, the 82 reference models, 240 fuzz models and the 48-shape matrix
-                //  unchanged.  KTN_STAG_CHECKS=3 restores the longer window.)
-                const int stag_checks = dev.stag_checks;
-                // ("flat" = within 0.4 tol_g; 0.1 until round 3.  The exit decides whether x* is a good separation point, not
-                //  the stop of the ECP loop, and tol_g itself is the accuracy asked of this solve: -12 % PDHG iterations on
-                //  cfg3 over 96 seeds, -9 % on cfg4, cfg2 unchanged, worst objective error 5e-7 of the 1e-6 allowed, the GPU
-                //  suite, fuzz set and shape matrix unchanged.  KTN_FLAT_FACTOR overrides.)
-                const double flat_f = dev.flat_factor;
-                const double ff = boxed_free ? std::min(flat_f, 0.1) : flat_f;
-                const int nchk = boxed_free ? 3 : stag_checks;
-                const bool flat = std::fabs(pobj - pobj_h[0]) <= ff * tol_g * scale && std::fabs(pobj - pobj_h[1]) <= ff * tol_g * scale &&
-                                  (nchk < 3 || std::fabs(pobj - pobj_h[2]) <= ff * tol_g * scale);
-                // (a row violation that sits on a plateau -- unchanged to 2 % over three checks -- within the stalled-row allowance
-                //  below counts as feasible here: cfg4 seed 2 idled 23 000 iterations at 3.098e-7 against tol_p = 3.0e-7 with the
-                //  objective flat and the gap at 3 tol_g, so that neither exit applied)
-                const double accept0 = (tol_p > prm.lp_tol_floor * prm.f_tol * (1.0 + 1e-9)) ? 10.0 : 3.0;
-                const bool plateau = pviol <= accept0 * tol_p && std::fabs(pviol - pviol_h[0]) <= 0.02 * pviol &&
-                                     std::fabs(pviol - pviol_h[1]) <= 0.02 * pviol && std::fabs(pviol - pviol_h[2]) <= 0.02 * pviol;
-                if (flat && (pviol <= tol_p || plateau) && gap <= stag * tol_g && dres * cinf_scale <= tol_g * (1.0 + std::sqrt(nc2_tol))) {
-                    done = true;
-                    R.stag_exit = true;
-                    stats["lp_stagnation_exits"] += 1.0;
-                }
-            }
-            // ... and its mirror image: objective, gap and dual residual converged, but ONE row stays violated by a hair more
-            // than tol_p for millions of iterations (multiplier mass idling between nearly parallel cuts, seen with dense
-            // epigraph cuts after the consolidation budget is spent: 3.47e-7 against tol_p = 3.0e-7 for 2.1e6 iterations).
-            // tol_p's floor is 0.3 f_tol -- a safety factor, the stop rule itself is the sweep at f_tol -- so a violation that
-            // has not moved by 2 % over three checks is accepted up to 3 tol_p (0.9 f_tol).  An INTERMEDIATE solve (tol_p above its floor:
-            // its x* only has to be a useful separation point, cuts are valid anywhere) accepts up to 10 tol_p -- the new cuts
-            // of the next sweep are what ends such a stall (263 000 iterations at 6.25e-2 against 3e-2 otherwise).
-            const double stall_accept = (tol_p > prm.lp_tol_floor * prm.f_tol * (1.0 + 1e-9)) ? 10.0 : 3.0;
-            if (stag > 0.0 && mode == 0 && !done && gap <= tol_g && dres * cinf_scale <= tol_g * (1.0 + std::sqrt(nc2_tol)) &&
-                pviol <= stall_accept * tol_p && std::fabs(pviol - pviol_h[0]) <= 0.02 * pviol && std::fabs(pviol - pviol_h[1]) <= 0.02 * pviol &&
-                std::fabs(pviol - pviol_h[2]) <= 0.02 * pviol) {
-                done = true;
-                stats["lp_stalled_row_exits"] += 1.0;
-            }
-            pviol_h[2] = pviol_h[1]; pviol_h[1] = pviol_h[0]; pviol_h[0] = pviol;
-            pobj_h[2] = pobj_h[1]; pobj_h[1] = pobj_h[0]; pobj_h[0] = pobj;
-        }
-        if (done || !(r == r)) {
-            R.status = done ? KTN_STATUS_OPTIMAL : KTN_STATUS_ERROR;
+                                 mode, (long long)it, (long long)k, t.r, S.pviol, S.dres, t.gap, S.pobj, S.dobj, om, eta);
+        R.pobj = S.pobj; R.dobj = S.dobj; R.row_viol = S.pviol; R.gap = t.gap;
+        R.dres_rel = S.dres / rules.dres_scale;
+        near_conv = t.near; primal_ok = t.primal_ok;
+        if (t.exit != PDHG_EXIT_NONE) {
+            if (t.exit == PDHG_EXIT_STAGNATION) { R.stag_exit = true; stats["lp_stagnation_exits"] += 1.0; }
+            if (t.exit == PDHG_EXIT_STALLED_ROW) stats["lp_stalled_row_exits"] += 1.0;
+            R.status = t.exit == PDHG_EXIT_NAN ? KTN_STATUS_ERROR : KTN_STATUS_OPTIMAL;
             ++it;
             break;
         }
         // primal infeasibility: yt is a Farkas certificate when the dual objective of the c = 0 problem is
         // positive (weak duality makes it <= 0 for every sign-valid y of a feasible LP).  Two checks in a row.
+        // (after the exits: the plateau exits accept a row violation above tol_p, which the certificate requires)
         if (mode == 0 && (m > 0 || row_sharded())) {     // (row-sharded: every quantity below is all-reduced, so all ranks agree)
             const double farkas = dobj_rows + q[kChkQ + 10];
             const double mag = q[10] + q[kChkQ + 11] + 1e-300;
-            const bool cert = farkas > 1e-6 * mag && q[kChkQ + 14] <= 1e-9 * (1.0 + std::sqrt(yt2)) && pviol > tol_p;
+            const bool cert = farkas > 1e-6 * mag && q[kChkQ + 14] <= 1e-9 * (1.0 + std::sqrt(yt2)) && S.pviol > tol_p;
             infeas_hits = cert ? infeas_hits + 1 : 0;
             if (infeas_hits >= 2 && it >= 2 * chk) {
                 R.status = KTN_STATUS_INFEASIBLE;
@@ -1096,87 +1077,28 @@ LpResult Engine::lp_solve_core(double tol_p, double tol_g, int mode, bool identi
                 break;
             }
         }
-        bool restart = k > 0 && (r <= 0.2 * r0 || (r <= 0.8 * r0 && r > r_prev) || (double)k >= 0.36 * (double)(it + 1));
-        const bool decayed = r <= 0.8 * r0;             // (a restart that the residual earned; the artificial one below is by the clock)
-        // step-size safeguard: a fixed-point residual that no longer moves (or a negative M-norm) while
-        // the LP is not solved means eta * sigma_max > 1 -> shrink eta and restart from the current point
-        if (k > 0 && eta > eta_safe * (1.0 + 1e-12)) {
-            stall = (r2 < 0.0 || (r_last_check > 0.0 && r > 0.97 * r_last_check && r < 1.03 * r_last_check)) ? stall + 1 : 0;
-            // ... and the other face of the same fault: the residual GROWS check after check, far above the residual the
-            // period started with (a non-expansive step never does that for long; seen on cfg3 seeds 28/29: r0 = 6 -> 87 -> 530
-            // -> 1e5 over 10 000 iterations until the flat-residual rule above finally fired).  Two growing checks above 5 r0.
-            grow = (r > 5.0 * r0 && r_last_check > 0.0 && r > r_last_check) ? grow + 1 : 0;
-            if (stall >= 3 || r2 < 0.0 || grow >= 2) {
-                eta = std::max(eta_safe, 0.85 * eta);
-                if (grow >= 2) stats["lp_divergence_backoffs"] += 1.0;
-                stall = 0; grow = 0;
-                restart = true;
-                stats["lp_eta_backoffs"] += 1.0;
-            }
+        const PdhgNext nx = pdhg_next(S, rules, pc, t, om, eta, k, it);
+        if (nx.backoff != PDHG_BACKOFF_NONE) stats["lp_eta_backoffs"] += 1.0;
+        if (nx.backoff == PDHG_BACKOFF_GROW) stats["lp_divergence_backoffs"] += 1.0;
+        eta = nx.eta;
+        if (nx.action == PDHG_CONSOLIDATE) {
+            // PDHG is idling between near-parallel cuts of one NL row (k_consolidate): move the multiplier mass onto the
+            // tightest cut at the current point and restart from there
+            stats["lp_consolidations"] += 1.0;
+            LAUNCH_1(k_unscale, n, stream, n, xth.p, dc.p, pv.p);
+            SpMat Au{lp_rowptr.p, lp_col.p, Wval()};
+            LAUNCH_G(grp_rows, k_spmv, m, stream, m, Au, pv.p, pw.p);
+            KTN_HIP(hipMemsetAsync(d_anynf.p + 1, 0, sizeof(int32_t), stream));
+            LAUNCH_1(k_consolidate, list_count(), stream, list_count(), list_heads(), d_cutprev.p, pw.p, Wlo(), Whi(), dr.p, tol_p, yth.p,
+                     d_anynf.p + 1);
         }
-        // objective converged, rows not, residual flat: PDHG is idling between near-parallel cuts of one
-        // NL row (k_consolidate).  Move the multiplier mass onto the tightest cut at the current point and
-        // restart from there.
-        // (row-sharded: the decision must not depend on what THIS rank holds -- a rank that consolidated while another did not
-        //  would leave the sequence of collectives -- so the local conditions are dropped; k_consolidate on a rank without cuts
-        //  is a no-op)
-        const bool have_lists = row_sharded() ? (prm.lp_dual_inherit != 0) : (prm.lp_dual_inherit && lists_ok() && list_count() > 0 && m > M_base);
-        if (mode == 0 && k > 0 && have_lists && gap <= tol_g &&
-            dres * cinf_scale <= tol_g * (1.0 + std::sqrt(nc2_tol)) && pviol > tol_p) {
-            flat_rows = (r_last_check > 0.0 && r > 0.98 * r_last_check) ? flat_rows + 1 : 0;
-            if (flat_rows >= 3 && consolidations < 8) {
-                flat_rows = 0;
-                ++consolidations;
-                stats["lp_consolidations"] += 1.0;
-                LAUNCH_1(k_unscale, n, stream, n, xth.p, dc.p, pv.p);
-                SpMat Au{lp_rowptr.p, lp_col.p, Wval()};
-                LAUNCH_G(grp_rows, k_spmv, m, stream, m, Au, pv.p, pw.p);
-                KTN_HIP(hipMemsetAsync(d_anynf.p + 1, 0, sizeof(int32_t), stream));
-                LAUNCH_1(k_consolidate, list_count(), stream, list_count(), list_heads(), d_cutprev.p, pw.p, Wlo(), Whi(), dr.p, tol_p, yth.p,
-                         d_anynf.p + 1);
-                lp_restart();
-                k = 0;
-                r_last_check = 0.0;
-                ++it;
-                continue;
+        if (nx.action != PDHG_ADVANCE) {
+            if (nx.action == PDHG_RESTART) {
+                if (dbg_lp) std::fprintf(stderr, "[lp restart] it %lld k %lld decayed %d dx %.3e dy %.3e |xt| %.3e |yt| %.3e om %.4g\n", (long long)it, (long long)k, (int)(t.r <= 0.8 * pc.r0), std::sqrt(S.dx0sq), std::sqrt(S.dy0sq), std::sqrt(S.xt2), std::sqrt(S.yt2), om);
+                stats["lp_restarts"] += 1.0;
             }
-        } else {
-            flat_rows = 0;
-        }
-        r_last_check = r;
-        r_prev = r;
-        if (restart) {
-            const double dx = std::sqrt(dx0sq), dy = std::sqrt(dy0sq);
-            if (dbg_lp) std::fprintf(stderr, "[lp restart] it %lld k %lld decayed %d dx %.3e dy %.3e |xt| %.3e |yt| %.3e om %.4g\n", (long long)it, (long long)k, (int)decayed, dx, dy, std::sqrt(xt2), std::sqrt(yt2), om);
-            // guarded primal-weight update (oracle/pdlp_mirror.py solve_lp_halpern)
-            const int om_art = dev.omega_art;
-            // Unearned restarts carry little information about the weight (round 4).  The update reads the ratio
-            // of the two movements since the last restart.  A solve's first restarts come "by the clock" (k >= 0.36 it: at the
-            // first check of every solve, after 32 iterations), whether or not the residual has moved.  After a warm start whose
-            // primal part is already converged (cfg2 seed 92: row violation 2e-7, dual objective 3e-4 away) x moves by 1e-6 of
-            // its norm in such a period -- the size of the tolerance -- and the ratio of that movement to the dual's sent the
-            // weight 603 -> 140 -> 13.8 -> 0.77 -> 0.16 in four restarts that had not reduced the residual at all; the solve then
-            // needed 44 000 iterations to earn it back.  (Tried first, and harmful: skipping the update below a relative movement
-            // of 10-100 gap tolerances -- any such floor also silences the early, loose solves, whose movements are small AND
-            // informative: cfg3 13 -> 36-85 cutting-plane rounds, profiles/r04_omega_ab.txt.)  Instead the weight of the new
-            // ratio in the geometric mean grows with the length of the period it was measured over: theta = 0.5 min(1, k / K)
-            // for a restart the residual did not earn (K = KTN_OMEGA_ART_K, 0 = the plain 0.5), 0.5 for an earned one.
-            const double om_art_k = dev.omega_art_k, om_art_clamp = dev.omega_art_clamp;
-            if ((om_art || decayed) && dx > 1e-8 * (1.0 + std::sqrt(xt2)) && dy > 1e-8 * (1.0 + std::sqrt(yt2))) {
-                const double om_clamp = dev.omega_clamp;
-                const double om_old = om;
-                // (models with free variables run inside the box the presolve put around them and keep the round-3 rule, like their
-                //  exit rules above: fuzz model 2/109 ends `:Error` -- a cut taken 1e13 from the origin -- under the damped update)
-                const double theta = (!decayed && om_art_k > 0.0 && !has_inf_bound) ? 0.5 * std::min(1.0, (double)k / om_art_k) : 0.5;
-                om = std::exp(theta * std::log(dy / dx) + (1.0 - theta) * std::log(om));
-                if (!decayed && om_art_clamp > 1.0) om = std::min(std::max(om, om_old / om_art_clamp), om_old * om_art_clamp);
-                const double om_clamp_dn = dev.omega_clamp_down;
-                if (om_clamp > 1.0) om = std::min(std::max(om, om_old / om_clamp), om_old * om_clamp);
-                if (om_clamp_dn > 1.0) om = std::max(om, om_old / om_clamp_dn);
-                om = std::min(std::max(om, omega_ref * 1e-3), omega_ref * 1e3);
-            }
+            om = nx.om;
             lp_restart();
-            stats["lp_restarts"] += 1.0;
             k = 0;
             ++it;
             continue;
@@ -1217,10 +1139,7 @@ void Engine::pdhg_raw(const double* x0, const double* y0, double eta, double ome
     compute_scaling(true);
     scaled_version = 0;                                  // (lp_solve_core must not take this identity scaling for its own)
     const int64_t n = n_lp, m = M;
-    const size_t mm = (size_t)std::max<int64_t>(m, 1);
-    ch.resize(n, stream); lh.resize(n, stream); uh.resize(n, stream); xh.resize(n, stream);
-    x0h.resize(n, stream); xth.resize(n, stream); xbar.resize(n, stream); pv.resize(n, stream);      // (pv: vector form of the x-step)
-    loh.resize(mm, stream); hih.resize(mm, stream); yh.resize(mm, stream); y0h.resize(mm, stream); yth.resize(mm, stream); pw.resize(mm, stream);
+    lp_resize_iterates();
     const double sgn = (sense == KTN_MAX) ? -1.0 : 1.0;
     KTN_HIP(hipMemcpyAsync(lp_x.p, x0, n * sizeof(double), hipMemcpyHostToDevice, stream));
     if (m > 0) KTN_HIP(hipMemcpyAsync(lp_y.p, y0, m * sizeof(double), hipMemcpyHostToDevice, stream));
@@ -1234,28 +1153,7 @@ void Engine::pdhg_raw(const double* x0, const double* y0, double eta, double ome
     KTN_HIP(hipMemcpyAsync(x0h.p, xh.p, n * sizeof(double), hipMemcpyDeviceToDevice, stream));
     if (m > 0) KTN_HIP(hipMemcpyAsync(y0h.p, yh.p, m * sizeof(double), hipMemcpyDeviceToDevice, stream));
     find_long_rows();
-    // LPs beyond the caches: tiled copies of A^ and A^' (kernels.hpp "tiled SpMV") serve the plain steps and the check
-    // iterations; the power iteration keeps the CSR / CSC kernels
-    {
-        const bool tenv = dev.tiled >= 0;
-        // ... and dense enough: every (tile, block) unit stages a 64 KB block of the input vector, so a matrix with few entries
-        // per unit pays more for the staging than for its entries (n = 1e6, 5.8e6 entries: 350 per unit, 1.31 s tiled against
-        // 0.49 s with the CSR kernels; cfg4: 9 500 per unit)
-        const int64_t units_t = ceil_div(M, (int64_t)kTileOut) * ceil_div(n_lp, (int64_t)kTileIn);
-        const int64_t units_tt = ceil_div(n_lp, (int64_t)kTileOut) * ceil_div(M, (int64_t)kTileIn);
-        tiled_on = prm.lp_tiled_nnz > 0 && NNZ >= prm.lp_tiled_nnz && n_lp >= 2 * kTileIn && M >= 2 * kTileIn &&
-                   NNZ >= 4096 * std::max(units_t, units_tt);
-        if (tenv) tiled_on = dev.tiled != 0 && M > 0 && NNZ > 0;
-        if (tiled_on) {
-            auto tt = std::chrono::steady_clock::now();
-            tiled_on = build_tiled(tA, M, n_lp, lp_rowptr.p, lp_col.p, r_sval.p, kLongRow) &&
-                       build_tiled(tAT, n_lp, M, c_ptr.p, c_row.p, c_sval.p, (int64_t)1 << 62);
-            tpart.resize((size_t)std::max<int64_t>(tA.pieces * M, tAT.pieces * n_lp), stream);
-            stats["lp_tiled_builds"] += 1.0;
-            stats["lp_tiled_build_time_s"] += std::chrono::duration<double>(std::chrono::steady_clock::now() - tt).count();
-            if (!tiled_on) stats["lp_tiled_overflows"] += 1.0;
-        }
-    }
+    lp_choose_tiled(false);                              // (scaled_version = 0 above: the next solve never reads tiled_built)
     const double tau = eta / omega_, sigma = eta * omega_;
     const double ky_bytes = (double)NNZ * 12 + 8.0 * (m + 1) + 8.0 * 5 * m + 8.0 * n;
     const double kx_bytes = (double)NNZ * 12 + 8.0 * (n + 1) + 8.0 * 7 * n + 8.0 * m;
@@ -1293,11 +1191,7 @@ void Engine::lp_script(const LpScriptIO& io) {
     compute_scaling(identity);
     scaled_version = 0;                                  // (lp_solve_core must not take this setup for its own)
     const int64_t n = n_lp, m = M;
-    const size_t mm = (size_t)std::max<int64_t>(m, 1);
-    ch.resize(n, stream); lh.resize(n, stream); uh.resize(n, stream); xh.resize(n, stream);
-    x0h.resize(n, stream); xth.resize(n, stream); xbar.resize(n, stream); pv.resize(n, stream);
-    loh.resize(mm, stream); hih.resize(mm, stream); yh.resize(mm, stream); y0h.resize(mm, stream);
-    yth.resize(mm, stream); pw.resize(mm, stream);
+    lp_resize_iterates();
     const double sgn = (sense == KTN_MAX) ? -1.0 : 1.0;
     auto prep = [&](const double* xs, const double* ys) {
         KTN_HIP(hipMemcpyAsync(lp_x.p, xs, n * sizeof(double), hipMemcpyHostToDevice, stream));
