@@ -351,6 +351,11 @@ int64_t ktn_lp_nnz(ktn_handle h);
 int ktn_lp_get_rows(ktn_handle h, int64_t* rowptr, int32_t* col, double* val,
                     double* lo, double* hi);
 int ktn_lp_get_objective(ktn_handle h, double* c_out, int64_t n, double* c0);
+/* Row multipliers of the last LP solve (> 0: the row's lower side, < 0: its upper side).  After a first-order solve or an exact
+ * solve of at most 32 columns: the solve's own multipliers.  After an exact mid-size solve (33 .. lp_mid_max_var columns) that ended
+ * optimal, for as long as no row is appended, purged or truncated and no other solve runs: the multipliers of the LP's own cost at
+ * the vertex returned, computed on this call; the cutting-plane loop itself keeps those of the solver's perturbed cost, which
+ * differ by the perturbation (1e-9 (1 + |c_j|) per column) and are what this call returns in every other state. */
 int ktn_lp_get_duals(ktn_handle h, double* y_out, int64_t m);
 /* solve the current LP to the given tolerances (tests / tools):
  * row_tol = max unscaled row violation, gap_tol = relative duality gap */

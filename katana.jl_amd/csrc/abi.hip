@@ -271,7 +271,8 @@ int ktn_lp_get_duals(ktn_handle h, double* y_out, int64_t m) {
     KTN_TRY(h, {
         Engine* e = h->eng;
         KTN_REQUIRE(e->loaded && m >= e->M, "dual buffer too small");
-        e->lp_y.download(y_out, (size_t)e->M, e->stream);
+        // after an exact mid-size solve: the multipliers of the LP's own cost, not of the perturbed one the pivoting keeps (mid_lp.hpp)
+        if (e->dev.raw_duals || !e->mid_true_duals(y_out)) e->lp_y.download(y_out, (size_t)e->M, e->stream);
         return KTN_OK;
     })
 }

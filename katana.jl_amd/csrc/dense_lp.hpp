@@ -24,7 +24,24 @@
 namespace ktn {
 
 constexpr int kDenseMaxN = 32;
+// Variable bounds and kDenseBig.  A bound with |b| >= kDenseBig is taken for a stand-in for "none" (1e20 and the like): this kernel
+// and mid_lp.hpp give such a side an artificial side at 0 that may only leave, and never price the bound itself.  For a FINITE
+// bound that is a relaxation of the LP, so:  "infeasible" stays true;  an optimum of the relaxation is the LP's optimum exactly
+// when it respects the bounds that were left out.  The exact paths therefore check those bounds at the point they return
+// (k_big_bounds_check, Engine::big_bounds_hold; only LPs that have such a bound pay for it) and an answer that breaks one is a
+// failed exact solve: a counted fall-back, the first-order method -- which knows every bound -- takes over.  (Before: min x0,
+// x0 <= 2e7, row x0 >= 2.5e7 came back "Optimal" at x0 = 2.5e7 from both solvers.)
 constexpr double kDenseBig = 1e7;
+
+static __global__ __launch_bounds__(256) void k_big_bounds_check(int n, const double* __restrict__ x, const double* __restrict__ l,
+                                                                 const double* __restrict__ u, int32_t* __restrict__ bad) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const double xj = x[j], lj = l[j], uj = u[j];
+    const bool up = uj >= kDenseBig && uj < __builtin_inf() && xj > uj + 1e-9 * uj;
+    const bool lw = -lj >= kDenseBig && -lj < __builtin_inf() && xj < lj + 1e-9 * lj;
+    if (up || lw) *bad = 1;
+}
 
 struct DenseLpIO {
     int n;

@@ -89,6 +89,8 @@ struct DevParams {
     double omega_art_k = 256.0;    // KTN_OMEGA_ART_K      period length at which such a restart's ratio gets the full weight 0.5
     double omega_art_clamp = 0.0, omega_clamp = 0.0, omega_clamp_down = 0.0;   // KTN_OMEGA_ART_CLAMP / _CLAMP / _CLAMP_DOWN (measured, off)
     double ipc_timeout_s = 20.0;   // KTN_IPC_TIMEOUT_S    spin bound of the peer-buffer transport
+    bool raw_duals = false;        // KTN_RAW_DUALS        ktn_lp_get_duals returns lp_y as the loop sees it, also after an exact mid-size solve
+    int mid_refactor = 0;          // KTN_MID_REFACTOR     pivots between refactorisations of the mid-size exact LP (<= 0: kMidRefactor, mid_lp.hpp)
     static bool flag(const char* k) { return std::getenv(k) != nullptr; }
     static int geti(const char* k, int d) { const char* v = std::getenv(k); return v ? std::atoi(v) : d; }
     static double getd(const char* k, double d) { const char* v = std::getenv(k); return v ? std::atof(v) : d; }
@@ -110,6 +112,7 @@ struct DevParams {
         omega_art = geti("KTN_OMEGA_ART", omega_art); omega_art_k = getd("KTN_OMEGA_ART_K", omega_art_k);
         omega_art_clamp = getd("KTN_OMEGA_ART_CLAMP", omega_art_clamp); omega_clamp = getd("KTN_OMEGA_CLAMP", omega_clamp);
         omega_clamp_down = getd("KTN_OMEGA_CLAMP_DOWN", omega_clamp_down); ipc_timeout_s = getd("KTN_IPC_TIMEOUT_S", ipc_timeout_s);
+        mid_refactor = geti("KTN_MID_REFACTOR", mid_refactor); raw_duals = flag("KTN_RAW_DUALS");
     }
 };
 
@@ -129,6 +132,7 @@ struct Engine {
     int sense = KTN_MIN;
     bool obj_linear = true;
     bool has_inf_bound = false;
+    bool has_big_bound = false;    // a FINITE variable bound with |b| >= kDenseBig: the exact LP paths leave it out and check it afterwards (dense_lp.hpp)
     std::vector<int64_t> h_rowptr;
     std::vector<int32_t> h_col;
     std::vector<uint8_t> h_rowkind;
@@ -284,6 +288,9 @@ struct Engine {
     // exact mid-size LP (mid_lp.hpp): basis inverse, working set, x and multipliers persist across the ECP iterations
     DBuf<double> md_Binv, md_hW, md_x, md_lam, md_u, md_d, md_r, md_pv, md_c, md_aug, md_prow, md_fcol;
     int64_t md_since_refactor = 0;
+    DBuf<double> md_y;                  // scratch of mid_true_duals: row multipliers of the TRUE cost (lp_y: those of the perturbed cost)
+    uint64_t md_y_version = 0;          // lp_version of the last exact mid-size solve that ended optimal (0: none, or another solve since)
+    bool mid_true_duals(double* y_out); // ktn_lp_get_duals while that solve's rows and working set stand
     int64_t mid_backoff = 0, mid_backoff_len = 0;      // after a failed exact solve the first-order method carries on alone for a while
     DBuf<int32_t> md_W, md_pi, md_lost;
     DBuf<MidState> md_st;
@@ -623,6 +630,7 @@ struct Engine {
     LpResult lp_solve(double tol_p, double tol_g, int mode, bool identity_scaling = false);
     LpResult lp_solve_core(double tol_p, double tol_g, int mode, bool identity_scaling);
     bool lp_solve_dense(LpResult* R);
+    bool big_bounds_hold();            // lp_x respects the finite bounds beyond kDenseBig that the exact paths left out
     bool lp_solve_mid(LpResult* R);
     void pdhg_raw(const double* x0, const double* y0, double eta, double omega_, int64_t iters, double* x_out,
                   double* y_out);

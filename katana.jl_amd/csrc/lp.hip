@@ -438,6 +438,7 @@ bool Engine::launch_check(const SpMat& A, const SpMat& AT, double tau, double si
 // columns, the exact kernel finishes the solve; each stall doubles the number of following solves that go to
 // the exact kernel directly.
 LpResult Engine::lp_solve(double tol_p, double tol_g, int mode, bool identity_scaling) {
+    md_y_version = 0;                                    // (set again by an exact mid-size solve that ends optimal)
     const bool dense_ok = mode == 0 && !identity_scaling && !row_sharded() && prm.lp_dense_after != 0 && n_lp >= 1 && n_lp <= kDenseMaxN &&
                           M * n_lp <= 8000000;
     // ... and LPs of 33 .. lp_mid_max_var columns by the exact mid-size solver (mid_lp.hpp), under the same hand-over rule
@@ -503,8 +504,10 @@ LpResult Engine::lp_solve(double tol_p, double tol_g, int mode, bool identity_sc
 }
 
 // Exact solve of a small LP by the dual active-set kernel (dense_lp.hpp).  Returns false when the kernel
-// gives up (singular working set, pivot limit, or an artificial bound left in the optimal working set, i.e.
-// the optimal face is unbounded in some zero-cost direction): the caller then runs the first-order method.
+// gives up (singular working set, pivot limit, an artificial side that still carries a multiplier with no real side to stop
+// at -- the LP is unbounded along it; an artificial side left with a ZERO multiplier, i.e. an optimal face unbounded in a
+// zero-cost direction, is no failure --, or an optimum that breaks a finite bound beyond kDenseBig): the caller then runs
+// the first-order method.
 bool Engine::lp_solve_dense(LpResult* R) {
     auto t0 = std::chrono::steady_clock::now();
     const int n = (int)n_lp;
@@ -534,6 +537,10 @@ bool Engine::lp_solve_dense(LpResult* R) {
     stats["lp_solves"] += 1.0;
     stats["lp_time_s"] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     const int st = (int)out[0];
+    if (st == 0 && !big_bounds_hold()) {                 // optimal for the LP without its bounds beyond kDenseBig only
+        ds_valid.zero(stream);
+        return false;
+    }
     if (st == 0) {
         R->status = KTN_STATUS_OPTIMAL;
         R->iters = (int64_t)out[1];
@@ -549,6 +556,46 @@ bool Engine::lp_solve_dense(LpResult* R) {
         return true;
     }
     return false;
+}
+
+// The finite variable bounds beyond kDenseBig, which the exact solvers treat as absent (dense_lp.hpp), at the point in lp_x.
+bool Engine::big_bounds_hold() {
+    if (!has_big_bound) return true;
+    int32_t bad = 0;
+    KTN_HIP(hipMemsetAsync(d_anynf.p + 3, 0, sizeof(int32_t), stream));
+    hipLaunchKernelGGL(k_big_bounds_check, dim3((unsigned)ceil_div(n_lp, 256)), dim3(256), 0, stream, (int)n_lp, lp_x.p, lp_l.p, lp_u.p, d_anynf.p + 3);
+    check_launch();
+    KTN_HIP(hipMemcpyAsync(&bad, d_anynf.p + 3, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    sync();
+    if (bad) stats["lp_big_bound_rejects"] += 1.0;
+    return bad == 0;
+}
+
+// the solver's view of the LP and of its own persistent state
+static MidLpIO mid_io(Engine* e) {
+    MidLpIO P;
+    P.n = (int)e->n_lp; P.m = e->M; P.rowptr = e->lp_rowptr.p; P.col = e->lp_col.p; P.val = e->lp_val.p; P.lo = e->lp_lo.p; P.hi = e->lp_hi.p;
+    P.l = e->lp_l.p; P.u = e->lp_u.p; P.c = e->lp_c.p; P.sgn = (e->sense == KTN_MAX) ? -1.0 : 1.0;
+    P.Binv = e->md_Binv.p; P.W = e->md_W.p; P.hW = e->md_hW.p; P.x = e->md_x.p; P.lam = e->md_lam.p; P.uvec = e->md_u.p; P.dvec = e->md_d.p; P.rvec = e->md_r.p;
+    P.part_val = e->md_pv.p; P.part_idx = e->md_pi.p; P.st = e->md_st.p; P.ctil = e->md_c.p;
+    P.tol = 1e-9; P.max_pivots = 0;
+    return P;
+}
+
+// ktn_lp_get_duals after an exact mid-size solve whose rows and working set still stand: the multipliers of the LP's own cost
+// (mid_lp.hpp k_mid_true_duals), not those of the perturbed cost that lp_y holds for the loop.  false: nothing to add to lp_y.
+bool Engine::mid_true_duals(double* y_out) {
+    if (!md_valid || md_y_version == 0 || md_y_version != lp_version || md_W.n != (size_t)n_lp) return false;
+    MidLpIO P = mid_io(this);
+    const size_t mm = (size_t)std::max<int64_t>(M, 1);
+    md_y.resize(mm, stream);
+    KTN_HIP(hipMemsetAsync(md_y.p, 0, mm * sizeof(double), stream));
+    const unsigned g_n = (unsigned)ceil_div(P.n, 256);
+    hipLaunchKernelGGL(k_mid_lambda, dim3(g_n), dim3(256), 0, stream, P, 1);
+    hipLaunchKernelGGL(k_mid_true_duals, dim3(g_n), dim3(256), 0, stream, P, md_y.p);
+    check_launch();
+    md_y.download(y_out, (size_t)M, stream);
+    return true;
 }
 
 // Exact solve of a mid-size LP (mid_lp.hpp): batches of pivots enqueued without a host synchronisation, the device-resident
@@ -567,11 +614,7 @@ bool Engine::lp_solve_mid(LpResult* R) {
     }
     lp_y.resize((size_t)std::max<int64_t>(m, 1), stream);
     lp_y.n = (size_t)m;
-    MidLpIO P;
-    P.n = n; P.m = m; P.rowptr = lp_rowptr.p; P.col = lp_col.p; P.val = lp_val.p; P.lo = lp_lo.p; P.hi = lp_hi.p;
-    P.l = lp_l.p; P.u = lp_u.p; P.c = lp_c.p; P.sgn = (sense == KTN_MAX) ? -1.0 : 1.0;
-    P.Binv = md_Binv.p; P.W = md_W.p; P.hW = md_hW.p; P.x = md_x.p; P.lam = md_lam.p; P.uvec = md_u.p; P.dvec = md_d.p; P.rvec = md_r.p;
-    P.part_val = md_pv.p; P.part_idx = md_pi.p; P.st = md_st.p; P.ctil = md_c.p;
+    MidLpIO P = mid_io(this);
     P.tol = 1e-9;
     // (a cold start from the bound vertex of a cutting-plane LP that the first-order method has already grown to a few thousand
     //  rows takes tens of pivots per column -- every variable leaves its box corner, many of them more than once; the warm
@@ -585,7 +628,7 @@ bool Engine::lp_solve_mid(LpResult* R) {
         hipLaunchKernelGGL(k_mid_apply, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, stream, P, 1);
         hipLaunchKernelGGL(k_mid_resid, dim3(g_n), dim3(256), 0, stream, P, 1);
         hipLaunchKernelGGL(k_mid_resid_norm, dim3(1), dim3(256), 0, stream, P, 1);
-        hipLaunchKernelGGL(k_mid_lambda, dim3(g_n), dim3(256), 0, stream, P);
+        hipLaunchKernelGGL(k_mid_lambda, dim3(g_n), dim3(256), 0, stream, P, 0);
     };
     // B^-1 afresh from the working set (mid_lp.hpp "refactorisation"), then x and lambda from their definitions
     auto refactor = [&]() {
@@ -603,6 +646,7 @@ bool Engine::lp_solve_mid(LpResult* R) {
         md_since_refactor = 0;
         stats["mid_lp_refactors"] += 1.0;
     };
+    const int64_t refactor_every = dev.mid_refactor > 0 ? dev.mid_refactor : kMidRefactor;      // (KTN_MID_REFACTOR: tests reach the refactorisation on small LPs)
     MidState hs;
     int total_pivots = 0, status = 4;
     for (int attempt = 0; attempt < 2; ++attempt) {
@@ -612,7 +656,7 @@ bool Engine::lp_solve_mid(LpResult* R) {
             md_since_refactor = 0;
         } else {
             hipLaunchKernelGGL(k_mid_rearm, dim3(1), dim3(1), 0, stream, md_st.p);
-            if (md_since_refactor >= kMidRefactor) refactor();
+            if (md_since_refactor >= refactor_every) refactor();
         }
         int refined_at = -1, refinements = 0, pivots_seen = 0;
         bool bad_inverse = false;
@@ -632,7 +676,7 @@ bool Engine::lp_solve_mid(LpResult* R) {
             pivots_seen = hs.pivots;
             if (hs.gj_singular) { bad_inverse = true; break; }            // the working set itself is (numerically) dependent: cold start
             if (hs.status == 0) {
-                if (md_since_refactor >= kMidRefactor) refactor();
+                if (md_since_refactor >= refactor_every) refactor();
                 continue;
             }
             if (hs.status == 1) {
@@ -665,7 +709,7 @@ bool Engine::lp_solve_mid(LpResult* R) {
         KTN_HIP(hipMemcpyAsync(&hs, md_st.p, sizeof(hs), hipMemcpyDeviceToHost, stream));
         check_launch();
         sync();
-        if (hs.art_left == 0) {
+        if (hs.art_left == 0 && big_bounds_hold()) {
             R->status = KTN_STATUS_OPTIMAL;
             R->iters = total_pivots;
             R->pobj = R->dobj = hs.obj;
@@ -673,6 +717,7 @@ bool Engine::lp_solve_mid(LpResult* R) {
             R->exact = true;
             objval = P.sgn * hs.obj + c0;
             md_valid = true;
+            md_y_version = lp_version;
             ok = true;
         } else {
             md_valid = false;

@@ -349,13 +349,23 @@ static __global__ __launch_bounds__(256) void k_mid_apply(MidLpIO P, int accumul
     acc = group_sum<64>(acc);
     if (lane == 0) P.x[j] = accumulate ? P.x[j] + acc : acc;
 }
-// lambda_r = -sum_j Binv[j][r] s c_j (coalesced over r), clamped at 0
-static __global__ __launch_bounds__(256) void k_mid_lambda(MidLpIO P) {
+// lambda_r = -sum_j Binv[j][r] s c_j (coalesced over r), clamped at 0.  true_cost = 0: with the perturbed cost the pivoting works
+// with, into lam.  true_cost = 1: with the cost of the LP itself, into uvec (free once the pivoting is over) -- the multipliers that
+// k_mid_true_duals scatters for ktn_lp_get_duals.  Those of the perturbed cost miss dual feasibility for the true one by the perturbation, 1e-9 (1 + |c_j|)
+// per column, and every basic column then costs the dual bound that much times its distance from its box: a duality gap of
+// 7e-7 at 33 columns to 1.2e-5 at 512 on boxes of +-10 (measured with exact rational arithmetic, tests/exact_lp_ref.py), where the
+// x returned is optimal to 1e-13.
+static __global__ __launch_bounds__(256) void k_mid_lambda(MidLpIO P, int true_cost) {
     const int r = blockIdx.x * 256 + threadIdx.x;
     if (r >= P.n) return;
     double acc = 0.0;
-    for (int j = 0; j < P.n; ++j) acc += P.Binv[(int64_t)j * P.n + r] * P.ctil[j];
-    P.lam[r] = fmax(-acc, 0.0);
+    if (true_cost) {
+        for (int j = 0; j < P.n; ++j) acc += P.Binv[(int64_t)j * P.n + r] * (P.sgn * P.c[j]);
+        P.uvec[r] = fmax(-acc, 0.0);
+    } else {
+        for (int j = 0; j < P.n; ++j) acc += P.Binv[(int64_t)j * P.n + r] * P.ctil[j];
+        P.lam[r] = fmax(-acc, 0.0);
+    }
 }
 static __global__ void k_mid_rearm(MidState* st) { st->status = 0; st->pivots = 0; st->degen_run = 0; st->art_left = 0; st->p = -1; st->gj_singular = 0; }
 // max |rvec| into st->resid, and back to "running" for the confirming price
@@ -370,7 +380,9 @@ static __global__ __launch_bounds__(256) void k_mid_resid_norm(MidLpIO P, int re
     if (t == 0) { P.st->resid = sv[0]; if (rearm && P.st->status == 1) P.st->status = 0; }
 }
 
-// outputs: row multipliers in the engine's convention (> 0 lower side, < 0 upper side), objective, leftover artificial sides
+// outputs: row multipliers in the engine's convention (> 0 lower side, < 0 upper side), objective, leftover artificial sides.
+// The multipliers are those of the perturbed cost the pivoting worked with: what the cutting-plane loop consumes (dual inheritance,
+// purge, certificate).  Those of the TRUE cost are computed only when ktn_lp_get_duals asks for them (k_mid_true_duals below).
 static __global__ __launch_bounds__(256) void k_mid_final(MidLpIO P, double* y) {
     __shared__ double sv[256];
     __shared__ int s_art;
@@ -397,6 +409,17 @@ static __global__ __launch_bounds__(256) void k_mid_final(MidLpIO P, double* y) 
     }
     __syncthreads();
     if (t == 0) { P.st->obj = sv[0]; P.st->art_left = s_art; }
+}
+
+// The row multipliers of the TRUE cost, after k_mid_lambda(P, 1) left -B^-T s c in uvec (yt zeroed by the caller).  Engine::
+// mid_true_duals runs the pair when ktn_lp_get_duals is called after an exact solve, while its rows and working set stand; a
+// solve itself pays nothing for it.  (Feeding these to the loop instead of k_mid_final's was tried and is not done: Kelley's round
+// counts on the smooth-face models are sensitive to it -- quad, n = 100, half pinned: 371 -> 2 175 rounds.)
+static __global__ __launch_bounds__(256) void k_mid_true_duals(MidLpIO P, double* yt) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= P.n) return;
+    const int k = P.W[r];
+    if (k >= 0) yt[k >> 1] = (k & 1) ? P.uvec[r] : -P.uvec[r];
 }
 
 // ---- refactorisation: B^-1 afresh from the working set ----------------------------------------------------------------

@@ -9,6 +9,7 @@
 #include "quad_rows.hpp"
 #include "batch_lp.hpp"
 #include "batch_ecp.hpp"
+#include "dense_lp.hpp"
 
 namespace ktn {
 
@@ -582,6 +583,9 @@ void Engine::loadproblem(int64_t num_var, int64_t num_constr, const double* l_va
     has_inf_bound = false;
     for (int64_t j = 0; j < n_lp; ++j)
         if (!std::isfinite(lv[j]) || !std::isfinite(uv[j])) has_inf_bound = true;
+    has_big_bound = false;
+    for (int64_t j = 0; j < n_lp; ++j)
+        if ((std::isfinite(uv[j]) && uv[j] >= kDenseBig) || (std::isfinite(lv[j]) && -lv[j] >= kDenseBig)) has_big_bound = true;
 
     lapl("tapes, bounds, nl list");
     // ---- upload the NLP
