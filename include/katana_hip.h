@@ -310,6 +310,45 @@ int64_t ktn_numiters(ktn_handle h);
 int64_t ktn_numcuts(ktn_handle h);
 int     ktn_setwarmstart(ktn_handle h, const double* x, int64_t n);
 
+/* ---- Lagrange multipliers, reduced costs and a dual bound of the solved NLP (MathProgBase.getconstrduals / getreducedcosts /
+ * getobjbound; no counterpart in the reference, which returns none) ------
+ * Problem, sense Min:  min f(x)  s.t.  lb_i <= g_i(x) <= ub_i (i < num_constr),  l <= x <= u, x the caller's num_var variables
+ * (the epigraph variable and row are internal and never reported).  x* = what ktn_get_solution returns.
+ *
+ *   d[num_constr]  constraint duals in the caller's row order, signed like ktn_lp_get_duals: d_i > 0 the lower side is active,
+ *                  d_i < 0 the upper side (d_i = d f* / d bound_i).  A linear row of the loaded LP: the multiplier of its own LP
+ *                  row.  An NL row: the sum of the multipliers of the cuts now in its list, newest to oldest; 0 for an empty list.
+ *                  The LP multipliers are those ktn_lp_get_duals returns (unscaled; after an exact mid-size solve: of the true cost).
+ *   z[num_var]     reduced costs = the gradient of the Lagrangian at x*:  z = grad f(x*) - J(x*)' d,  J the Jacobian of all
+ *                  num_constr rows at x*, grad f the objective row's own Jacobian entries with weight exactly 1.  At a KKT point
+ *                  z_j >= 0 on a lower bound, <= 0 on an upper bound, 0 in between.
+ *   bound          with d+ = max(d, 0), d- = max(-d, 0), likewise z:
+ *                    LB = f(x*) - sum_i d+_i (g_i(x*) - lb_i) + sum_i d-_i (g_i(x*) - ub_i) - sum_j [z+_j (x*_j - l_j) + z-_j (u_j - x*_j)]
+ *                  For a convex problem LB <= f* for ANY d (the Lagrangian is convex in x, bounded below by its tangent at x*, and
+ *                  the tangent is minimised over the box).  An infinite bound under a non-zero multiplier of that side makes
+ *                  LB = -inf; 0 * inf counts as 0.  gap = f(x*) - LB.
+ *   sense Max      the three are those of the mirrored Min problem, mirrored back: d and z negated (d stays d f* / d bound), the
+ *                  bound is an upper bound, gap = bound - f(x*).
+ *
+ * The three getters compute once (on the first call) and cache; a solve that is followed by no getter launches nothing for them.
+ * The cached values are dropped -- the next getter computes again -- by ktn_loadproblem, ktn_reset, any LP solve and any change
+ * of the LP rows, whoever makes it.  Whether the getters ANSWER is a separate rule: KTN_E_INVALID (with a message) while no LP
+ * solve has run since the problem was loaded or reset, or since the CALLER last changed the rows through ktn_lp_append_rows[_nl],
+ * ktn_lp_append_packed_dev, ktn_lp_truncate or ktn_lp_purge (a call of these counts whether or not it changed a row).  Rows
+ * that the engine itself appends or purges -- inside ktn_optimize*, ktn_ecp_step, ktn_sep_sweep, ktn_sweep_lp_point -- do NOT make
+ * the getters refuse: a purge compacts the multipliers with the rows and relinks the lists, a new cut starts at 0 or takes over
+ * the multiplier of its list's previous cut, so every NL row's sum is still that of the last LP solve (the answer is then
+ * recomputed from that state, not served from the cache).  KTN_E_UNSUPPORTED on a row-sharded handle
+ * (ktn_dist_init_*) or one with a cut exchange: it owns only a part of the lists.  One handle with ktn_lp_enable_global_lists is
+ * served from those lists.  After ktn_optimize_blocks[_ex] that ended in the device loop the multipliers and lists are the
+ * arenas'; after its fallback to the ordinary loop the ordinary state's.  m >= num_constr, n >= num_var (buffers too small:
+ * KTN_E_INVALID).  KTN_ROW_HOST rows: the caller's callback runs once per computation.
+ * Stats: "kkt_evals" times the kernels ran; "kkt_epi_dual" the aggregated multiplier of the epigraph row (a diagnostic: +-1 in an
+ * exact LP, NaN for a linear objective). */
+int ktn_get_constr_duals(ktn_handle h, double* d_out, int64_t m);
+int ktn_get_reduced_costs(ktn_handle h, double* z_out, int64_t n);
+int ktn_get_dual_bound(ktn_handle h, double* bound, double* gap);
+
 /* ---- supporting-hyperplane cuts (cut_algo = KTN_CUT_SUPPORTING or KTN_CUT_SUPPORTING_QUAD) ------
  * The interior point x_int [num_var, without the epigraph variable]: ktn_set_interior_point hands one over (NULL clears
  * it, and the engine then looks for one itself when it next needs it); ktn_loadproblem forgets it, ktn_reset keeps it.
@@ -517,6 +556,14 @@ int ktn_blocks_get_results(ktn_handle h, double* out, int64_t cap, int64_t* coun
  * cap_rows >= *n_rows (rowptr: cap_rows + 1) and cap_nnz >= *n_nnz.  KTN_E_INVALID before any device launch on the loaded problem. */
 int ktn_blocks_get_cuts(ktn_handle h, int64_t block, int64_t* rowptr, int32_t* col, double* val, double* lo, double* hi,
                         int64_t* nl_slot, double* lambda, int64_t cap_rows, int64_t cap_nnz, int64_t* n_rows, int64_t* n_nnz);
+/* The multiplier of each cut row of instance `block` after the last device launch, row for row as in ktn_blocks_get_cuts, unscaled
+ * (the arenas keep the multipliers unscaled between LP solves: y = y^ dr).  y_out == NULL only reports *count. */
+int ktn_blocks_get_duals(ktn_handle h, int64_t block, double* y_out, int64_t cap, int64_t* count);
+/* The dual bound of ktn_get_dual_bound per instance of a fused batch (ktn_set_blocks; rows and columns grouped by instance):
+ * out[2 b] = bound of instance b from its own rows, columns and share c_b'x_b of the objective (without the loaded problem's
+ * constant), out[2 b + 1] = its gap.  One workgroup per instance.  States and errors as ktn_get_dual_bound; out == NULL only
+ * reports *count = 2 n_blocks. */
+int ktn_blocks_get_dual_bounds(ktn_handle h, double* out, int64_t cap, int64_t* count);
 
 /* ---- row-sharded LP over several GPUs (no reference counterpart: it splits the LP re-solve of
  * src/model.jl:259 and the cut loop of :272-283 over the ranks) -------------------------------------------------------

@@ -79,6 +79,11 @@ PROTOTYPES = {
     "ktn_numiters": (c_i64, [C.c_void_p]),
     "ktn_numcuts": (c_i64, [C.c_void_p]),
     "ktn_setwarmstart": (c_i32, [C.c_void_p, P(c_f64), c_i64]),
+    "ktn_get_constr_duals": (c_i32, [C.c_void_p, P(c_f64), c_i64]),
+    "ktn_get_reduced_costs": (c_i32, [C.c_void_p, P(c_f64), c_i64]),
+    "ktn_get_dual_bound": (c_i32, [C.c_void_p, P(c_f64), P(c_f64)]),
+    "ktn_blocks_get_duals": (c_i32, [C.c_void_p, c_i64, P(c_f64), c_i64, P(c_i64)]),
+    "ktn_blocks_get_dual_bounds": (c_i32, [C.c_void_p, P(c_f64), c_i64, P(c_i64)]),
     "ktn_set_interior_point": (c_i32, [C.c_void_p, P(c_f64), c_i64]),
     "ktn_get_interior_point": (c_i32, [C.c_void_p, P(c_f64), c_i64, P(c_i32)]),
     "ktn_sep_precompute": (c_i32, [C.c_void_p, P(c_f64), c_i64]),

@@ -175,6 +175,51 @@ class FusedBatch:
         return [dict(common, objval=float(seg[k] + inst.obj_const), x=x[offs[k]:offs[k + 1]]) for k, inst in enumerate(self.instances)]
 
 
+    # ---- Lagrange multipliers, reduced costs, dual bounds per instance ----
+    def _row_ranges(self):
+        """per instance: the index arrays of its rows in the fused problem, in the instance's own row order (the epigraph row
+        that fusion gave a quadratic objective left out), and its sign (+1 Min, -1 Max: fusion negates a Max objective)"""
+        import numpy as np
+        if self._objinfo is None:                                  # fuse_instances: linear rows of every instance, then the NL rows
+            lo = np.concatenate([[0], np.cumsum([i.m_lin for i in self.instances])])
+            no = np.concatenate([[0], np.cumsum([i.m_nl for i in self.instances])]) + lo[-1]
+            return [(np.concatenate([np.arange(lo[k], lo[k + 1]), np.arange(no[k], no[k + 1])]), 1.0) for k in range(len(self.instances))]
+        probs = [_as_problem(i) for i in self.instances]           # fuse_problems: rows instance after instance
+        epi = [int(self.offs[k + 1] - self.offs[k]) - self._nvar[k] for k in range(len(probs))]
+        ro = np.concatenate([[0], np.cumsum([int(p.num_constr) + e for p, e in zip(probs, epi)])])
+        return [(np.arange(ro[k], ro[k] + int(p.num_constr)), -1.0 if p.sense == "Max" else 1.0) for k, p in enumerate(probs)]
+
+    def constr_duals(self):
+        """one array per instance: its constraint duals in its own row order and sense (KatanaNonlinearModel.getconstrduals)"""
+        d = self.m.getconstrduals()
+        return [sgn * d[idx] for idx, sgn in self._row_ranges()]
+
+    def reduced_costs(self):
+        """one array per instance: the reduced costs of its own variables, in its own sense"""
+        z = self.m.getreducedcosts()
+        nv = self._nvar if self._objinfo is not None else [int(self.offs[k + 1] - self.offs[k]) for k in range(len(self.instances))]
+        return [sgn * z[int(self.offs[k]):int(self.offs[k]) + int(nv[k])] for k, (_, sgn) in enumerate(self._row_ranges())]
+
+    def dual_bounds(self):
+        """[(bound, gap)] per instance, in its own sense and with its own objective constant: instance k's share of the fused
+        bound from its rows and columns alone (k_dual_bound, one workgroup per instance).  A batch solved by the host loop has no
+        blocks set: they are set for the call and cleared again."""
+        m = self.m
+        temp = not (self.per_instance_lp or self.device_loop)
+        if temp:
+            m.set_blocks(self.offs)
+        try:
+            bg = m.blocks_dual_bounds()
+        finally:
+            if temp:
+                m.set_blocks([0])
+        out = []
+        for k, (_, sgn) in enumerate(self._row_ranges()):
+            c0 = float(self._objinfo[k][2]) if self._objinfo is not None else float(self.instances[k].obj_const)
+            out.append((sgn * float(bg[k, 0]) + c0, float(bg[k, 1])))
+        return out
+
+
 def _solve_fused(solver, instances, per_instance_lp=False, device_loop=False):
     t0 = time.perf_counter()
     out = FusedBatch(solver, instances, per_instance_lp, device_loop).solve()

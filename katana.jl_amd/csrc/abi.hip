@@ -124,6 +124,36 @@ int ktn_setwarmstart(ktn_handle h, const double* x, int64_t n) {   // src/model.
     return (h && h->eng) ? KTN_OK : KTN_E_INVALID;
 }
 
+// ---- Lagrange multipliers, reduced costs, dual bound (Engine::kkt_compute, sweep.hip: computed on the first call, cached)
+int ktn_get_constr_duals(ktn_handle h, double* d_out, int64_t m) {
+    KTN_TRY(h, {
+        Engine* e = h->eng;
+        KTN_REQUIRE(e->loaded && d_out && m >= e->m0, "ktn_get_constr_duals: dual buffer missing or too small");
+        e->kkt_compute();
+        if (e->m0 > 0) std::memcpy(d_out, e->h_kkt_d.data(), (size_t)e->m0 * sizeof(double));
+        return KTN_OK;
+    })
+}
+int ktn_get_reduced_costs(ktn_handle h, double* z_out, int64_t n) {
+    KTN_TRY(h, {
+        Engine* e = h->eng;
+        KTN_REQUIRE(e->loaded && z_out && n >= e->n0, "ktn_get_reduced_costs: buffer missing or too small");
+        e->kkt_compute();
+        if (e->n0 > 0) std::memcpy(z_out, e->h_kkt_z.data(), (size_t)e->n0 * sizeof(double));
+        return KTN_OK;
+    })
+}
+int ktn_get_dual_bound(ktn_handle h, double* bound, double* gap) {
+    KTN_TRY(h, {
+        Engine* e = h->eng;
+        KTN_REQUIRE(e->loaded && (bound || gap), "ktn_get_dual_bound: no problem loaded or no output");
+        e->kkt_compute();
+        if (bound) *bound = e->kkt_bound;
+        if (gap) *gap = e->kkt_gap;
+        return KTN_OK;
+    })
+}
+
 // ---- supporting-hyperplane cuts: the interior point
 int ktn_set_interior_point(ktn_handle h, const double* x, int64_t n) {
     KTN_TRY(h, {
@@ -415,6 +445,7 @@ int ktn_lp_truncate(ktn_handle h, int64_t nrows) {
         if (e->d_age.n > (size_t)nrows) e->d_age.n = (size_t)nrows;
         if (e->d_cutprev.n > (size_t)nrows) e->d_cutprev.n = (size_t)nrows;
         e->lp_dirty = true; ++e->lp_version; ++e->lp_epoch;
+        e->kkt_solved = false;
         return KTN_OK;
     })
 }
@@ -482,6 +513,7 @@ int ktn_lp_purge(ktn_handle h, int64_t* rows_removed) {
         Engine* e = h->eng;
         KTN_REQUIRE(e->loaded, "no problem loaded");
         const int64_t before = e->M;
+        e->kkt_solved = false;
         if (e->prm.purge_age > 0 && !e->prm.vis_data && e->M - e->M_base >= std::max<int64_t>(e->prm.purge_min_rows, 1)) e->purge_cuts();
         if (rows_removed) *rows_removed = before - e->M;
         return KTN_OK;
@@ -492,7 +524,7 @@ int ktn_set_blocks(ktn_handle h, int64_t nblocks, const int64_t* col_offsets) {
     KTN_TRY(h, {
         Engine* e = h->eng;
         KTN_REQUIRE(e->loaded && nblocks >= 0, "ktn_set_blocks: after loadproblem");
-        if (nblocks == 0) { e->n_blocks = 0; return KTN_OK; }
+        if (nblocks == 0) { e->n_blocks = 0; e->kkt_seg_ok = false; e->h_kkt_blk.clear(); return KTN_OK; }
         KTN_REQUIRE(col_offsets && e->obj_linear, "ktn_set_blocks: needs a linear objective (no shared epigraph variable)");
         KTN_REQUIRE(col_offsets[0] == 0 && col_offsets[nblocks] == e->n_lp, "ktn_set_blocks: offsets must cover the columns");
         e->h_blkcol.assign(col_offsets, col_offsets + nblocks + 1);
@@ -507,6 +539,7 @@ int ktn_set_blocks(ktn_handle h, int64_t nblocks, const int64_t* col_offsets) {
         e->sync();
         e->n_blocks = nblocks;
         e->blocks_built_rows = -1;
+        e->kkt_seg_ok = false; e->h_kkt_blk.clear();
         return KTN_OK;
     })
 }
@@ -586,6 +619,36 @@ int ktn_blocks_get_cuts(ktn_handle h, int64_t block, int64_t* rowptr, int32_t* c
                 std::memcpy(lo, l.data(), l.size() * sizeof(double)); std::memcpy(hi, u.data(), u.size() * sizeof(double));
                 std::memcpy(nl_slot, sl.data(), sl.size() * sizeof(int64_t)); std::memcpy(lambda, lm.data(), lm.size() * sizeof(double));
             }
+        }
+        return KTN_OK;
+    })
+}
+int ktn_blocks_get_duals(ktn_handle h, int64_t block, double* y_out, int64_t cap, int64_t* count) {
+    KTN_TRY(h, {
+        Engine* e = h->eng;
+        KTN_REQUIRE(e->loaded && count && e->blocks_launched, "ktn_blocks_get_duals: after a device launch of ktn_optimize_blocks[_ex] on the loaded problem");
+        KTN_REQUIRE(block >= 0 && block < (int64_t)e->h_ar_row0.size(), "ktn_blocks_get_duals: no such instance");
+        const int64_t m_lin = e->h_blklin[(size_t)block + 1] - e->h_blklin[(size_t)block];
+        const int64_t Mb = std::min<int64_t>((int64_t)e->h_blkres[(size_t)block * 8 + 6], e->h_ar_rows[(size_t)block]);
+        const int64_t nc = std::max<int64_t>(Mb - m_lin, 0);
+        *count = nc;
+        if (y_out && nc > 0) {
+            KTN_REQUIRE(cap >= nc, "ktn_blocks_get_duals: buffer too small");
+            KTN_HIP(hipMemcpyAsync(y_out, e->e_y.p + (e->h_ar_row0[(size_t)block] + m_lin), (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+            e->sync();
+        }
+        return KTN_OK;
+    })
+}
+int ktn_blocks_get_dual_bounds(ktn_handle h, double* out, int64_t cap, int64_t* count) {
+    KTN_TRY(h, {
+        Engine* e = h->eng;
+        KTN_REQUIRE(e->loaded && count && e->n_blocks > 0, "ktn_blocks_get_dual_bounds: after ktn_loadproblem and ktn_set_blocks");
+        *count = 2 * e->n_blocks;
+        if (out) {
+            KTN_REQUIRE(cap >= *count, "ktn_blocks_get_dual_bounds: buffer too small");
+            e->kkt_blocks();
+            std::memcpy(out, e->h_kkt_blk.data(), (size_t)*count * sizeof(double));
         }
         return KTN_OK;
     })
@@ -780,6 +843,7 @@ int ktn_lp_append_rows_nl(ktn_handle h, int64_t nrows, const int64_t* rowptr, co
         e->M += nrows; e->NNZ += nz; e->numcuts += nrows;
         e->sharded_rows = true;
         e->lp_dirty = true; ++e->lp_version;
+        e->kkt_solved = false;
         return KTN_OK;
     })
 }
@@ -837,6 +901,7 @@ int ktn_lp_append_packed_dev(ktn_handle h, int64_t nrows, int64_t nnz, const dou
         e->max_row_len = (int64_t)1 << 62;                             // (row lengths of other ranks' cuts are not known on the host)
         e->sharded_rows = true;
         e->lp_dirty = true; ++e->lp_version;
+        e->kkt_solved = false;
         return KTN_OK;
     })
 }

@@ -157,6 +157,7 @@ int Engine::optimize_blocks_device(int cap_mul, int flags) {
     std::vector<double> res = e_res.to_host(stream);
     blocks_launched = true;
     h_blkres = res;
+    ++kkt_solves; kkt_solved = true; kkt_arena = true; kkt_cached = false;      // (KKT report: multipliers and lists are the arenas' now)
     stats["ecp_blocks_esh_rows"] = 0.0;
     if (esh) {                                                  // the instances' counters: rows moved, fallback rows, passes, QUAD rows moved
         const std::vector<double> r2 = e_res2.to_host(stream);

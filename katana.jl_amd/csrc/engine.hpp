@@ -91,6 +91,7 @@ struct DevParams {
     double ipc_timeout_s = 20.0;   // KTN_IPC_TIMEOUT_S    spin bound of the peer-buffer transport
     bool raw_duals = false;        // KTN_RAW_DUALS        ktn_lp_get_duals returns lp_y as the loop sees it, also after an exact mid-size solve
     int mid_refactor = 0;          // KTN_MID_REFACTOR     pivots between refactorisations of the mid-size exact LP (<= 0: kMidRefactor, mid_lp.hpp)
+    int kkt_group = 0;             // KTN_KKT_GROUP        lanes per column of k_lagr_grad (0 = by mean column length)
     static bool flag(const char* k) { return std::getenv(k) != nullptr; }
     static int geti(const char* k, int d) { const char* v = std::getenv(k); return v ? std::atoi(v) : d; }
     static double getd(const char* k, double d) { const char* v = std::getenv(k); return v ? std::atof(v) : d; }
@@ -113,6 +114,7 @@ struct DevParams {
         omega_art_clamp = getd("KTN_OMEGA_ART_CLAMP", omega_art_clamp); omega_clamp = getd("KTN_OMEGA_CLAMP", omega_clamp);
         omega_clamp_down = getd("KTN_OMEGA_CLAMP_DOWN", omega_clamp_down); ipc_timeout_s = getd("KTN_IPC_TIMEOUT_S", ipc_timeout_s);
         mid_refactor = geti("KTN_MID_REFACTOR", mid_refactor); raw_duals = flag("KTN_RAW_DUALS");
+        kkt_group = geti("KTN_KKT_GROUP", kkt_group);
     }
 };
 
@@ -609,6 +611,26 @@ struct Engine {
     DBuf<int64_t> d_esh_slot;
     bool esh_gencut_row(int64_t i, double* coefs, double* constant);
     void esh_last_lambdas(double* out);
+
+    // ================================================================ KKT report (kkt.hpp) ===
+    // Constraint duals in the caller's row order, reduced costs and the dual bound, computed on the first getter after a solve and
+    // kept until the LP is solved again or its rows change.  kkt_solved: an LP solve (or a device launch of the batch loop:
+    // kkt_arena, the multipliers and lists are then the arenas') has run since the caller last appended, truncated or purged rows.
+    bool kkt_solved = false, kkt_arena = false, kkt_cached = false, kkt_mirror = false, kkt_seg_ok = false;
+    uint64_t kkt_solves = 0, kkt_key_version = 0, kkt_key_solves = 0;
+    DBuf<int32_t> d_kkt_rowmap;                  // [m0] position among the linear rows (= LP row), or -1 - NL slot; built at load
+    int64_t kkt_n_lin = 0;
+    // column mirror of the extended NLP structure, built on first use per loaded problem: 8 (n0 + 2) + (4 + 4) nnz_ext bytes
+    DBuf<int64_t> d_kkt_cptr, d_kkt_seg;
+    DBuf<int32_t> d_kkt_crow, d_kkt_nonfin;
+    DBuf<uint32_t> d_kkt_cperm;
+    DBuf<double> d_kkt_x, d_kkt_g, d_kkt_jac, d_kkt_bconst, d_kkt_maxc, d_kkt_d, d_kkt_z, d_kkt_t, d_kkt_out, d_kkt_blk;
+    std::vector<double> h_kkt_d, h_kkt_z, h_kkt_blk;      // results on the host; h_kkt_blk: (bound, gap) per instance of a fused batch
+    double kkt_bound = 0.0, kkt_gap = 0.0;
+    bool kkt_foreign() const { return row_sharded() || dist.cb != nullptr || dist.comm != nullptr || dist.ipc.data != nullptr || exchanging(); }
+    void kkt_build_mirror();
+    void kkt_compute();
+    void kkt_blocks();
 
     // ================================================================ LP ============
     void rebuild_csc();

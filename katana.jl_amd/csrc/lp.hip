@@ -439,6 +439,7 @@ bool Engine::launch_check(const SpMat& A, const SpMat& AT, double tau, double si
 // the exact kernel directly.
 LpResult Engine::lp_solve(double tol_p, double tol_g, int mode, bool identity_scaling) {
     md_y_version = 0;                                    // (set again by an exact mid-size solve that ends optimal)
+    ++kkt_solves; kkt_solved = mode == 0; kkt_arena = false;      // (KKT report: lp_y is this solve's from here on)
     const bool dense_ok = mode == 0 && !identity_scaling && !row_sharded() && prm.lp_dense_after != 0 && n_lp >= 1 && n_lp <= kDenseMaxN &&
                           M * n_lp <= 8000000;
     // ... and LPs of 33 .. lp_mid_max_var columns by the exact mid-size solver (mid_lp.hpp), under the same hand-over rule
@@ -594,7 +595,7 @@ bool Engine::mid_true_duals(double* y_out) {
     hipLaunchKernelGGL(k_mid_lambda, dim3(g_n), dim3(256), 0, stream, P, 1);
     hipLaunchKernelGGL(k_mid_true_duals, dim3(g_n), dim3(256), 0, stream, P, md_y.p);
     check_launch();
-    md_y.download(y_out, (size_t)M, stream);
+    if (y_out) md_y.download(y_out, (size_t)M, stream);      // (null: the caller reads md_y on the device)
     return true;
 }
 

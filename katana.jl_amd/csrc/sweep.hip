@@ -10,6 +10,7 @@
 #include "batch_lp.hpp"
 #include "batch_ecp.hpp"
 #include "dense_lp.hpp"
+#include "kkt.hpp"
 
 namespace ktn {
 
@@ -638,6 +639,14 @@ void Engine::loadproblem(int64_t num_var, int64_t num_constr, const double* l_va
     for (auto r : h_nlrows) n_host_nl += (h_rowkind[r] == KTN_ROW_HOST) ? 1 : 0;
     d_taperows_nl.upload(tape_nl, stream);
     d_nlrows.upload(h_nlrows, stream);
+    {   // KKT report: where each original row's multiplier lives (its own LP row, or the cut list of its NL slot)
+        std::vector<int32_t> rowmap((size_t)std::max<int64_t>(m0, 1), 0);
+        for (size_t k = 0; k < lin_rows.size(); ++k) rowmap[(size_t)lin_rows[k]] = (int32_t)k;
+        for (size_t si = 0; si < h_nlrows.size(); ++si) if (h_nlrows[si] < m0) rowmap[(size_t)h_nlrows[si]] = -1 - (int32_t)si;
+        d_kkt_rowmap.upload(rowmap, stream);
+        kkt_n_lin = (int64_t)lin_rows.size();
+        kkt_mirror = false; kkt_seg_ok = false;
+    }
     build_tape_classes(nodeptr, nop, na, nb, nc, tape_all);
     lapl("tape shape classes");
     grp_sweep = pick_group(m_nl ? (double)nnz_nl / (double)m_nl : 4.0);
@@ -966,6 +975,7 @@ void Engine::reset() {
     d_age.zero(stream);
     lp_dirty = true; ++lp_version; ++lp_epoch; have_omega = false; have_precompute = false; sharded_rows = false; scal_rows = 0; smax_rows = 0; n_longc = 0; col_len_max = -1; col_scan_rows = 0; col_removed_rows = 0;
     blocks_built_rows = -1;
+    kkt_solved = false; kkt_arena = false; kkt_cached = false;
     if (d_blkomega.n) d_blkomega.zero(stream);
     if (ds_valid.n) ds_valid.zero(stream);
     dense_credit = dense_run = 0;
@@ -1031,6 +1041,159 @@ void Engine::precompute_all(const double* d_x) {
         LAUNCH_1(k_gj_stats, m_ext, stream, P, d_allrows.p, m_ext, d_x, 0.0, (int)KTN_ROW_TAPE,
                  (const uint8_t*)(tc_rows > 0 ? d_tc_rowflag.p : nullptr), O);
     check_launch();
+}
+
+// ================================================================ KKT report (kkt.hpp) =====
+// Column mirror of the extended structure (rows 0 .. m0, the objective row last; columns 0 .. n0), by the radix sort the LP's
+// mirror uses: keys (col << 32 | row) in CSR order (k_kkt_keys: a thread per entry), a stable sort on the column bits gives row-ordered columns.  Built on the
+// first getter after ktn_loadproblem, never changed until the next one.
+void Engine::kkt_build_mirror() {
+    if (kkt_mirror) return;
+    if (nnz_ext >= ((int64_t)1 << 32)) throw Error(KTN_E_UNSUPPORTED, "KKT report: 2^32 Jacobian entries and more are not mirrored");
+    const int64_t nc = n0 + 1;
+    d_kkt_cptr.resize((size_t)nc + 1, stream);
+    d_kkt_crow.resize((size_t)nnz_ext + 1, stream); d_kkt_cperm.resize((size_t)nnz_ext + 1, stream);
+    DBuf<int64_t> cnt;
+    DBuf<uint64_t> kin, kout;
+    DBuf<uint32_t> pin, pout;
+    DBuf<char> tmp;
+    cnt.resize((size_t)nc + 1, stream); cnt.zero(stream);
+    if (nnz_ext > 0) {
+        kin.resize((size_t)nnz_ext, stream); kout.resize((size_t)nnz_ext, stream);
+        pin.resize((size_t)nnz_ext, stream); pout.resize((size_t)nnz_ext, stream);
+        LAUNCH_1(k_kkt_keys, nnz_ext, stream, nnz_ext, m_ext, d_rowptr.p, d_col.p, kin.p, pin.p, cnt.p);
+        check_launch();
+    }
+    exclusive_scan(cnt.p, d_kkt_cptr.p, (size_t)nc + 1);
+    if (nnz_ext > 0) {
+        int bits = 1;
+        while (((int64_t)1 << bits) < nc + 1 && bits < 31) ++bits;
+        const size_t need = sort_pairs_temp_bytes((size_t)nnz_ext);
+        tmp.resize(need + 16, stream);
+        KTN_HIP(sort_pairs_u64_u32(tmp.p, need, kin.p, kout.p, pin.p, pout.p, (size_t)nnz_ext, 32, 32 + bits, stream));
+        LAUNCH_1(k_csc_rows_perm, nnz_ext, stream, nnz_ext, kout.p, pout.p, d_kkt_crow.p, d_kkt_cperm.p);
+        check_launch();
+    }
+    sync();                                             // the temporaries are freed on leaving the scope
+    kkt_mirror = true;
+    stats["kkt_mirror_bytes"] = 8.0 * (double)(nc + 1) + 8.0 * (double)nnz_ext;
+}
+
+void Engine::kkt_compute() {
+    KTN_REQUIRE(loaded, "KKT report: no problem loaded");
+    if (kkt_foreign())
+        throw Error(KTN_E_UNSUPPORTED, "KKT report: a row-sharded handle or one with a cut exchange owns only a part of the cut lists");
+    KTN_REQUIRE(kkt_solved, "KKT report: no LP solve since the problem was loaded or reset, or since rows were appended, truncated or purged");
+    if (!kkt_arena && !lists_ok())
+        throw Error(KTN_E_UNSUPPORTED, "KKT report: rows were appended from the host without cut lists (ktn_lp_enable_global_lists)");
+    if (kkt_cached && kkt_key_version == lp_version && kkt_key_solves == kkt_solves) return;
+    kkt_cached = false;
+    kkt_build_mirror();
+    const double sgn = (sense == KTN_MAX) ? -1.0 : 1.0;
+    const size_t mm = (size_t)std::max<int64_t>(m_ext, 1);
+    d_kkt_d.resize(mm, stream); d_kkt_z.resize((size_t)n0 + 1, stream); d_kkt_t.resize((size_t)(m0 + n0) + 1, stream);
+    d_kkt_out.resize(8, stream);
+    // ---- 1. constraint duals
+    KktSrc S{};
+    const bool epi = !obj_linear && !kkt_arena;
+    if (kkt_arena) {
+        S.y = e_y.p; S.a_last = e_last.p; S.a_prev = e_prev.p; S.arena = d_ar.p;
+        S.blk_lin = d_blklin.p; S.blk_nl = d_blknl.p; S.nb = (int64_t)h_ar_row0.size();
+        LAUNCH_1(k_row_duals<true>, m0, stream, m0, d_kkt_rowmap.p, S, sgn, (int64_t)0, (int64_t)0, (int64_t)-1, (double*)nullptr, d_kkt_d.p);
+    } else {
+        // what ktn_lp_get_duals returns: the true-cost multipliers of an exact mid-size solve while they stand, lp_y otherwise
+        S.y = (!dev.raw_duals && mid_true_duals(nullptr)) ? md_y.p : lp_y.p;
+        S.heads = list_heads(); S.prev = d_cutprev.p; S.n_heads = list_count(); S.n_rows = M;
+        LAUNCH_1(k_row_duals<false>, std::max<int64_t>(m0, 1), stream, m0, d_kkt_rowmap.p, S, sgn, M_lin, M_base, epi ? m_nl - 1 : (int64_t)-1,
+                 epi ? d_kkt_out.p + 2 : (double*)nullptr, d_kkt_d.p);
+    }
+    check_launch();
+    // ---- 2. g and J of every row at x* = lp_x, into buffers of the report's own: what ktn_sep_* and the certificate read stays
+    d_kkt_x.resize((size_t)n0 + 1, stream); d_kkt_x.zero(stream);
+    KTN_HIP(hipMemcpyAsync(d_kkt_x.p, lp_x.p, (size_t)std::min<int64_t>(n_lp, n0 + 1) * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    d_kkt_g.resize(mm, stream); d_kkt_bconst.resize(mm, stream); d_kkt_maxc.resize(mm, stream); d_kkt_nonfin.resize(mm, stream);
+    d_kkt_jac.resize((size_t)nnz_ext + 1, stream); d_kkt_jac.zero(stream);
+    auto swap_bufs = [&]() { d_g.swap(d_kkt_g); d_jac.swap(d_kkt_jac); d_bconst.swap(d_kkt_bconst); d_maxc.swap(d_kkt_maxc); d_nonfin.swap(d_kkt_nonfin); };
+    swap_bufs();
+    try {
+        precompute_all(d_kkt_x.p);
+    } catch (...) {
+        swap_bufs();
+        throw;
+    }
+    swap_bufs();
+    // ---- 3. reduced costs
+    int G = dev.kkt_group;
+    if (!(G == 4 || G == 8 || G == 16 || G == 32 || G == 64)) G = pick_group((double)nnz_ext / (double)(n0 + 1));
+    LAUNCH_G(G, k_lagr_grad, n0, stream, n0, (int32_t)m0, d_kkt_cptr.p, d_kkt_crow.p, d_kkt_cperm.p, d_kkt_jac.p, d_kkt_d.p, d_kkt_z.p);
+    // ---- 4. the bound
+    LAUNCH_1(k_dual_terms, m0 + n0, stream, m0, n0, sgn, d_kkt_rowmap.p, kkt_n_lin, d_kkt_d.p, d_kkt_z.p, d_kkt_g.p, d_lb.p, d_ub.p, d_kkt_x.p,
+             lp_l.p, lp_u.p, d_kkt_t.p);
+    if (m0 + n0 > 0) hipLaunchKernelGGL(k_sum_partial, dim3(kRedBlocks), dim3(kBlock), 0, stream, m0 + n0, d_kkt_t.p, partials.p);
+    else KTN_HIP(hipMemsetAsync(partials.p, 0, kRedBlocks * sizeof(double), stream));
+    hipLaunchKernelGGL(k_dual_final, dim3(1), dim3(64), 0, stream, partials.p, (int)kRedBlocks, d_kkt_g.p, d_kkt_x.p, m0, n0, d_kkt_out.p);
+    check_launch();
+    h_kkt_d.assign((size_t)m0, 0.0); h_kkt_z.assign((size_t)n0, 0.0);
+    std::vector<double> out(d_kkt_out.n, 0.0);
+    if (m0 > 0) KTN_HIP(hipMemcpyAsync(h_kkt_d.data(), d_kkt_d.p, (size_t)m0 * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (n0 > 0) KTN_HIP(hipMemcpyAsync(h_kkt_z.data(), d_kkt_z.p, (size_t)n0 * sizeof(double), hipMemcpyDeviceToHost, stream));
+    d_kkt_out.download(out.data(), out.size(), stream);
+    // Min form: LB = f_min - T with f_min = sgn f; mirrored back: bound = sgn LB, gap = T in both senses
+    const double T = out[0], f = out[1];
+    kkt_bound = sgn * (sgn * f - T);
+    kkt_gap = T;
+    h_kkt_blk.clear();                                  // (per instance: kkt_blocks, on ktn_blocks_get_dual_bounds only)
+    stats["kkt_evals"] += 1.0;
+    stats["kkt_epi_dual"] = epi ? out[2] : std::numeric_limits<double>::quiet_NaN();
+    stats["kkt_group"] = (double)G;
+    kkt_key_version = lp_version; kkt_key_solves = kkt_solves; kkt_cached = true;
+}
+
+// The bound per instance of a fused batch (ktn_blocks_get_dual_bounds) from the terms the last evaluation left in d_kkt_t: one
+// launch of k_dual_bound, no re-evaluation.  The instances' ranges -- linear rows, NL slots, columns, each grouped by instance,
+// instance after instance -- are found once per ktn_set_blocks (kkt_seg_ok).
+void Engine::kkt_blocks() {
+    kkt_compute();
+    const int64_t nb = n_blocks;
+    KTN_REQUIRE(nb > 0, "KKT report: no blocks set (ktn_set_blocks)");
+    if ((int64_t)h_kkt_blk.size() == 2 * nb) return;
+    const double sgn = (sense == KTN_MAX) ? -1.0 : 1.0;
+    if (!kkt_seg_ok) {
+        std::vector<int64_t> seg((size_t)nb * 6), bl((size_t)nb + 1, 0), bn((size_t)nb + 1, 0);
+        auto block_of_col = [&](int64_t c) { return (int64_t)(std::upper_bound(h_blkcol.begin(), h_blkcol.end(), c) - h_blkcol.begin()) - 1; };
+        std::vector<char> is_nl((size_t)std::max<int64_t>(m0, 1), 0);
+        for (auto r : h_nlrows) if (r < m0) is_nl[(size_t)r] = 1;
+        int64_t prev_l = 0, prev_n = 0;
+        bool grouped = true;
+        for (int64_t i = 0; i < m0; ++i) {
+            if (h_rowptr[i + 1] == h_rowptr[i]) { grouped = false; break; }
+            const int64_t b = std::min<int64_t>(std::max<int64_t>(block_of_col(h_col[(size_t)h_rowptr[i]]), 0), nb - 1);
+            int64_t& prev = is_nl[(size_t)i] ? prev_n : prev_l;
+            if (b < prev) { grouped = false; break; }
+            prev = b;
+            (is_nl[(size_t)i] ? bn : bl)[(size_t)b + 1] += 1;
+        }
+        if (!grouped) throw Error(KTN_E_UNSUPPORTED, "KKT report: the rows of the fused batch are not grouped by instance");
+        for (int64_t b = 0; b < nb; ++b) { bl[(size_t)b + 1] += bl[(size_t)b]; bn[(size_t)b + 1] += bn[(size_t)b]; }
+        for (int64_t b = 0; b < nb; ++b) {
+            int64_t* s = seg.data() + 6 * b;
+            s[0] = bl[(size_t)b]; s[1] = bl[(size_t)b + 1];
+            s[2] = kkt_n_lin + bn[(size_t)b]; s[3] = kkt_n_lin + bn[(size_t)b + 1];
+            s[4] = m0 + h_blkcol[(size_t)b]; s[5] = m0 + std::min<int64_t>(h_blkcol[(size_t)b + 1], n0);
+        }
+        d_kkt_seg.upload(seg, stream);
+        kkt_seg_ok = true;
+    }
+    d_kkt_blk.resize((size_t)(2 * nb), stream);
+    hipLaunchKernelGGL(k_dual_bound, dim3((unsigned)nb), dim3(kBlock), 0, stream, d_kkt_seg.p, d_kkt_t.p, lp_c.p, d_kkt_x.p, m0, d_kkt_blk.p);
+    check_launch();
+    const std::vector<double> out = d_kkt_blk.to_host(stream);
+    h_kkt_blk.assign((size_t)(2 * nb), 0.0);
+    for (int64_t b = 0; b < nb; ++b) {
+        const double Tb = out[(size_t)(2 * b)], fb = out[(size_t)(2 * b + 1)];
+        h_kkt_blk[(size_t)(2 * b)] = sgn * (sgn * fb - Tb);
+        h_kkt_blk[(size_t)(2 * b + 1)] = Tb;
+    }
 }
 
 // the batched {isconstrsat, gencut, round_coefs, _addcut} over the NL rows

@@ -75,6 +75,11 @@ class SeparableInstance:
     m_lin: int
     m_nl: int
     meta: dict = field(default_factory=dict)
+    # planted multipliers (make_instance; None where the generator plants none): lam of the NL rows, mu of the linear rows, nu of the
+    # variable bounds signed like a reduced cost (+ on a pinned lower bound, - on a pinned upper bound, 0 elsewhere)
+    lam: np.ndarray = None
+    mu: np.ndarray = None
+    nu: np.ndarray = None
 
     @property
     def num_constr(self):
@@ -224,6 +229,9 @@ def make_instance(n, m_nl, k, family="explog", seed=0, m_lin=None, lin_nnz=8, B=
         c -= np.bincount(lcol, weights=(mu[lrow] * lval), minlength=n)
         c[lower] += nu[lower]
         c[upper] -= nu[upper]
+        nu_signed = np.where(lower, nu, 0.0) - np.where(upper, nu, 0.0)
+    else:
+        nu_signed = np.zeros(n)
 
     # ---- objective ---------------------------------------------------------
     if objective == "linear":
@@ -256,6 +264,7 @@ def make_instance(n, m_nl, k, family="explog", seed=0, m_lin=None, lin_nnz=8, B=
         opt += ct * that
         xhat = np.append(xhat, that)
         l_var, u_var = np.append(l_var, that), np.append(u_var, B)
+        nu_signed = np.append(nu_signed, 1.0)          # t on its lower bound with multiplier 1
         n, k = n + 1, k + 1
     rowptr = np.concatenate([np.arange(m_lin + 1) * lin_nnz,
                              m_lin * lin_nnz + np.arange(1, m_nl + 1) * k]).astype(np.int64)
@@ -275,7 +284,8 @@ def make_instance(n, m_nl, k, family="explog", seed=0, m_lin=None, lin_nnz=8, B=
                   vertex=bool(vertex), bound_frac=float(bound_frac), pivot_boost=bool(pivot_boost), n_lin_active=int(lin_active.sum()), shared_column=bool(shared_column),
                   # planted multipliers: an x with g_i(x) <= eps on the NL rows, a_r'x <= b_r + delta on the linear rows and the
                   # bounds met exactly has  c'x >= c'xhat - eps * lam_sum - delta * mu_sum  (Lagrangian bound at xhat)
-                  lam_sum=float(lam.sum()), mu_sum=float(mu.sum())))
+                  lam_sum=float(lam.sum()), mu_sum=float(mu.sum())),
+        lam=lam, mu=mu, nu=nu_signed)
     return inst
 
 

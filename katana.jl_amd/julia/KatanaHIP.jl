@@ -285,6 +285,8 @@ mutable struct KatanaHipModel <: MathProgBase.AbstractNonlinearModel
     params::KtnParams
     arrays::Union{NlpArrays,Void}
     host::Union{HostEval,Void}            # kept alive while the engine holds its address (eval_user)
+    num_var::Int                          # the caller's sizes (getconstrduals / getreducedcosts: the epigraph row and variable are not reported)
+    num_constr::Int
 end
 
 function check(m::KatanaHipModel, code)
@@ -328,7 +330,7 @@ function KatanaHipModel(s)
     h = Ref{Ptr{Void}}(C_NULL)
     code = ccall((:ktn_create, LIB), Cint, (Ref{KtnParams}, Ref{Ptr{Void}}), Ref(prm), h)
     code == 0 || error("ktn_create failed ($code): no MI355X visible? the engine has no CPU path")
-    m = KatanaHipModel(h[], prm, nothing, nothing)
+    m = KatanaHipModel(h[], prm, nothing, nothing, 0, 0)
     finalizer(m, x -> ccall((:ktn_destroy, LIB), Void, (Ptr{Void},), x.handle))
     m
 end
@@ -339,6 +341,7 @@ function MathProgBase.loadproblem!(m::KatanaHipModel, num_var::Int, num_constr::
     desc, arrs, host = describe(d, num_var, num_constr)       # tapes from :ExprGraph, else eval_g / eval_jac_g callbacks
     m.arrays = arrs
     m.host = host
+    m.num_var, m.num_constr = num_var, num_constr
     check(m, ccall((:ktn_loadproblem, LIB), Cint,
         (Ptr{Void}, Int64, Int64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Int32, Ref{KtnNlpDesc}),
         m.handle, num_var, num_constr, l_var, u_var, l_constr, u_constr, sense == :Max ? 1 : 0, Ref(desc)))
@@ -353,6 +356,23 @@ function MathProgBase.getsolution(m::KatanaHipModel)              # incl. the ep
     x = Vector{Float64}(n)
     check(m, ccall((:ktn_get_solution, LIB), Cint, (Ptr{Void}, Ptr{Cdouble}, Int64), m.handle, x, n))
     x
+end
+# Lagrange multipliers, reduced costs and the bound they certify (include/katana_hip.h; DESIGN.md section 12): d_i > 0 lower side
+# active, < 0 upper side; z = grad f(x*) - J(x*)'d; a lower bound of the optimum for :Min, an upper bound for :Max
+function MathProgBase.getconstrduals(m::KatanaHipModel)
+    d = zeros(Float64, max(m.num_constr, 1))
+    check(m, ccall((:ktn_get_constr_duals, LIB), Cint, (Ptr{Void}, Ptr{Cdouble}, Int64), m.handle, d, length(d)))
+    d[1:m.num_constr]
+end
+function MathProgBase.getreducedcosts(m::KatanaHipModel)
+    z = zeros(Float64, max(m.num_var, 1))
+    check(m, ccall((:ktn_get_reduced_costs, LIB), Cint, (Ptr{Void}, Ptr{Cdouble}, Int64), m.handle, z, length(z)))
+    z[1:m.num_var]
+end
+function MathProgBase.getobjbound(m::KatanaHipModel)
+    b, g = Ref{Cdouble}(0.0), Ref{Cdouble}(0.0)
+    check(m, ccall((:ktn_get_dual_bound, LIB), Cint, (Ptr{Void}, Ref{Cdouble}, Ref{Cdouble}), m.handle, b, g))
+    b[]
 end
 MathProgBase.getsolvetime(m::KatanaHipModel) = ccall((:ktn_get_solvetime, LIB), Cdouble, (Ptr{Void},), m.handle)
 MathProgBase.setwarmstart!(m::KatanaHipModel, x) = fill(0.0, length(x))                      # src/model.jl:335

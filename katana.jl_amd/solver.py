@@ -111,6 +111,7 @@ class KatanaNonlinearModel:
         self.num_var = 0
         self.num_constr = 0
         self._n0 = 0
+        self._m0 = 0
 
     def __del__(self):
         try:
@@ -133,6 +134,7 @@ class KatanaNonlinearModel:
         self.num_var = int(self._lib.ktn_get_num_var(self._h))
         self.num_constr = int(self._lib.ktn_sep_num_constr(self._h))
         self._n0 = int(num_var)
+        self._m0 = int(num_constr)
 
     # ---- MathProgBase.optimize!  src/model.jl:219-319 ---------------------------------------
     def optimize(self):
@@ -166,6 +168,52 @@ class KatanaNonlinearModel:
 
     def getsolvetime(self):
         return float(self._lib.ktn_get_solvetime(self._h))
+
+    # ---- Lagrange multipliers, reduced costs, dual bound (include/katana_hip.h) ----
+    def getconstrduals(self):
+        """MathProgBase.getconstrduals: d[num_constr] in the caller's row order, d_i > 0 lower side active, < 0 upper side
+        (ktn_get_constr_duals; the epigraph row is not reported)"""
+        d = np.zeros(max(self._m0, 1))
+        L.check(self._h, self._lib.ktn_get_constr_duals(self._h, _p(d), len(d)))
+        return d[:self._m0]
+
+    def getreducedcosts(self):
+        """MathProgBase.getreducedcosts: z = grad f(x*) - J(x*)' d over the caller's variables (ktn_get_reduced_costs)"""
+        z = np.zeros(max(self._n0, 1))
+        L.check(self._h, self._lib.ktn_get_reduced_costs(self._h, _p(z), len(z)))
+        return z[:self._n0]
+
+    def _dual_bound(self):
+        b, g = C.c_double(0.0), C.c_double(0.0)
+        L.check(self._h, self._lib.ktn_get_dual_bound(self._h, C.byref(b), C.byref(g)))
+        return float(b.value), float(g.value)
+
+    def getobjbound(self):
+        """MathProgBase.getobjbound: the bound on the optimum that (d, z) certify at x* -- a lower bound for Min, an upper bound
+        for Max (ktn_get_dual_bound)"""
+        return self._dual_bound()[0]
+
+    def getobjgap(self):
+        """f(x*) - bound (Min) / bound - f(x*) (Max)"""
+        return self._dual_bound()[1]
+
+    def blocks_duals(self, block):
+        """the unscaled multiplier of each cut row of instance `block` after the last device launch, row for row as in
+        blocks_cuts(block) (ktn_blocks_get_duals)"""
+        n = C.c_int64(0)
+        L.check(self._h, self._lib.ktn_blocks_get_duals(self._h, int(block), C.POINTER(C.c_double)(), 0, C.byref(n)))
+        y = np.zeros(max(n.value, 1))
+        L.check(self._h, self._lib.ktn_blocks_get_duals(self._h, int(block), _p(y), len(y), C.byref(n)))
+        return y[:n.value]
+
+    def blocks_dual_bounds(self):
+        """[n_blocks, 2] (bound, gap) per instance of a fused batch, each without the loaded problem's objective constant
+        (ktn_blocks_get_dual_bounds; needs set_blocks)"""
+        n = C.c_int64(0)
+        L.check(self._h, self._lib.ktn_blocks_get_dual_bounds(self._h, C.POINTER(C.c_double)(), 0, C.byref(n)))
+        out = np.zeros(max(n.value, 1))
+        L.check(self._h, self._lib.ktn_blocks_get_dual_bounds(self._h, _p(out), len(out), C.byref(n)))
+        return out[:n.value].reshape(-1, 2)
 
     def numiters(self):
         return int(self._lib.ktn_numiters(self._h))
