@@ -457,7 +457,10 @@ double ktn_get_stat(ktn_handle h, const char* name);
  * every rank holds the identical LP.  These calls are what that host loop is made of:
  *   ktn_sweep_lp_point   : the loop body of src/model.jl:268-283 at the current LP solution
  *   ktn_lp_get_rows_from : export the rows appended since `first_row` (rowptr rebased to 0)
- *   ktn_lp_truncate      : drop the rows >= nrows again (own cuts are re-appended in rank order)
+ *   ktn_lp_truncate      : drop the rows >= nrows again (own cuts are re-appended in rank order).  The cut lists stay valid:
+ *                          every list that started in a dropped row now starts at its newest surviving cut (or is empty), so a
+ *                          row appended afterwards -- its index is one that was just given up -- links to that cut, never to
+ *                          itself; the surviving rows keep their multipliers and ages
  *   ktn_lp_append_rows   : append a CSR block of rows (rowptr 0-based), duals start at 0
  * Use lp_dual_inherit = 0 with truncate/append (row indices of earlier cuts change). */
 int ktn_sweep_lp_point(ktn_handle h, double f_tol, int64_t* nviol, double* maxviol);

@@ -432,6 +432,7 @@ int ktn_lp_truncate(ktn_handle h, int64_t nrows) {
         KTN_REQUIRE(e->loaded && nrows >= e->M_base && nrows <= e->M, "truncate: nrows outside [base rows, current rows]");
         int64_t base = 0;
         KTN_HIP(hipMemcpyAsync(&base, e->lp_rowptr.p + nrows, 8, hipMemcpyDeviceToHost, e->stream));
+        e->clip_lists(nrows);                           // (every list head leaves the rows that go: kernels.hpp k_list_clip)
         e->sync();
         e->numcuts -= (e->M - nrows);
         e->col_removed_rows += e->M - nrows;

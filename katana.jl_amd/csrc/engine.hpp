@@ -236,6 +236,7 @@ struct Engine {
     DBuf<int64_t> d_glast, d_nlid;
     void append_link(int64_t nrows, const int64_t* nl_id_host);       // rows [M, M + nrows) just appended from the host
     void append_link_dev(int64_t nrows);                              // the same with the ids already in d_nlid (device-resident exchange)
+    void clip_lists(int64_t nrows);                                   // ktn_lp_truncate: list heads leave the rows >= nrows (k_list_clip)
     int64_t* list_heads() { return glists ? d_glast.p : d_lastcut.p; }
     int64_t list_count() const { return glists ? nl_total : m_nl; }
     bool lists_ok() const { return !sharded_rows || glists; }

@@ -690,8 +690,10 @@ static __global__ __launch_bounds__(kBlock) void k_sep_combine(const SepSlot* __
 }
 
 // ---- deepest-cut selection (cut_cap): depth keys of the violated rows, then re-flagging against the threshold ----
-// key = bit pattern of the violation depth max(g - ub, lb - g) (non-negative doubles order like unsigned integers;
-// NaN counts as +inf), 0 for satisfied rows.
+// key = bit pattern of the violation depth max(g - ub, lb - g) (non-negative doubles order like unsigned integers), 0 for
+// satisfied rows, 1 -- the smallest non-zero key -- for a flagged row whose depth is not positive (inside its bound, flagged by a
+// negative f_tol).  NaN counts as +inf: row_violation has already turned a NaN depth into +inf, so `d > 0` below never sees one
+// (and the selection is skipped altogether when a violated row is non-finite).
 static __global__ __launch_bounds__(kBlock) void k_depth_keys(NlpDev P, const int32_t* __restrict__ nl_rows, int64_t m_nl,
                                                        const double* __restrict__ g, const int64_t* __restrict__ flag,
                                                        uint64_t* __restrict__ keys) {
@@ -874,6 +876,13 @@ struct LpRows {
     double* y;   // duals (unscaled), warm start across ECP iterations
 };
 
+// The cut lists (newest first): a row's link leads to a LOWER row index or is -1.  Every walker steps through list_next, which
+// ends the walk at a link that does not strictly descend -- whatever state the lists are in, a walk visits at most r + 1 rows.
+__device__ __forceinline__ int64_t list_next(const int64_t* __restrict__ cut_prev, int64_t r) {
+    const int64_t nx = cut_prev[r];
+    return nx < r ? nx : -1;
+}
+
 // _addcut bookkeeping after the scans: row bounds (lb - b, ub - b), new rowptr entries,
 // violated-row list, and the dual warm start (new cut inherits the dual of the previous
 // cut of the same NL row).
@@ -922,6 +931,19 @@ static __global__ __launch_bounds__(kBlock) void k_append_link(int64_t nrows, in
     cut_prev[R] = prev;
 }
 
+// ktn_lp_truncate: rows >= nrows are gone.  Every list head among them moves down its links to the first surviving row (-1: none),
+// so that no list starts in -- and no later append links to -- a row index that the next append hands out again.  One thread per
+// list; m_old = rows before the truncation (a head outside [0, m_old) is void).
+static __global__ __launch_bounds__(kBlock) void k_list_clip(int64_t nlists, int64_t nrows, int64_t m_old, int64_t* __restrict__ heads,
+                                                     const int64_t* __restrict__ cut_prev) {
+    const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (s >= nlists) return;
+    int64_t r = heads[s];
+    if (r >= m_old) r = -1;
+    while (r >= nrows) r = list_next(cut_prev, r);
+    heads[s] = r < 0 ? -1 : r;
+}
+
 // Dual-mass consolidation among the cuts of ONE nonlinear row (stall handler of the GPU LP).
 // Near the optimum successive cuts of a row are nearly parallel; PDHG moves multiplier mass between
 // two of them only at a rate proportional to the (tiny) violation and idles with the iterate stuck
@@ -941,7 +963,7 @@ static __global__ __launch_bounds__(kBlock) void k_consolidate(int64_t m_nl, con
     int64_t best_u = -1, best_l = -1;
     double res_u = -__builtin_inf(), res_l = -__builtin_inf();
     int ncuts = 0;
-    for (int64_t r = last_cut[s]; r >= 0; r = cut_prev[r]) {
+    for (int64_t r = last_cut[s]; r >= 0; r = list_next(cut_prev, r)) {
         ++ncuts;
         const double ru = ax[r] - hi[r], rl = lo[r] - ax[r];      // -inf on an infinite side, NaN on a vacuous one
         if (ru > res_u) { res_u = ru; best_u = r; }
@@ -949,7 +971,7 @@ static __global__ __launch_bounds__(kBlock) void k_consolidate(int64_t m_nl, con
     }
     if (ncuts < 2) return;
     double mass_u = 0.0, mass_l = 0.0;                             // unscaled multipliers: y_unscaled = y * dr
-    for (int64_t r = last_cut[s]; r >= 0; r = cut_prev[r]) {
+    for (int64_t r = last_cut[s]; r >= 0; r = list_next(cut_prev, r)) {
         const double yu = y[r] * dr[r];
         if (yu < 0.0 && best_u >= 0 && r != best_u && (ax[r] - hi[r]) < -thresh) { mass_u += yu; y[r] = 0.0; }
         else if (yu > 0.0 && best_l >= 0 && r != best_l && (lo[r] - ax[r]) < -thresh) { mass_l += yu; y[r] = 0.0; }
@@ -1018,7 +1040,7 @@ __global__ __launch_bounds__(kBlock) void k_dedupe_mark(int64_t nslots, const in
     const double bh = (up ? hi[head] : lo[head]) / nh;
     if (!isfinite(bh)) return;
     int nd = 0;
-    for (int64_t r = cut_prev[head]; r >= 0; r = cut_prev[r]) {
+    for (int64_t r = list_next(cut_prev, head); r >= 0; r = list_next(cut_prev, r)) {
         if (!keep[r]) continue;
         const int64_t rb = rowptr[r];
         if (rowptr[r + 1] - rb != hl || isfinite(hi[r]) != up) continue;
@@ -1063,7 +1085,7 @@ static __global__ __launch_bounds__(kBlock) void k_purge_relink(int64_t m_nl, in
     const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (s >= m_nl) return;
     int64_t head = -1, tail = -1;
-    for (int64_t r = last_cut[s]; r >= 0; r = prev_old[r]) {
+    for (int64_t r = last_cut[s]; r >= 0; r = list_next(prev_old, r)) {
         if (!keep[r]) continue;
         const int64_t nr = newidx[r];
         if (head < 0) head = nr; else prev_new[tail] = nr;
@@ -2638,7 +2660,7 @@ static __global__ __launch_bounds__(kBlock) void k_cert_nl(int64_t m_nl, const i
     const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (s >= m_nl) return;
     double lam = 0.0;
-    for (int64_t r = last_cut[s]; r >= 0; r = cut_prev[r]) lam += fabs(y[r]);
+    for (int64_t r = last_cut[s]; r >= 0; r = list_next(cut_prev, r)) lam += fabs(y[r]);
     const int32_t i = nl_rows[s];
     double v = -__builtin_inf();                                   // the tighter side's signed residual
     if (isfinite(ub[i])) v = fmax(v, g[i] - ub[i]);

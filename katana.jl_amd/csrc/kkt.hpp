@@ -46,9 +46,9 @@ static __global__ __launch_bounds__(kBlock) void k_kkt_keys(int64_t nnz, int64_t
     atomicAdd(reinterpret_cast<unsigned long long*>(&colcount[c]), 1ULL);
 }
 
-// Sum of y over one list of the ordinary state, newest to oldest as k_cert_nl walks it.  ktn_lp_truncate shortens the LP without
-// relinking the global lists, so a list may still start in rows that are gone: those are passed over (their links still lead
-// down to the surviving rows), and the walk ends should a link ever fail to descend.
+// Sum of y over one list of the ordinary state, newest to oldest as k_cert_nl walks it.  ktn_lp_truncate moves every list head
+// down to the surviving rows (k_list_clip), so a list starts below n_rows; a head that does not is still passed over, and the
+// walk ends should a link ever fail to descend (the rule of every list walker: kernels.hpp list_next).
 __device__ __forceinline__ double kkt_list_sum(const KktSrc& S, int64_t s) {
     double a = 0.0;
     if (s < 0 || s >= S.n_heads) return a;

@@ -23,6 +23,18 @@ void Engine::append_link_dev(int64_t nrows) {                              // th
     check_launch();
 }
 
+// ktn_lp_truncate: the list heads leave the rows >= nrows (k_list_clip); call BEFORE M and the buffers shrink.  The global lists
+// when they are on, else the sweep's own lists while they are still the ones in use (no host-appended rows yet).
+void Engine::clip_lists(int64_t nrows) {
+    if (nrows >= M) return;
+    if (glists) {
+        LAUNCH_1(k_list_clip, nl_total, stream, nl_total, nrows, M, d_glast.p, d_cutprev.p);
+    } else if (lists_ok() && m_nl > 0 && d_lastcut.n >= (size_t)m_nl) {
+        LAUNCH_1(k_list_clip, m_nl, stream, m_nl, nrows, M, d_lastcut.p, d_cutprev.p);
+    }
+    check_launch();
+}
+
 void Engine::pack_rows_launch(int64_t nr, int64_t nz, int64_t first_row, int64_t base, bool ids, int64_t id_offset, double* dev_out) {
     LAUNCH_1(k_pack_rows, std::max(nr, nz), stream, nr, nz, lp_rowptr.p + first_row, lp_col.p + base, lp_val.p + base,
              lp_lo.p + first_row, lp_hi.p + first_row, ids ? (const int32_t*)d_violslots.p : (const int32_t*)nullptr,
