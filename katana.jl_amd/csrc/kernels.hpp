@@ -35,6 +35,88 @@ __device__ __forceinline__ double group_sum(double v) {
     for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
 }
+// ---- lane-strided gather-dot: lane `lane` of a G-lane group adds val[e] * vec[idx[e]] for e = beg + lane, beg + lane + G, ... ----
+// The plain loop  `for (e = beg + lane; e < end; e += G) acc += val[e] * vec[idx[e]]`  compiles to load - wait - gather - wait - add per
+// trip: 2 ceil(len / G) dependent round trips per output.  Here a lane takes its entries in batches of U: the U (idx, val) pairs are
+// requested first, then the U gathers, then the products are added -- two round trips per batch.  An entry past the end is neither
+// loaded nor added (no zero is added), and the adds run in ascending e, so a lane's sum has the bits of the plain loop's.
+// The three phases are separate calls so that a kernel that serves several outputs per lane group can request the batches of all of
+// them before it adds any (k_pdhg_x_packed / k_pdhg_y_packed with T > 1).
+constexpr int kLaneU = 4;        // entries per lane and batch: one batch covers a row or column of 4 G entries
+template <int U>
+struct LaneBatch {
+    uint32_t ix[U];              // unsigned: widening it to an address needs no instruction that would wait for the load where it is issued
+    double v[U], g[U], h[U];     // h: the second vector of lane_gather2 (unused -- and not allocated -- otherwise)
+    bool on[U];                  // entry u is there; ix, v, g, h of an absent entry are zeros that are never added
+};
+// (The loads sit in branches on the lane's length, and with loads in branches the compiler cannot count how many are in flight: a
+//  wait for any of them waits for all but the last one issued.  That is harmless where the wait stands in front of the first gather
+//  and of the first add, which is where this text puts it -- check `hipcc -S` after any change here.  Seen while this was written:
+//  without the zeros above every gather waits for the last but one; with the packed record requested behind the gathers instead of
+//  in front of them, the record waits for the gathers.  A form without branches -- the count of slots decided per wavefront, absent
+//  entries loading element 0 -- was measured too: exact counts, but no faster than the serial loop at cfg3's size and 0.15 us
+//  slower below it)
+template <int G, int U, class E>
+__device__ __forceinline__ void lane_load(LaneBatch<U>& b, E e0, E end, const int32_t* __restrict__ idx, const double* __restrict__ val) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        b.on[u] = (E)(u * G) < end - e0;          // (not e0 + u G < end: the sum may pass the end of E's range)
+        b.ix[u] = 0; b.v[u] = 0.0;
+        if (b.on[u]) { b.ix[u] = (uint32_t)idx[e0 + u * G]; b.v[u] = val[e0 + u * G]; }
+    }
+}
+template <int U>
+__device__ __forceinline__ void lane_gather(LaneBatch<U>& b, const double* __restrict__ vec) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        b.g[u] = 0.0;
+        if (b.on[u]) b.g[u] = vec[b.ix[u]];
+    }
+}
+template <int U>
+__device__ __forceinline__ void lane_gather2(LaneBatch<U>& b, const double* __restrict__ vec, const double* __restrict__ vec2) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        b.g[u] = 0.0; b.h[u] = 0.0;
+        if (b.on[u]) { b.g[u] = vec[b.ix[u]]; b.h[u] = vec2[b.ix[u]]; }
+    }
+}
+template <int U>
+__device__ __forceinline__ void lane_add(const LaneBatch<U>& b, double& acc) {
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+        if (b.on[u]) acc += b.v[u] * b.g[u];
+}
+template <int U>
+__device__ __forceinline__ void lane_add2(const LaneBatch<U>& b, double& acc, double& acc2) {
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+        if (b.on[u]) { acc += b.v[u] * b.g[u]; acc2 += b.v[u] * b.h[u]; }
+}
+// acc += the lane's share of entries [beg + from, beg + len): whole batches, in order (from = U G after a first batch done by hand)
+template <int G, int U = kLaneU, class E>
+__device__ __forceinline__ void lane_dot(double& acc, E beg, E len, int lane, const int32_t* __restrict__ idx, const double* __restrict__ val,
+                                         const double* __restrict__ vec, int from = 0) {
+    const E end = beg + len;
+    for (E left = len - from - lane; left > 0; left -= U * G) {
+        LaneBatch<U> b;
+        lane_load<G, U>(b, end - left, end, idx, val);
+        lane_gather<U>(b, vec);
+        lane_add<U>(b, acc);
+    }
+}
+template <int G, int U = kLaneU, class E>
+__device__ __forceinline__ void lane_dot2(double& acc, double& acc2, E beg, E len, int lane, const int32_t* __restrict__ idx,
+                                          const double* __restrict__ val, const double* __restrict__ vec, const double* __restrict__ vec2) {
+    const E end = beg + len;
+    for (E left = len - lane; left > 0; left -= U * G) {
+        LaneBatch<U> b;
+        lane_load<G, U>(b, end - left, end, idx, val);
+        lane_gather2<U>(b, vec, vec2);
+        lane_add2<U>(b, acc, acc2);
+    }
+}
+
 template <int G>
 __device__ __forceinline__ double group_max(double v) {
 #pragma unroll
@@ -1227,7 +1309,7 @@ __global__ __launch_bounds__(kBlock) void k_pdhg_x(int64_t n, SpMat AT, const do
     //  on, it swaps that array in for x instead of launching k_halpern2; the same halpern(), hence the same bits)
     const double xv = x[j], cj = c[j], lj = l[j], uj = u[j], x0j = (UPDATE || xbar) ? x0[j] : 0.0;
     double acc = 0.0;
-    for (int64_t e = beg + lane; e < end; e += G) acc += AT.val[e] * y[AT.idx[e]];
+    lane_dot<G>(acc, beg, end - beg, lane, AT.idx, AT.val, y);
     acc = group_sum<G>(acc);
     if (lane == 0) {
         const double xtv = prox_x(xv, tau, cj, acc, lj, uj);
@@ -1256,7 +1338,7 @@ __global__ __launch_bounds__(kBlock) void k_pdhg_x_skip(int64_t n, SpMat AT, con
     if (end - beg > skip_longer) return;                  // k_pdhg_x_long
     const double xv = x[j], cj = c[j], lj = l[j], uj = u[j], x0j = UPDATE ? x0[j] : 0.0;
     double acc = 0.0;
-    for (int64_t e = beg + lane; e < end; e += G) acc += AT.val[e] * y[AT.idx[e]];
+    lane_dot<G>(acc, beg, end - beg, lane, AT.idx, AT.val, y);
     acc = group_sum<G>(acc);
     if (lane == 0) {
         const double xtv = prox_x(xv, tau, cj, acc, lj, uj);
@@ -1326,18 +1408,31 @@ __global__ __launch_bounds__(kBlock) void k_pdhg_x_packed(int64_t n, const int2*
     int2 b[T];
     ColRec r[T];
     double xv[T], acc[T];
+    LaneBatch<kLaneU> lb[T];
+    // (beg, len) first and alone: the entries are requested as soon as it has arrived, the record and x[j] right behind them (they
+    // travel with the entries; requested in front, the wait for (beg, len) would cover them too.  Behind the gathers is worse: the
+    // loads sit in branches on the lane's length, so the compiler's wait for a register it reuses there drains the gathers first.)
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        const int64_t j = g0 + t * groups;
+        b[t] = (j < n) ? bl[j] : make_int2(0, 0);
+        acc[t] = 0.0;
+    }
+#pragma unroll
+    for (int t = 0; t < T; ++t) lane_load<G, kLaneU>(lb[t], b[t].x + lane, b[t].x + b[t].y, idx, val);
 #pragma unroll
     for (int t = 0; t < T; ++t) {
         const int64_t j = g0 + t * groups;
         const bool on = j < n;
-        b[t] = on ? bl[j] : make_int2(0, 0);
         if (on) r[t] = rec[j];
         xv[t] = on ? x[j] : 0.0;
-        acc[t] = 0.0;
     }
 #pragma unroll
-    for (int t = 0; t < T; ++t)
-        for (int e = b[t].x + lane; e < b[t].x + b[t].y; e += G) acc[t] += val[e] * y[idx[e]];
+    for (int t = 0; t < T; ++t) lane_gather<kLaneU>(lb[t], y);
+#pragma unroll
+    for (int t = 0; t < T; ++t) lane_add<kLaneU>(lb[t], acc[t]);
+#pragma unroll
+    for (int t = 0; t < T; ++t) lane_dot<G>(acc[t], b[t].x, b[t].y, lane, idx, val, y, kLaneU * G);      // columns longer than one batch
 #pragma unroll
     for (int t = 0; t < T; ++t) {
         const int64_t j = g0 + t * groups;
@@ -1397,18 +1492,28 @@ __global__ __launch_bounds__(kBlock) void k_pdhg_y_packed(int64_t m, const int32
     const int lane = threadIdx.x & (G - 1);
     RowRec r[T];
     double yv[T], acc[T];
+    LaneBatch<kLaneU> lb[T];
+    // the record (it holds beg | len) first, y[i] behind the entries: see k_pdhg_x_packed
 #pragma unroll
     for (int t = 0; t < T; ++t) {
         const int64_t i = g0 + t * groups;
-        const bool on = i < m;
-        if (on) r[t] = rec[i]; else { r[t].beg = 0; r[t].len = 0; }
+        if (i < m) r[t] = rec[i]; else { r[t].beg = 0; r[t].len = 0; }
         if (r[t].len > long_thresh) r[t].len = -1;      // served by k_pdhg_y_long (a workgroup per row)
-        yv[t] = on ? y[i] : 0.0;
         acc[t] = 0.0;
     }
 #pragma unroll
-    for (int t = 0; t < T; ++t)
-        for (int e = r[t].beg + lane; e < r[t].beg + r[t].len; e += G) acc[t] += val[e] * xbar[idx[e]];
+    for (int t = 0; t < T; ++t) lane_load<G, kLaneU>(lb[t], r[t].beg + lane, r[t].beg + r[t].len, idx, val);
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        const int64_t i = g0 + t * groups;
+        yv[t] = (i < m) ? y[i] : 0.0;
+    }
+#pragma unroll
+    for (int t = 0; t < T; ++t) lane_gather<kLaneU>(lb[t], xbar);
+#pragma unroll
+    for (int t = 0; t < T; ++t) lane_add<kLaneU>(lb[t], acc[t]);
+#pragma unroll
+    for (int t = 0; t < T; ++t) lane_dot<G>(acc[t], r[t].beg, r[t].len, lane, idx, val, xbar, kLaneU * G);      // rows longer than one batch
 #pragma unroll
     for (int t = 0; t < T; ++t) {
         const int64_t i = g0 + t * groups;
@@ -1470,7 +1575,7 @@ __global__ __launch_bounds__(kBlock) void k_pdhg_y(int64_t m, SpMat A, const dou
     if (end - beg > long_thresh) return;          // served by k_pdhg_y_long (a workgroup per row)
     const double yv = y[i], loi = lo[i], hii = hi[i], y0i = y0[i];
     double acc = 0.0;
-    for (int64_t e = beg + lane; e < end; e += G) acc += A.val[e] * xbar[A.idx[e]];
+    lane_dot<G>(acc, beg, end - beg, lane, A.idx, A.val, xbar);
     acc = group_sum<G>(acc);
     if (lane == 0) {
         y[i] = halpern(w, rho, prox_y(yv, sigma, acc, loi, hii), yv, y0i);
@@ -1496,13 +1601,7 @@ __global__ __launch_bounds__(kBlock) void k_pdhg_y_chk(int64_t m, SpMat A, const
     double yv = 0.0, loi = 0.0, hii = 0.0, y0i = 0.0, dri = 1.0;
     if (mine) { yv = y[i]; loi = lo[i]; hii = hi[i]; y0i = y0[i]; dri = dr[i]; }
     double axt = 0.0, axk = 0.0;
-    if (mine)
-        for (int64_t e = beg + lane; e < end; e += G) {
-            const int c = A.idx[e];
-            const double v = A.val[e];
-            axt += v * xt[c];
-            axk += v * x[c];
-        }
+    if (mine) lane_dot2<G>(axt, axk, beg, end - beg, lane, A.idx, A.val, xt, x);
     axt = group_sum<G>(axt);
     axk = group_sum<G>(axk);
     if (mine && lane == 0) {
@@ -1673,7 +1772,7 @@ __global__ __launch_bounds__(kBlock) void k_chk_cols(int64_t n, SpMat AT, const 
     double xtv = 0.0, xv = 0.0, x0v = 0.0, cj = 0.0, lj = 0.0, uj = 0.0, dcj = 1.0;
     if (on) { xtv = xt[j]; xv = x[j]; x0v = x0[j]; cj = c[j]; lj = l[j]; uj = u[j]; dcj = dc[j]; }
     double aty = 0.0;
-    for (int64_t e = beg + lane; e < end; e += G) aty += AT.val[e] * yt[AT.idx[e]];
+    lane_dot<G>(aty, beg, end - beg, lane, AT.idx, AT.val, yt);
     aty = group_sum<G>(aty);
     if (on && lane == 0) {
         chk_col_accumulate(a, xtv, xv, x0v, aty, cj, lj, uj, dcj);
@@ -2365,8 +2464,9 @@ __global__ __launch_bounds__(kBlock) void k_spmv(int64_t m, SpMat A, const doubl
     const int64_t i = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / G;
     const int lane = threadIdx.x & (G - 1);
     if (i >= m) return;
+    const int64_t beg = A.ptr[i], end = A.ptr[i + 1];
     double acc = 0.0;
-    for (int64_t e = A.ptr[i] + lane; e < A.ptr[i + 1]; e += G) acc += A.val[e] * v[A.idx[e]];
+    lane_dot<G>(acc, beg, end - beg, lane, A.idx, A.val, v);
     acc = group_sum<G>(acc);
     if (lane == 0) out[i] = acc;
 }
@@ -2382,7 +2482,7 @@ __global__ __launch_bounds__(kBlock) void k_spmv_skip(int64_t m, SpMat A, const 
     const int64_t beg = A.ptr[i], end = A.ptr[i + 1];
     if (end - beg > skip_longer) return;
     double acc = 0.0;
-    for (int64_t e = beg + lane; e < end; e += G) acc += A.val[e] * v[A.idx[e]];
+    lane_dot<G>(acc, beg, end - beg, lane, A.idx, A.val, v);
     acc = group_sum<G>(acc);
     if (lane == 0) out[i] = acc;
 }
