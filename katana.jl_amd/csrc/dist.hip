@@ -9,8 +9,7 @@ namespace ktn {
 int64_t Engine::ipc_barrier() {
     const int64_t off = ipc_off();
     dist.ipc.epoch += 1;
-    hipLaunchKernelGGL(k_ipc_barrier, dim3(1), dim3(64), 0, stream, dist.ipc.P, dist.rank, dist.world, dist.ipc.epoch,
-                       dist.ipc.timeout_ticks, dist.ipc.h_err_dev);
+    launch(k_ipc_barrier, 1, 64, 0, stream, dist.ipc.P, dist.rank, dist.world, dist.ipc.epoch, dist.ipc.timeout_ticks, dist.ipc.h_err_dev);
     return off;
 }
 
@@ -24,8 +23,7 @@ void Engine::allreduce(double* d, size_t n, int op) {          // in place; op 0
         if (prm.profile) { ea = ev_get(); eb = ev_get(); KTN_HIP(hipEventRecord(ev_pool[ea], stream)); }
         if (d != ipc_slot()) KTN_HIP(hipMemcpyAsync(ipc_slot(), d, n * sizeof(double), hipMemcpyDeviceToDevice, stream));
         const int64_t off = ipc_barrier();
-        if (op) hipLaunchKernelGGL((k_ipc_reduce<1>), dim3(ceil_div((int64_t)n, kBlock)), dim3(kBlock), 0, stream, (int64_t)n, dist.ipc.P, dist.world, off, d);
-        else hipLaunchKernelGGL((k_ipc_reduce<0>), dim3(ceil_div((int64_t)n, kBlock)), dim3(kBlock), 0, stream, (int64_t)n, dist.ipc.P, dist.world, off, d);
+        with_value<1, 0>(op ? 1 : 0, [&](auto o) { launch_n(k_ipc_reduce<o()>, n, stream, (int64_t)n, dist.ipc.P, dist.world, off, d); });
         check_launch();
         if (prm.profile) { KTN_HIP(hipEventRecord(ev_pool[eb], stream)); ev_recs.push_back({3, ea, eb, 8.0 * (double)n}); }
     } else if (dist.comm) {
@@ -58,7 +56,7 @@ void Engine::allreduce_host(double* v, int k, int op) {
 }
 
 void Engine::probe_fill(int64_t n, double* v, double value) {
-    hipLaunchKernelGGL(k_probe_fill, dim3(ceil_div(n, kBlock)), dim3(kBlock), 0, stream, n, v, value);
+    launch(k_probe_fill, grid_n(n), kBlock, 0, stream, n, v, value);
 }
 
 // Leave the peer-buffer transport: one last barrier (after it no peer kernel of an earlier epoch can still be reading this

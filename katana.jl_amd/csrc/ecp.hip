@@ -145,13 +145,13 @@ int Engine::optimize_blocks_device(int cap_mul, int flags) {
             KTN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ecp_blocks<1, EcpEsh>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             lds_set_ecp_esh = lds;
         }
-        hipLaunchKernelGGL((k_ecp_blocks<1, EcpEsh>), dim3((unsigned)nb), dim3(kEcpThreads), lds, stream, B, E);
+        launch(k_ecp_blocks<1, EcpEsh>, (unsigned)nb, kEcpThreads, lds, stream, B, E);
     } else {
         if (lds > lds_set_ecp) {
             KTN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ecp_blocks<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             lds_set_ecp = lds;
         }
-        hipLaunchKernelGGL(k_ecp_blocks<0>, dim3((unsigned)nb), dim3(kEcpThreads), lds, stream, B);
+        launch(k_ecp_blocks<0>, (unsigned)nb, kEcpThreads, lds, stream, B);
     }
     check_launch();
     std::vector<double> res = e_res.to_host(stream);
@@ -242,7 +242,7 @@ void Engine::blocks_cuts(int64_t block, std::vector<int64_t>& rowptr, std::vecto
 void Engine::boundroutine() {
     for (int nn = 2; nn <= 1023; ++nn) {
         const double s = std::ldexp(1.0, nn);
-        LAUNCH_1(k_axpy_scaled, n_lp, stream, n_lp, d_ray.p, s, d_xs.p);
+        launch_n(k_axpy_scaled, n_lp, stream, n_lp, d_ray.p, s, d_xs.p);
         int64_t nviol = 0;
         double mv = 0.0;
         bool nonfin = false;
@@ -452,9 +452,9 @@ void Engine::polish_step(int32_t* done) {
 double Engine::objective_certificate(int64_t id_offset, bool raw) {
     if (m_nl <= 0) return 0.0;
     d_cert.resize((size_t)m_nl, stream);
-    LAUNCH_1(k_cert_nl, m_nl, stream, m_nl, d_nlrows.p, list_heads() + id_offset, d_cutprev.p, lp_y.p, d_g.p, d_lb.p, d_ub.p, prm.f_tol, d_cert.p);
-    hipLaunchKernelGGL(k_sum_partial, dim3(kRedBlocks), dim3(kBlock), 0, stream, m_nl, d_cert.p, partials.p);
-    hipLaunchKernelGGL(k_sum_final, dim3(1), dim3(kRedBlocks), 0, stream, partials.p, kRedBlocks, d_scal.p);
+    launch_n(k_cert_nl, m_nl, stream, m_nl, d_nlrows.p, list_heads() + id_offset, d_cutprev.p, lp_y.p, d_g.p, d_lb.p, d_ub.p, prm.f_tol, d_cert.p);
+    launch(k_sum_partial, kRedBlocks, kBlock, 0, stream, m_nl, d_cert.p, partials.p);
+    launch(k_sum_final, 1, kRedBlocks, 0, stream, partials.p, kRedBlocks, d_scal.p);
     check_launch();
     double D = 0.0;
     KTN_HIP(hipMemcpyAsync(&D, d_scal.p, sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -468,10 +468,10 @@ double Engine::objective_certificate(int64_t id_offset, bool raw) {
 double Engine::certificate_blocks(double* gap_tol) {
     if (m_nl <= 0 || n_blocks <= 0) return 0.0;
     d_cert.resize((size_t)m_nl, stream);
-    LAUNCH_1(k_cert_nl, m_nl, stream, m_nl, d_nlrows.p, list_heads(), d_cutprev.p, lp_y.p, d_g.p, d_lb.p, d_ub.p, prm.f_tol, d_cert.p);
+    launch_n(k_cert_nl, m_nl, stream, m_nl, d_nlrows.p, list_heads(), d_cutprev.p, lp_y.p, d_g.p, d_lb.p, d_ub.p, prm.f_tol, d_cert.p);
     d_certblk.resize((size_t)(2 * n_blocks), stream);
-    hipLaunchKernelGGL(k_cert_blocks, dim3((unsigned)n_blocks), dim3(kBlock), 0, stream, m_nl, d_nlrows.p, d_rowptr.p, d_col.p, d_cert.p,
-                       d_blkcol.p, n_blocks, lp_c.p, lp_x.p, prm.obj_cert_tol, d_certblk.p);
+    launch(k_cert_blocks, (unsigned)n_blocks, kBlock, 0, stream, m_nl, d_nlrows.p, d_rowptr.p, d_col.p, d_cert.p, d_blkcol.p, n_blocks, lp_c.p, lp_x.p,
+           prm.obj_cert_tol, d_certblk.p);
     check_launch();
     std::vector<double> h = d_certblk.to_host(stream);
     double worst = 0.0, gap = kInf;

@@ -505,7 +505,7 @@ struct Engine {
         }
         return ev_used++;
     }
-    // profile mode: the timed launches go through hipExtLaunchKernelGGL, whose start/stop events
+    // profile mode: the timed launches go through launch_ev (launch.hpp), whose start/stop events
     // carry the dispatch's own begin/end timestamps (what rocprofv3 --kernel-trace reports)
     void ev_flush() {   // stream must be synchronised
         static const char* names[6] = {"kx", "ky", "sweep_eval", "allreduce", "tape_eval", "quad_eval"};
@@ -644,6 +644,7 @@ struct Engine {
     bool recession_ray_dense(bool* unbounded);
     void launch_y(const SpMat& A, double sigma, double w, double rho, hipEvent_t e0, hipEvent_t e1);
     void launch_x(const SpMat& AT, double tau, double w, double rho, bool update, hipEvent_t e0, hipEvent_t e1);
+    void pdhg_iteration(const SpMat& A, const SpMat& AT, double tau, double sigma, double w, double rho);
     // w_next >= 0: the check kernels also write the Halpern update of this iteration into xnext / ynext (returns true when they did:
     // the plain CSR form only); the caller swaps them in for x / y instead of launching k_halpern2
     bool launch_check(const SpMat& A, const SpMat& AT, double tau, double sigma, double w_next = -1.0, double rho = 1.0);

@@ -206,16 +206,17 @@ void Engine::esh_search(const double* d_x, double f_tol) {
     NlpDev P = nlp_view();
     SweepOut O = sweep_view();
     d_esh_cnt.zero(stream);
-    LAUNCH_1(k_fill, m_ext, stream, m_ext, d_lam.p, 1.0);            // (rows the search leaves alone keep Kelley's cut: lambda 1)
+    launch_n(k_fill, m_ext, stream, m_ext, d_lam.p, 1.0);            // (rows the search leaves alone keep Kelley's cut: lambda 1)
     const EshArgs A{d_x, d_xint.p, d_esh_sig.p, d_lam.p, d_esh_cnt.p, prm.esh_root_tol * f_tol, prm.esh_root_iters, 0};
-    LAUNCH_G(grp_sweep, k_esh_sep, m_nl, stream, P, d_nlrows.p, m_nl, (const int64_t*)d_flag.p, A, O);
+    with_group(grp_sweep, [&](auto g) { launch(k_esh_sep<g()>, group_grid(m_nl, g()), kBlock, 0, stream, P, d_nlrows.p, m_nl, (const int64_t*)d_flag.p, A, O); });
     if (n_longev_nl > 0)
-        hipLaunchKernelGGL(k_esh_long, dim3((unsigned)n_longev_nl), dim3(1024), 0, stream, P, d_longev_nlrows.p, d_longev_nlslots.p,
-                           (const int64_t*)d_flag.p, A, O);
-    LAUNCH_1(k_esh_tape, n_tape_nl, stream, P, d_taperows_nl.p, d_tape_nlslots.p, n_tape_nl, (const int64_t*)d_flag.p, A, O);
+        launch(k_esh_long, (unsigned)n_longev_nl, 1024, 0, stream, P, d_longev_nlrows.p, d_longev_nlslots.p, (const int64_t*)d_flag.p, A, O);
+    launch_n(k_esh_tape, n_tape_nl, stream, P, d_taperows_nl.p, d_tape_nlslots.p, n_tape_nl, (const int64_t*)d_flag.p, A, O);
     if (esh_n_quad_part > 0 && n_quad_nl > 0) {         // (KTN_CUT_SUPPORTING_QUAD; d_jint stands)
         const QuadList QL{d_qrows_nl.p, d_qslots_nl.p, d_qtbase_nl.p, nullptr, n_quad_nl, n_quad_ent_nl};
-        LAUNCH_G(esh_quad_group(), k_esh_quad, n_quad_nl, stream, P, QL, (const int64_t*)d_flag.p, (const double*)d_jint.p, A, O);
+        with_group(esh_quad_group(), [&](auto g) {
+            launch(k_esh_quad<g()>, group_grid(n_quad_nl, g()), kBlock, 0, stream, P, QL, (const int64_t*)d_flag.p, (const double*)d_jint.p, A, O);
+        });
     }
     check_launch();
     unsigned long long c[3] = {0ull, 0ull, 0ull};
@@ -234,10 +235,14 @@ void Engine::esh_emit(const double* d_x, int64_t V) {
     LpRows L = lp_view();
     stats["esh_fallback_rows"] += (double)(V - (esh_on ? esh_last_rows : 0));
     if (esh_on)
-        LAUNCH_G(grp_sweep, k_emit_esh, V, stream, P, d_nlrows.p, d_violslots.p, V, d_x, (const double*)d_xint.p, (const double*)d_lam.p,
-                 d_jac.p, (const double*)(esh_n_quad_part > 0 ? d_jint.p : nullptr), d_maxc.p, prm.cut_coef_rng, 1, M, L);
+        with_group(grp_sweep, [&](auto g) {
+            launch(k_emit_esh<g()>, group_grid(V, g()), kBlock, 0, stream, P, d_nlrows.p, d_violslots.p, V, d_x, (const double*)d_xint.p,
+                   (const double*)d_lam.p, d_jac.p, (const double*)(esh_n_quad_part > 0 ? d_jint.p : nullptr), d_maxc.p, prm.cut_coef_rng, 1, M, L);
+        });
     else
-        LAUNCH_G(grp_sweep, k_emit, V, stream, P, d_nlrows.p, d_violslots.p, V, d_x, d_jac.p, d_maxc.p, prm.cut_coef_rng, 1, M, L);
+        with_group(grp_sweep, [&](auto g) {
+            launch(k_emit<g()>, group_grid(V, g()), kBlock, 0, stream, P, d_nlrows.p, d_violslots.p, V, d_x, d_jac.p, d_maxc.p, prm.cut_coef_rng, 1, M, L);
+        });
 }
 
 // ktn_sep_gencut: row i's cut at the point of the last precompute (d_xs).  Returns true when the row was cut at x_b and writes that
@@ -269,15 +274,17 @@ bool Engine::esh_gencut_row(int64_t i, double* coefs, double* constant) {
     d_esh_cnt.zero(stream);
     const EshArgs A{d_xs.p, d_xint.p, d_esh_sig.p, d_lam.p, d_esh_cnt.p, prm.esh_root_tol * prm.f_tol, prm.esh_root_iters, 1};
     if (longrow)
-        hipLaunchKernelGGL(k_esh_long, dim3(1), dim3(1024), 0, stream, P, d_esh_one.p, d_esh_slot.p, (const int64_t*)nullptr, A, O);
+        launch(k_esh_long, 1, 1024, 0, stream, P, d_esh_one.p, d_esh_slot.p, (const int64_t*)nullptr, A, O);
     else if (kind == KTN_ROW_TAPE)
-        LAUNCH_1(k_esh_tape, 1, stream, P, d_esh_one.p, d_esh_one.p, (int64_t)1, (const int64_t*)nullptr, A, O);
+        launch_n(k_esh_tape, 1, stream, P, d_esh_one.p, d_esh_one.p, (int64_t)1, (const int64_t*)nullptr, A, O);
     else if (kind == KTN_ROW_QUAD) {
         const QuadList QL{d_esh_one.p, d_esh_slot.p, nullptr, nullptr, 1, len};
-        LAUNCH_G(esh_quad_group(), k_esh_quad, 1, stream, P, QL, (const int64_t*)nullptr, (const double*)d_jint.p, A, O);
+        with_group(esh_quad_group(), [&](auto g) {
+            launch(k_esh_quad<g()>, group_grid(1, g()), kBlock, 0, stream, P, QL, (const int64_t*)nullptr, (const double*)d_jint.p, A, O);
+        });
     }
     else
-        LAUNCH_G(grp_sweep, k_esh_sep, 1, stream, P, d_esh_one.p, (int64_t)1, (const int64_t*)nullptr, A, O);
+        with_group(grp_sweep, [&](auto g) { launch(k_esh_sep<g()>, group_grid(1, g()), kBlock, 0, stream, P, d_esh_one.p, (int64_t)1, (const int64_t*)nullptr, A, O); });
     check_launch();
     unsigned long long c[3] = {0ull, 0ull, 0ull};
     KTN_HIP(hipMemcpyAsync(c, d_esh_cnt.p, sizeof(c), hipMemcpyDeviceToHost, stream));

@@ -1,85 +1,68 @@
-// launch.hpp -- launch macros shared by the translation units that launch kernels (G lanes per output selected at run time).
+// launch.hpp -- every kernel launch goes through here: the two entry points, the grid rules, and the run-time -> compile-time
+// selection of a kernel's template arguments (G lanes per output first of all).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include <type_traits>
+
 #include "common.hpp"
 #include "types.hpp"
 
-#define LAUNCH_G(G, KERNEL, count, stream, ...)                                                          \
-    do {                                                                                                 \
-        const int64_t cnt__ = (count);                                                                   \
-        if (cnt__ > 0) {                                                                                 \
-            switch (G) {                                                                                 \
-                case 4: hipLaunchKernelGGL((KERNEL<4>), dim3(ceil_div(cnt__ * 4, kBlock)), dim3(kBlock), 0, stream, __VA_ARGS__); break;   \
-                case 8: hipLaunchKernelGGL((KERNEL<8>), dim3(ceil_div(cnt__ * 8, kBlock)), dim3(kBlock), 0, stream, __VA_ARGS__); break;   \
-                case 16: hipLaunchKernelGGL((KERNEL<16>), dim3(ceil_div(cnt__ * 16, kBlock)), dim3(kBlock), 0, stream, __VA_ARGS__); break; \
-                case 32: hipLaunchKernelGGL((KERNEL<32>), dim3(ceil_div(cnt__ * 32, kBlock)), dim3(kBlock), 0, stream, __VA_ARGS__); break; \
-                default: hipLaunchKernelGGL((KERNEL<64>), dim3(ceil_div(cnt__ * 64, kBlock)), dim3(kBlock), 0, stream, __VA_ARGS__); break; \
-            }                                                                                            \
-        }                                                                                                \
-    } while (0)
+namespace ktn {
 
-#define LAUNCH_GB(G, KERNEL, B, count, stream, ...)                                                      \
-    do {                                                                                                 \
-        const int64_t cnt__ = (count);                                                                   \
-        if (cnt__ > 0) {                                                                                 \
-            switch (G) {                                                                                 \
-                case 4: hipLaunchKernelGGL((KERNEL<4, B>), dim3(ceil_div(cnt__ * 4, kBlock)), dim3(kBlock), 0, stream, __VA_ARGS__); break;   \
-                case 8: hipLaunchKernelGGL((KERNEL<8, B>), dim3(ceil_div(cnt__ * 8, kBlock)), dim3(kBlock), 0, stream, __VA_ARGS__); break;   \
-                case 16: hipLaunchKernelGGL((KERNEL<16, B>), dim3(ceil_div(cnt__ * 16, kBlock)), dim3(kBlock), 0, stream, __VA_ARGS__); break; \
-                case 32: hipLaunchKernelGGL((KERNEL<32, B>), dim3(ceil_div(cnt__ * 32, kBlock)), dim3(kBlock), 0, stream, __VA_ARGS__); break; \
-                default: hipLaunchKernelGGL((KERNEL<64, B>), dim3(ceil_div(cnt__ * 64, kBlock)), dim3(kBlock), 0, stream, __VA_ARGS__); break; \
-            }                                                                                            \
-        }                                                                                                \
-    } while (0)
+// ---- grid rules (workgroups of kBlock threads); a count <= 0 gives 0 workgroups, which the launchers skip
+inline unsigned grid_n(int64_t count) { return count > 0 ? (unsigned)ceil_div(count, kBlock) : 0u; }               // a thread per item
+inline unsigned group_grid(int64_t count, int G, int T = 1) {                                                      // G lanes per T outputs
+    return count > 0 ? (unsigned)ceil_div(count * G, kBlock * T) : 0u;
+}
+// G lanes per output, then one trailing workgroup per long output
+inline unsigned group_grid_long(int64_t count, int G, int64_t n_long) { return group_grid(count, G) + (unsigned)n_long; }
 
-// same, with the kernel's own start/stop timestamps recorded into (E0, E1)
-#define LAUNCH_G_EV(G, KERNEL, count, stream, E0, E1, ...)                                               \
-    do {                                                                                                 \
-        const int64_t cnt__ = (count);                                                                   \
-        if (cnt__ > 0) {                                                                                 \
-            switch (G) {                                                                                 \
-                case 4: hipExtLaunchKernelGGL((KERNEL<4>), dim3(ceil_div(cnt__ * 4, kBlock)), dim3(kBlock), 0, stream, E0, E1, 0, __VA_ARGS__); break;   \
-                case 8: hipExtLaunchKernelGGL((KERNEL<8>), dim3(ceil_div(cnt__ * 8, kBlock)), dim3(kBlock), 0, stream, E0, E1, 0, __VA_ARGS__); break;   \
-                case 16: hipExtLaunchKernelGGL((KERNEL<16>), dim3(ceil_div(cnt__ * 16, kBlock)), dim3(kBlock), 0, stream, E0, E1, 0, __VA_ARGS__); break; \
-                case 32: hipExtLaunchKernelGGL((KERNEL<32>), dim3(ceil_div(cnt__ * 32, kBlock)), dim3(kBlock), 0, stream, E0, E1, 0, __VA_ARGS__); break; \
-                default: hipExtLaunchKernelGGL((KERNEL<64>), dim3(ceil_div(cnt__ * 64, kBlock)), dim3(kBlock), 0, stream, E0, E1, 0, __VA_ARGS__); break; \
-            }                                                                                            \
-        }                                                                                                \
-    } while (0)
+// ---- the two entry points.  A site keeps the one it has: the Ext one where a launch can carry the kernel's own start / stop
+// events (null outside profile mode), the plain one everywhere else.  A zero-size grid is skipped.
+template <class... P, class... A>
+inline void launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, A&&... args) {
+    if (grid.x == 0) return;
+    hipLaunchKernelGGL(kernel, grid, block, lds, stream, static_cast<P>(args)...);
+}
 
-#define LAUNCH_GB_EV(G, KERNEL, B, count, stream, E0, E1, ...)                                           \
-    do {                                                                                                 \
-        const int64_t cnt__ = (count);                                                                   \
-        if (cnt__ > 0) {                                                                                 \
-            switch (G) {                                                                                 \
-                case 4: hipExtLaunchKernelGGL((KERNEL<4, B>), dim3(ceil_div(cnt__ * 4, kBlock)), dim3(kBlock), 0, stream, E0, E1, 0, __VA_ARGS__); break;   \
-                case 8: hipExtLaunchKernelGGL((KERNEL<8, B>), dim3(ceil_div(cnt__ * 8, kBlock)), dim3(kBlock), 0, stream, E0, E1, 0, __VA_ARGS__); break;   \
-                case 16: hipExtLaunchKernelGGL((KERNEL<16, B>), dim3(ceil_div(cnt__ * 16, kBlock)), dim3(kBlock), 0, stream, E0, E1, 0, __VA_ARGS__); break; \
-                case 32: hipExtLaunchKernelGGL((KERNEL<32, B>), dim3(ceil_div(cnt__ * 32, kBlock)), dim3(kBlock), 0, stream, E0, E1, 0, __VA_ARGS__); break; \
-                default: hipExtLaunchKernelGGL((KERNEL<64, B>), dim3(ceil_div(cnt__ * 64, kBlock)), dim3(kBlock), 0, stream, E0, E1, 0, __VA_ARGS__); break; \
-            }                                                                                            \
-        }                                                                                                \
-    } while (0)
+template <class... P, class... A>
+inline void launch_ev(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, hipEvent_t e0, hipEvent_t e1,
+                      A&&... args) {
+    if (grid.x == 0) return;
+    hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t)lds, stream, e0, e1, 0, static_cast<P>(args)...);
+}
 
-// G lanes per output, T outputs per lane group: grid = ceil(count * G / (kBlock * T))
-#define LAUNCH_GT(G, T, KERNEL, count, stream, E0, E1, ...)                                              \
-    do {                                                                                                 \
-        const int64_t cnt__ = (count);                                                                   \
-        if (cnt__ > 0) {                                                                                 \
-            switch (G) {                                                                                 \
-                case 4: hipExtLaunchKernelGGL((KERNEL<4, T>), dim3(ceil_div(cnt__ * 4, kBlock * T)), dim3(kBlock), 0, stream, E0, E1, 0, __VA_ARGS__); break;   \
-                case 8: hipExtLaunchKernelGGL((KERNEL<8, T>), dim3(ceil_div(cnt__ * 8, kBlock * T)), dim3(kBlock), 0, stream, E0, E1, 0, __VA_ARGS__); break;   \
-                case 16: hipExtLaunchKernelGGL((KERNEL<16, T>), dim3(ceil_div(cnt__ * 16, kBlock * T)), dim3(kBlock), 0, stream, E0, E1, 0, __VA_ARGS__); break; \
-                case 32: hipExtLaunchKernelGGL((KERNEL<32, T>), dim3(ceil_div(cnt__ * 32, kBlock * T)), dim3(kBlock), 0, stream, E0, E1, 0, __VA_ARGS__); break; \
-                default: hipExtLaunchKernelGGL((KERNEL<64, T>), dim3(ceil_div(cnt__ * 64, kBlock * T)), dim3(kBlock), 0, stream, E0, E1, 0, __VA_ARGS__); break; \
-            }                                                                                            \
-        }                                                                                                \
-    } while (0)
+// the sites that are timed in profile mode only: the plain entry point without events, the Ext one with either of them
+template <class... P, class... A>
+inline void launch_timed(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, hipEvent_t e0, hipEvent_t e1,
+                         A&&... args) {
+    if (e0 || e1) launch_ev(kernel, grid, block, lds, stream, e0, e1, args...);
+    else launch(kernel, grid, block, lds, stream, args...);
+}
 
-#define LAUNCH_1(KERNEL, count, stream, ...)                                                             \
-    do {                                                                                                 \
-        const int64_t cnt__ = (count);                                                                   \
-        if (cnt__ > 0) hipLaunchKernelGGL(KERNEL, dim3(ceil_div(cnt__, kBlock)), dim3(kBlock), 0, stream, __VA_ARGS__); \
-    } while (0)
+// a thread per item, kBlock threads per workgroup
+template <class... P, class... A>
+inline void launch_n(void (*kernel)(P...), int64_t count, hipStream_t stream, A&&... args) {
+    launch(kernel, grid_n(count), kBlock, 0, stream, args...);
+}
+
+// ---- f(std::integral_constant<., V>) for the V of the list that equals v; the LAST entry is the fallback for any other v.
+// (`auto`, not `void`: a deduced return type makes the compiler instantiate these where they are called and not at the end of
+//  the translation unit, so a unit's kernels are emitted in the order its launches are written.)
+template <auto V0, auto... Vs, class T, class F>
+inline auto with_value(T v, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<decltype(V0), V0>{});
+    else if (v == (T)V0) f(std::integral_constant<decltype(V0), V0>{});
+    else with_value<Vs...>(v, f);
+}
+
+// lanes per output: with_group(G, [&](auto g) { launch(k<g()>, group_grid(count, g()), kBlock, 0, stream, ...); })
+template <class F>
+inline auto with_group(int G, F&& f) { with_value<4, 8, 16, 32, 64>(G, f); }
+
+template <class F>
+inline auto with_bool(bool b, F&& f) { with_value<true, false>(b, f); }
+
+}  // namespace ktn

@@ -11,8 +11,8 @@ namespace ktn {
 
 // --------------------------------------------------------------- reductions ---
 double Engine::dev_dot(int64_t n, const double* a, const double* b) {
-    hipLaunchKernelGGL(k_dot_partial, dim3(kRedBlocks), dim3(kBlock), 0, stream, n, a, b, partials.p);
-    hipLaunchKernelGGL(k_sum_final, dim3(1), dim3(kRedBlocks), 0, stream, partials.p, kRedBlocks, chkout.p + 2 * kChkQ);
+    launch(k_dot_partial, kRedBlocks, kBlock, 0, stream, n, a, b, partials.p);
+    launch(k_sum_final, 1, kRedBlocks, 0, stream, partials.p, kRedBlocks, chkout.p + 2 * kChkQ);
     double v = 0.0;
     KTN_HIP(hipMemcpyAsync(&v, chkout.p + 2 * kChkQ, sizeof(double), hipMemcpyDeviceToHost, stream));
     sync();
@@ -20,8 +20,8 @@ double Engine::dev_dot(int64_t n, const double* a, const double* b) {
 }
 
 double Engine::dev_finite_sq(int64_t n, const double* a) {
-    hipLaunchKernelGGL(k_finite_sq_partial, dim3(kRedBlocks), dim3(kBlock), 0, stream, n, a, partials.p);
-    hipLaunchKernelGGL(k_sum_final, dim3(1), dim3(kRedBlocks), 0, stream, partials.p, kRedBlocks, chkout.p + 2 * kChkQ);
+    launch(k_finite_sq_partial, kRedBlocks, kBlock, 0, stream, n, a, partials.p);
+    launch(k_sum_final, 1, kRedBlocks, 0, stream, partials.p, kRedBlocks, chkout.p + 2 * kChkQ);
     double v = 0.0;
     KTN_HIP(hipMemcpyAsync(&v, chkout.p + 2 * kChkQ, sizeof(double), hipMemcpyDeviceToHost, stream));
     sync();
@@ -32,12 +32,11 @@ double Engine::dev_finite_sq(int64_t n, const double* a) {
 void Engine::spmv_cols(const SpMat& AT, const double* v, double* out, hipEvent_t e0, hipEvent_t e1) {
     const int64_t n = n_lp;
     if (n_longc > 0) {
-        LAUNCH_G(grp_cols, k_spmv_skip, n, stream, n, AT, v, out, kLongRow);
-        hipLaunchKernelGGL(k_spmv_long, dim3((unsigned)n_longc), dim3(1024), 0, stream, d_longcols.p, AT, v, out);
-    } else if (e0) {
-        LAUNCH_G_EV(grp_cols, k_spmv, n, stream, e0, e1, n, AT, v, out);
+        // (timed as a pair: the first kernel's start, the second one's stop)
+        with_group(grp_cols, [&](auto g) { launch_timed(k_spmv_skip<g()>, group_grid(n, g()), kBlock, 0, stream, e0, nullptr, n, AT, v, out, kLongRow); });
+        launch_timed(k_spmv_long, (unsigned)n_longc, 1024, 0, stream, nullptr, e1, d_longcols.p, AT, v, out);
     } else {
-        LAUNCH_G(grp_cols, k_spmv, n, stream, n, AT, v, out);
+        with_group(grp_cols, [&](auto g) { launch_timed(k_spmv<g()>, group_grid(n, g()), kBlock, 0, stream, e0, e1, n, AT, v, out); });
     }
 }
 
@@ -57,11 +56,11 @@ void Engine::compute_scaling(bool identity) {
     if (warm) {
         KTN_HIP(hipMemcpyAsync(dr.p, dr_r.p, (size_t)scal_rows * sizeof(double), hipMemcpyDeviceToDevice, stream));
         KTN_HIP(hipMemcpyAsync(dc.p, dc_r.p, (size_t)n_lp * sizeof(double), hipMemcpyDeviceToDevice, stream));
-        LAUNCH_1(k_fill, M - scal_rows, stream, M - scal_rows, dr.p + scal_rows, 1.0);
+        launch_n(k_fill, M - scal_rows, stream, M - scal_rows, dr.p + scal_rows, 1.0);
         stats["lp_scaling_warm"] += 1.0;
     } else {
-        LAUNCH_1(k_fill, M, stream, M, dr.p, 1.0);
-        LAUNCH_1(k_fill, n_lp, stream, n_lp, dc.p, 1.0);
+        launch_n(k_fill, M, stream, M, dr.p, 1.0);
+        launch_n(k_fill, n_lp, stream, n_lp, dc.p, 1.0);
     }
     const int gr = pick_group((double)NNZ / (double)std::max<int64_t>(M, 1));
     const int gc = pick_group((double)NNZ / (double)std::max<int64_t>(n_lp, 1));
@@ -77,32 +76,39 @@ void Engine::compute_scaling(bool identity) {
             if (n_long == 0 && n_longc == 0 && !row_sharded() && M > 0) {
                 // statistic + update of BOTH sides in one launch, into new arrays that are swapped in (9 launches; round 1: 33, round 2: 22)
                 dr2.resize((size_t)M, stream); dc2.resize((size_t)n_lp, stream);
-                const int br = ceil_div(M * gr, kBlock), bc = ceil_div(n_lp * gc, kBlock);
-                hipLaunchKernelGGL(k_scale_stat_upd_both, dim3((unsigned)(br + bc)), dim3(kBlock), 0, stream, M, lp_rowptr.p, lp_col.p, Wval(), n_lp,
-                                   c_ptr.p, c_row.p, c_val.p, dr.p, dc.p, mode, dr2.p, dc2.p, cap_c, gr, gc, br);
+                const unsigned br = group_grid(M, gr), bc = group_grid(n_lp, gc);
+                launch(k_scale_stat_upd_both, br + bc, kBlock, 0, stream, M, lp_rowptr.p, lp_col.p, Wval(), n_lp, c_ptr.p, c_row.p, c_val.p, dr.p, dc.p, mode,
+                       dr2.p, dc2.p, cap_c, gr, gc, br);
                 dr.swap(dr2); dc.swap(dc2);
                 stats["lp_scale_fused_passes"] += 1.0;
                 continue;
             }
             if (n_long > 0) {
-                LAUNCH_G(gr, k_scale_stat_skip, M, stream, M, lp_rowptr.p, lp_col.p, Wval(), dr.p, dc.p, mode, statr.p, kLongRow);
-                hipLaunchKernelGGL(k_scale_stat_long, dim3((unsigned)n_long), dim3(1024), 0, stream, d_longrows.p, lp_rowptr.p, lp_col.p,
-                                   Wval(), dr.p, dc.p, mode, statr.p);
+                with_group(gr, [&](auto g) {
+                    launch(k_scale_stat_skip<g()>, group_grid(M, g()), kBlock, 0, stream, M, lp_rowptr.p, lp_col.p, Wval(), dr.p, dc.p, mode, statr.p, kLongRow);
+                });
+                launch(k_scale_stat_long, (unsigned)n_long, 1024, 0, stream, d_longrows.p, lp_rowptr.p, lp_col.p, Wval(), dr.p, dc.p, mode, statr.p);
             } else {
-                LAUNCH_G(gr, k_scale_stat, M, stream, M, lp_rowptr.p, lp_col.p, Wval(), dr.p, dc.p, mode, statr.p);
+                with_group(gr, [&](auto g) {
+                    launch(k_scale_stat<g()>, group_grid(M, g()), kBlock, 0, stream, M, lp_rowptr.p, lp_col.p, Wval(), dr.p, dc.p, mode, statr.p);
+                });
             }
             if (n_longc > 0) {
-                LAUNCH_G(gc, k_scale_stat_skip, n_lp, stream, n_lp, c_ptr.p, c_row.p, c_val.p, dc.p, dr.p, mode, statc.p, kLongRow);
-                hipLaunchKernelGGL(k_scale_stat_long, dim3((unsigned)n_longc), dim3(1024), 0, stream, d_longcols.p, c_ptr.p, c_row.p,
-                                   c_val.p, dc.p, dr.p, mode, statc.p);
+                with_group(gc, [&](auto g) {
+                    launch(k_scale_stat_skip<g()>, group_grid(n_lp, g()), kBlock, 0, stream, n_lp, c_ptr.p, c_row.p, c_val.p, dc.p, dr.p, mode, statc.p,
+                           kLongRow);
+                });
+                launch(k_scale_stat_long, (unsigned)n_longc, 1024, 0, stream, d_longcols.p, c_ptr.p, c_row.p, c_val.p, dc.p, dr.p, mode, statc.p);
             } else {
-                LAUNCH_G(gc, k_scale_stat, n_lp, stream, n_lp, c_ptr.p, c_row.p, c_val.p, dc.p, dr.p, mode, statc.p);
+                with_group(gc, [&](auto g) {
+                    launch(k_scale_stat<g()>, group_grid(n_lp, g()), kBlock, 0, stream, n_lp, c_ptr.p, c_row.p, c_val.p, dc.p, dr.p, mode, statc.p);
+                });
             }
             if (row_sharded()) {                       // a column's max / sum runs over the rows of every rank
-                if (M == 0) LAUNCH_1(k_fill, n_lp, stream, n_lp, statc.p, 0.0);
+                if (M == 0) launch_n(k_fill, n_lp, stream, n_lp, statc.p, 0.0);
                 allreduce(statc.p, (size_t)n_lp, mode ? 0 : 1);
             }
-            LAUNCH_1(k_scale_apply2, std::max(M, n_lp), stream, M, dr.p, statr.p, n_lp, dc.p, statc.p, cap_c);
+            launch_n(k_scale_apply2, std::max(M, n_lp), stream, M, dr.p, statr.p, n_lp, dc.p, statc.p, cap_c);
             stats["lp_scale_split_passes"] += 1.0;
         }
     }
@@ -112,20 +118,19 @@ void Engine::compute_scaling(bool identity) {
     c_sval.resize((size_t)NNZ + 1, stream);
     // (long columns: the mirror's scaled values are gathered entry-parallel from the row copy instead of walked column by column)
     if (n_longc > 0 || M == 0) {
-        LAUNCH_G(gr, k_scale_vals, M, stream, M, lp_rowptr.p, lp_col.p, Wval(), dr.p, dc.p, r_sval.p);
-        if (n_longc > 0) LAUNCH_1(k_csc_vals, NNZ, stream, NNZ, c_perm.p, r_sval.p, c_sval.p);
-        else LAUNCH_G(gc, k_scale_vals, n_lp, stream, n_lp, c_ptr.p, c_row.p, c_val.p, dc.p, dr.p, c_sval.p);
+        with_group(gr, [&](auto g) { launch(k_scale_vals<g()>, group_grid(M, g()), kBlock, 0, stream, M, lp_rowptr.p, lp_col.p, Wval(), dr.p, dc.p, r_sval.p); });
+        if (n_longc > 0) launch_n(k_csc_vals, NNZ, stream, NNZ, c_perm.p, r_sval.p, c_sval.p);
+        else with_group(gc, [&](auto g) { launch(k_scale_vals<g()>, group_grid(n_lp, g()), kBlock, 0, stream, n_lp, c_ptr.p, c_row.p, c_val.p, dc.p, dr.p, c_sval.p); });
     } else {                                            // both copies in one launch
-        const int br = ceil_div(M * gr, kBlock), bc = ceil_div(n_lp * gc, kBlock);
-        hipLaunchKernelGGL(k_scale_vals_both, dim3((unsigned)(br + bc)), dim3(kBlock), 0, stream, M, lp_rowptr.p, lp_col.p, Wval(), n_lp, c_ptr.p, c_row.p,
-                           c_val.p, dr.p, dc.p, r_sval.p, c_sval.p, gr, gc, br);
+        const unsigned br = group_grid(M, gr), bc = group_grid(n_lp, gc);
+        launch(k_scale_vals_both, br + bc, kBlock, 0, stream, M, lp_rowptr.p, lp_col.p, Wval(), n_lp, c_ptr.p, c_row.p, c_val.p, dr.p, dc.p, r_sval.p, c_sval.p,
+               gr, gc, br);
     }
     check_launch();
 }
 
 void Engine::launch_tiled(const TiledBuf& T, int64_t n_out, int64_t n_in, const double* in, hipEvent_t e0) {
-    hipExtLaunchKernelGGL(k_spmv_tiled, dim3((unsigned)T.grid), dim3(kTileThreads), 0, stream, e0, nullptr, 0, n_out, n_in, T.tiles,
-                          T.view(), in, tpart.p);
+    launch_ev(k_spmv_tiled, (unsigned)T.grid, kTileThreads, 0, stream, e0, nullptr, n_out, n_in, T.tiles, T.view(), in, tpart.p);
 }
 
 // Tiled copy of a sparse matrix given by (ptr, idx, val) over n_out outputs and n_in inputs; outputs longer than
@@ -150,17 +155,17 @@ bool Engine::build_tiled(TiledBuf& T, int64_t n_out, int64_t n_in, const int64_t
         T.segtot.zero(stream);
         KTN_HIP(hipMemsetAsync(d_anynf.p + 1, 0, sizeof(int32_t), stream));
         if (pass == 0) {
-            LAUNCH_1(k_tile_count_sorted, n_out, stream, n_out, ptr, idx, T.nb_in, skip_longer, T.bptr.p, d_anynf.p + 1);
+            launch_n(k_tile_count_sorted, n_out, stream, n_out, ptr, idx, T.nb_in, skip_longer, T.bptr.p, d_anynf.p + 1);
         } else {
             T.cur.resize(cells * (kTileOut + 1), stream);
             T.cur.zero(stream);
-            LAUNCH_1(k_tile_count, n_out, stream, n_out, ptr, idx, T.nb_in, skip_longer, T.bptr.p, d_anynf.p + 1);
+            launch_n(k_tile_count, n_out, stream, n_out, ptr, idx, T.nb_in, skip_longer, T.bptr.p, d_anynf.p + 1);
         }
-        hipLaunchKernelGGL(k_tile_scan, dim3((unsigned)cells), dim3(kTileThreads), 0, stream, T.bptr.p, T.segtot.p, d_anynf.p + 1);
+        launch(k_tile_scan, (unsigned)cells, kTileThreads, 0, stream, T.bptr.p, T.segtot.p, d_anynf.p + 1);
         check_launch();
         exclusive_scan(T.segtot.p, T.segstart.p, cells + 1);
-        if (pass == 0) LAUNCH_1(k_tile_fill_sorted, n_out, stream, n_out, ptr, idx, val, T.nb_in, skip_longer, T.bptr.p, T.segstart.p, d_anynf.p + 1, T.idx.p, T.val.p);
-        else LAUNCH_1(k_tile_fill, n_out, stream, n_out, ptr, idx, val, T.nb_in, skip_longer, T.bptr.p, T.cur.p, T.segstart.p, T.idx.p, T.val.p);
+        if (pass == 0) launch_n(k_tile_fill_sorted, n_out, stream, n_out, ptr, idx, val, T.nb_in, skip_longer, T.bptr.p, T.segstart.p, d_anynf.p + 1, T.idx.p, T.val.p);
+        else launch_n(k_tile_fill, n_out, stream, n_out, ptr, idx, val, T.nb_in, skip_longer, T.bptr.p, T.cur.p, T.segstart.p, T.idx.p, T.val.p);
         check_launch();
         KTN_HIP(hipMemcpyAsync(&ovf, d_anynf.p + 1, 4, hipMemcpyDeviceToHost, stream));
         sync();
@@ -194,15 +199,15 @@ void Engine::build_blocks() {
     d_crowl.resize((size_t)NNZ + 1, stream);
     k_in.resize((size_t)std::max<int64_t>(M, 1), stream); k_out.resize((size_t)std::max<int64_t>(M, 1), stream);
     p_in.resize((size_t)std::max<int64_t>(M, 1), stream); p_out.resize((size_t)std::max<int64_t>(M, 1), stream);
-    LAUNCH_1(k_row_block, M, stream, M, lp_rowptr.p, lp_col.p, d_blkcol.p, nb, k_in.p, p_in.p);
+    launch_n(k_row_block, M, stream, M, lp_rowptr.p, lp_col.p, d_blkcol.p, nb, k_in.p, p_in.p);
     int bits = 1;
     while ((1 << bits) < nb + 1 && bits < 30) ++bits;
     const size_t need = sort_pairs_temp_bytes((size_t)M);
     d_sorttmp.resize(need + 16, stream);
     KTN_HIP(sort_pairs_u64_u32(d_sorttmp.p, need, k_in.p, k_out.p, p_in.p, p_out.p, (size_t)M, 0, bits, stream));   // stable: rows ascending
-    LAUNCH_1(k_block_rows, M, stream, M, k_out.p, p_out.p, nb, d_blkrowptr.p, d_blkrows.p, d_rowloc.p);
-    LAUNCH_1(k_row_local, M, stream, M, k_out.p, p_out.p, d_blkrowptr.p, d_rowloc.p);
-    LAUNCH_1(k_localize_rows, NNZ, stream, NNZ, c_row.p, d_rowloc.p, d_crowl.p);
+    launch_n(k_block_rows, M, stream, M, k_out.p, p_out.p, nb, d_blkrowptr.p, d_blkrows.p, d_rowloc.p);
+    launch_n(k_row_local, M, stream, M, k_out.p, p_out.p, d_blkrowptr.p, d_rowloc.p);
+    launch_n(k_localize_rows, NNZ, stream, NNZ, c_row.p, d_rowloc.p, d_crowl.p);
     check_launch();
     std::vector<int32_t> rp = d_blkrowptr.to_host(stream);
     blk_mmax = 1;
@@ -233,7 +238,7 @@ bool Engine::lp_solve_blocks(double tol_p, double tol_g, double eta, LpResult* R
     P.check_every = std::max(2, prm.lp_check_every); P.first_chunk = 31; P.near_chunk = prm.lp_near_check;
     P.max_iter = (int)std::min<int64_t>(max_it, 2000000000);
     P.nmax = blk_nmax; P.mmax = blk_mmax;
-    hipLaunchKernelGGL(k_pdhg_blocks, dim3((unsigned)nb), dim3(kBlkThreads), lds, stream, P);
+    launch(k_pdhg_blocks, (unsigned)nb, kBlkThreads, lds, stream, P);
     check_launch();
     std::vector<double> res = d_blkres.to_host(stream);
     bool all_ok = true;
@@ -261,37 +266,28 @@ void Engine::launch_y(const SpMat& A, double sigma, double w, double rho, hipEve
     const int64_t thr = n_long > 0 ? kLongRow : (int64_t)1 << 62;
     if (tiled_on && m > 0) {
         launch_tiled(tA, m, n_lp, xbar.p, e0);
-        hipExtLaunchKernelGGL(k_y_epilogue, dim3(ceil_div(m, kBlock)), dim3(kBlock), 0, stream, nullptr, e1, 0, m, tA.pcnt.p,
-                              tpart.p, (n_long > 0 ? A.ptr : (const int64_t*)nullptr), thr, yh.p, y0h.p,
-                              loh.p, hih.p, sigma, w, rho);
+        launch_ev(k_y_epilogue, grid_n(m), kBlock, 0, stream, nullptr, e1, m, tA.pcnt.p, tpart.p, (n_long > 0 ? A.ptr : (const int64_t*)nullptr), thr, yh.p,
+                  y0h.p, loh.p, hih.p, sigma, w, rho);
     } else if (packed_on) {
+        // T rows per lane group; T = 1 is one launch for all rows: the regular lane groups plus one trailing workgroup per long row
         const int thr32 = n_long > 0 ? (int)kLongRow : 0x7fffffff;
-        const int32_t* none = nullptr;
-        if (packed_trips == 2) LAUNCH_GT(grp_rows, 2, k_pdhg_y_packed, m, stream, e0, e1, m, A.idx, A.val, xbar.p, yh.p, d_rrec.p, sigma, w, rho, thr32, none, 0);
-        else if (packed_trips == 4) LAUNCH_GT(grp_rows, 4, k_pdhg_y_packed, m, stream, e0, e1, m, A.idx, A.val, xbar.p, yh.p, d_rrec.p, sigma, w, rho, thr32, none, 0);
-        else {
-            // one launch for all rows: the regular lane groups plus one trailing workgroup per long row
-            const unsigned grid = (unsigned)(ceil_div(m * grp_rows, (int64_t)kBlock) + n_long);
-#define KTN_Y_PACKED(G) hipExtLaunchKernelGGL((k_pdhg_y_packed<G, 1>), dim3(grid), dim3(kBlock), 0, stream, e0, e1, 0, m, A.idx, A.val, xbar.p, yh.p, \
-                                              d_rrec.p, sigma, w, rho, thr32, (const int32_t*)d_longrows.p, (int)n_long)
-            switch (grp_rows) {
-                case 4: KTN_Y_PACKED(4); break;
-                case 8: KTN_Y_PACKED(8); break;
-                case 16: KTN_Y_PACKED(16); break;
-                case 32: KTN_Y_PACKED(32); break;
-                default: KTN_Y_PACKED(64); break;
-            }
-#undef KTN_Y_PACKED
-            return;
-        }
-    } else if (e0) {
-        LAUNCH_G_EV(grp_rows, k_pdhg_y, m, stream, e0, e1, m, A, xbar.p, yh.p, y0h.p, loh.p, hih.p, sigma, w, rho, thr);
+        const bool with_long = packed_trips != 2 && packed_trips != 4;
+        with_value<2, 4, 1>(packed_trips, [&](auto t) {
+            with_group(grp_rows, [&](auto g) {
+                constexpr int G = g(), T = t();
+                launch_ev(k_pdhg_y_packed<G, T>, T == 1 ? group_grid_long(m, G, n_long) : group_grid(m, G, T), kBlock, 0, stream, e0, e1, m, A.idx, A.val,
+                          xbar.p, yh.p, d_rrec.p, sigma, w, rho, thr32, T == 1 ? (const int32_t*)d_longrows.p : nullptr, T == 1 ? (int)n_long : 0);
+            });
+        });
+        if (with_long) return;
     } else {
-        LAUNCH_G(grp_rows, k_pdhg_y, m, stream, m, A, xbar.p, yh.p, y0h.p, loh.p, hih.p, sigma, w, rho, thr);
+        with_group(grp_rows, [&](auto g) {
+            launch_timed(k_pdhg_y<g()>, group_grid(m, g()), kBlock, 0, stream, e0, e1, m, A, xbar.p, yh.p, y0h.p, loh.p, hih.p, sigma, w, rho, thr);
+        });
     }
     if (n_long > 0)
-        hipLaunchKernelGGL((k_pdhg_y_long<false>), dim3((unsigned)n_long), dim3(kLongBlock), 0, stream, d_longrows.p, A, xbar.p,
-                           (const double*)nullptr, yh.p, y0h.p, yth.p, loh.p, hih.p, dr.p, sigma, w, rho, (double*)nullptr);
+        launch(k_pdhg_y_long<false>, (unsigned)n_long, kLongBlock, 0, stream, d_longrows.p, A, xbar.p, (const double*)nullptr, yh.p, y0h.p, yth.p, loh.p, hih.p,
+               dr.p, sigma, w, rho, (double*)nullptr);
 }
 
 void Engine::launch_x(const SpMat& AT, double tau, double w, double rho, bool update, hipEvent_t e0, hipEvent_t e1) {
@@ -302,55 +298,75 @@ void Engine::launch_x(const SpMat& AT, double tau, double w, double rho, bool up
         //  ranks' slots itself -- spmv, one single-workgroup barrier kernel, prox: no reduction pass, no copy)
         const bool ipc = dist.ipc.on && n <= dist.ipc.cap;
         double* part = ipc ? ipc_slot() : pv.p;
-        if (M == 0) LAUNCH_1(k_fill, n, stream, n, part, 0.0);
+        if (M == 0) launch_n(k_fill, n, stream, n, part, 0.0);
         if (tiled_on && M > 0) {                          // this rank's block is large: its partial A_r'y_r from the tiled copy
             launch_tiled(tAT, n, M, yh.p, e0);
-            hipExtLaunchKernelGGL(k_tile_vec, dim3(ceil_div(n, kBlock)), dim3(kBlock), 0, stream, nullptr, e1, 0, n, tAT.pcnt.p, tpart.p, part);
+            launch_ev(k_tile_vec, grid_n(n), kBlock, 0, stream, nullptr, e1, n, tAT.pcnt.p, tpart.p, part);
         }
         else spmv_cols(AT, yh.p, part, e0, e1);
         if (ipc) {
             stats["allreduce_calls"] += 1.0;
             stats["allreduce_bytes"] += 8.0 * (double)n;
             const int64_t off = ipc_barrier();
-            if (update) LAUNCH_1(k_x_prox_ipc<true>, n, stream, n, dist.ipc.P, dist.world, off, xh.p, x0h.p, xth.p, xbar.p, ch.p, lh.p, uh.p, tau, w, rho);
-            else LAUNCH_1(k_x_prox_ipc<false>, n, stream, n, dist.ipc.P, dist.world, off, xh.p, x0h.p, xth.p, xbar.p, ch.p, lh.p, uh.p, tau, w, rho);
+            with_bool(update, [&](auto u) {
+                launch_n(k_x_prox_ipc<u()>, n, stream, n, dist.ipc.P, dist.world, off, xh.p, x0h.p, xth.p, xbar.p, ch.p, lh.p, uh.p, tau, w, rho);
+            });
             return;
         }
         allreduce(pv.p, (size_t)n, 0);
-        if (update) LAUNCH_1(k_x_prox<true>, n, stream, n, pv.p, xh.p, x0h.p, xth.p, xbar.p, ch.p, lh.p, uh.p, tau, w, rho);
-        else LAUNCH_1(k_x_prox<false>, n, stream, n, pv.p, xh.p, x0h.p, xth.p, xbar.p, ch.p, lh.p, uh.p, tau, w, rho);
+        with_bool(update, [&](auto u) { launch_n(k_x_prox<u()>, n, stream, n, pv.p, xh.p, x0h.p, xth.p, xbar.p, ch.p, lh.p, uh.p, tau, w, rho); });
         return;
     }
     if (n_longc > 0 && !(tiled_on && M > 0)) {
         // long columns: lane groups for the ordinary columns, a workgroup per long one -- the primal step fused into both
-        if (update) {
-            LAUNCH_GB(grp_cols, k_pdhg_x_skip, true, n, stream, n, AT, yh.p, xh.p, x0h.p, xth.p, xbar.p, ch.p, lh.p, uh.p, tau, w, rho, kLongRow);
-            hipLaunchKernelGGL((k_pdhg_x_long<true>), dim3((unsigned)n_longc), dim3(1024), 0, stream, d_longcols.p, AT, yh.p, xh.p, x0h.p, xth.p,
-                               xbar.p, ch.p, lh.p, uh.p, tau, w, rho);
-        } else {
-            LAUNCH_GB(grp_cols, k_pdhg_x_skip, false, n, stream, n, AT, yh.p, xh.p, x0h.p, xth.p, xbar.p, ch.p, lh.p, uh.p, tau, w, rho, kLongRow);
-            hipLaunchKernelGGL((k_pdhg_x_long<false>), dim3((unsigned)n_longc), dim3(1024), 0, stream, d_longcols.p, AT, yh.p, xh.p, x0h.p, xth.p,
-                               xbar.p, ch.p, lh.p, uh.p, tau, w, rho);
-        }
+        // (timed as a pair: the first kernel's start, the second one's stop)
+        with_bool(update, [&](auto u) {
+            constexpr bool U = u();
+            with_group(grp_cols, [&](auto g) {
+                launch_timed(k_pdhg_x_skip<g(), U>, group_grid(n, g()), kBlock, 0, stream, e0, nullptr, n, AT, yh.p, xh.p, x0h.p, xth.p, xbar.p, ch.p,
+                             lh.p, uh.p, tau, w, rho, kLongRow);
+            });
+            launch_timed(k_pdhg_x_long<U>, (unsigned)n_longc, 1024, 0, stream, nullptr, e1, d_longcols.p, AT, yh.p, xh.p, x0h.p, xth.p, xbar.p, ch.p,
+                         lh.p, uh.p, tau, w, rho);
+        });
         return;
     }
-    if (update) {
-        if (tiled_on && M > 0) {
-            launch_tiled(tAT, n, M, yh.p, e0);
-            hipExtLaunchKernelGGL(k_x_epilogue, dim3(ceil_div(n, kBlock)), dim3(kBlock), 0, stream, nullptr, e1, 0, n, tAT.pcnt.p,
-                                  tpart.p, xh.p, x0h.p, xbar.p, ch.p, lh.p, uh.p, tau, w, rho);
-        } else if (packed_on) {
-            if (packed_trips == 2) LAUNCH_GT(grp_cols, 2, k_pdhg_x_packed, n, stream, e0, e1, n, d_cbl.p, AT.idx, AT.val, yh.p, xh.p, xbar.p, d_crec.p, tau, w, rho);
-            else if (packed_trips == 4) LAUNCH_GT(grp_cols, 4, k_pdhg_x_packed, n, stream, e0, e1, n, d_cbl.p, AT.idx, AT.val, yh.p, xh.p, xbar.p, d_crec.p, tau, w, rho);
-            else LAUNCH_GT(grp_cols, 1, k_pdhg_x_packed, n, stream, e0, e1, n, d_cbl.p, AT.idx, AT.val, yh.p, xh.p, xbar.p, d_crec.p, tau, w, rho);
-        } else if (e0) {
-            LAUNCH_GB_EV(grp_cols, k_pdhg_x, true, n, stream, e0, e1, n, AT, yh.p, xh.p, x0h.p, xth.p, xbar.p, ch.p, lh.p, uh.p, tau, w, rho);
-        } else {
-            LAUNCH_GB(grp_cols, k_pdhg_x, true, n, stream, n, AT, yh.p, xh.p, x0h.p, xth.p, xbar.p, ch.p, lh.p, uh.p, tau, w, rho);
-        }
+    if (update && tiled_on && M > 0) {
+        launch_tiled(tAT, n, M, yh.p, e0);
+        launch_ev(k_x_epilogue, grid_n(n), kBlock, 0, stream, nullptr, e1, n, tAT.pcnt.p, tpart.p, xh.p, x0h.p, xbar.p, ch.p, lh.p, uh.p, tau, w, rho);
+    } else if (update && packed_on) {
+        with_value<2, 4, 1>(packed_trips, [&](auto t) {
+            with_group(grp_cols, [&](auto g) {
+                constexpr int G = g(), T = t();
+                launch_ev(k_pdhg_x_packed<G, T>, group_grid(n, G, T), kBlock, 0, stream, e0, e1, n, d_cbl.p, AT.idx, AT.val, yh.p, xh.p, xbar.p, d_crec.p, tau, w, rho);
+            });
+        });
     } else {
-        LAUNCH_GB(grp_cols, k_pdhg_x, false, n, stream, n, AT, yh.p, xh.p, x0h.p, xth.p, (double*)nullptr, ch.p, lh.p, uh.p, tau, w, rho);
+        // plain CSC; without update (the check) xbar is not written and the launch is never timed
+        with_bool(update, [&](auto u) {
+            constexpr bool U = u();
+            with_group(grp_cols, [&](auto g) {
+                launch_timed(k_pdhg_x<g(), U>, group_grid(n, g()), kBlock, 0, stream, U ? e0 : nullptr, U ? e1 : nullptr, n, AT, yh.p, xh.p, x0h.p, xth.p,
+                             U ? xbar.p : nullptr, ch.p, lh.p, uh.p, tau, w, rho);
+            });
+        });
     }
+}
+
+// One plain (update) iteration: the x-step, then the y-step.  profile: each step's kernels carry their own start / stop events
+// (bytes moved per step: DESIGN.md section 4).
+void Engine::pdhg_iteration(const SpMat& A, const SpMat& AT, double tau, double sigma, double w, double rho) {
+    if (!prm.profile) {
+        launch_x(AT, tau, w, rho, true, nullptr, nullptr);
+        launch_y(A, sigma, w, rho, nullptr, nullptr);
+        return;
+    }
+    const int64_t n = n_lp, m = M;
+    const size_t e0 = ev_get(), e1 = ev_get(), e2 = ev_get(), e3 = ev_get();
+    launch_x(AT, tau, w, rho, true, ev_pool[e0], ev_pool[e1]);
+    launch_y(A, sigma, w, rho, ev_pool[e2], ev_pool[e3]);
+    ev_recs.push_back({0, e0, e1, (double)NNZ * 12 + 8.0 * (n + 1) + 8.0 * 7 * n + 8.0 * m});
+    if (m > 0) ev_recs.push_back({1, e2, e3, (double)NNZ * 12 + 8.0 * (m + 1) + 8.0 * 5 * m + 8.0 * n});
 }
 
 // Check iteration: the PDHG step without update (xt, yt stored) and the KKT / fixed-point sums.  The row side rides on the
@@ -358,7 +374,7 @@ void Engine::launch_x(const SpMat& AT, double tau, double w, double rho, bool up
 bool Engine::launch_check(const SpMat& A, const SpMat& AT, double tau, double sigma, double w_next, double rho) {
     const int64_t n = n_lp, m = M;
     const int64_t thr = n_long > 0 ? kLongRow : (int64_t)1 << 62;
-    const int64_t brow = ceil_div(std::max<int64_t>(m, 1) * grp_rows, kBlock), bcol = ceil_div(n * grp_cols, kBlock);
+    const int64_t brow = group_grid(std::max<int64_t>(m, 1), grp_rows), bcol = group_grid(n, grp_cols);
     chk_part.resize((size_t)(brow + n_long + bcol) * kChkQ, stream);
     double* prow = chk_part.p;
     double* pcol = chk_part.p + (size_t)(brow + n_long) * kChkQ;
@@ -367,30 +383,30 @@ bool Engine::launch_check(const SpMat& A, const SpMat& AT, double tau, double si
         // the four SpMV passes of a check through the tiled copy (kernels.hpp "check iteration on the tiled copy"); row-sharded:
         // the two column-side vectors are this rank's partials and are summed over the ranks -- the same sequence of
         // collectives as the CSR form below, so ranks may differ in which form they run
-        const int64_t brow_t = ceil_div(m, (int64_t)kBlock), bcol_t = ceil_div(n, (int64_t)kBlock);      // <= brow, bcol
+        const int64_t brow_t = grid_n(m), bcol_t = grid_n(n);      // <= brow, bcol
         launch_tiled(tAT, n, m, yh.p, nullptr);
         if (row_sharded()) {
-            LAUNCH_1(k_tile_vec, n, stream, n, tAT.pcnt.p, tpart.p, pv.p);
+            launch_n(k_tile_vec, n, stream, n, tAT.pcnt.p, tpart.p, pv.p);
             allreduce(pv.p, (size_t)n, 0);
-            LAUNCH_1(k_x_prox<false>, n, stream, n, pv.p, xh.p, x0h.p, xth.p, xbar.p, ch.p, lh.p, uh.p, tau, 0.0, 1.0);
+            launch_n(k_x_prox<false>, n, stream, n, pv.p, xh.p, x0h.p, xth.p, xbar.p, ch.p, lh.p, uh.p, tau, 0.0, 1.0);
         } else {
-            LAUNCH_1(k_x_epilogue_chk, n, stream, n, tAT.pcnt.p, tpart.p, xh.p, xth.p, ch.p, lh.p, uh.p, tau);
+            launch_n(k_x_epilogue_chk, n, stream, n, tAT.pcnt.p, tpart.p, xh.p, xth.p, ch.p, lh.p, uh.p, tau);
         }
         launch_tiled(tA, m, n, xth.p, nullptr);
-        LAUNCH_1(k_tile_vec, m, stream, m, tA.pcnt.p, tpart.p, pw.p);
+        launch_n(k_tile_vec, m, stream, m, tA.pcnt.p, tpart.p, pw.p);
         launch_tiled(tA, m, n, xh.p, nullptr);
-        LAUNCH_1(k_y_epilogue_chk, m, stream, m, tA.pcnt.p, tpart.p, pw.p, (n_long > 0 ? A.ptr : (const int64_t*)nullptr), thr, yh.p, y0h.p,
-                 yth.p, loh.p, hih.p, dr.p, sigma, prow);
+        launch_n(k_y_epilogue_chk, m, stream, m, tA.pcnt.p, tpart.p, pw.p, (n_long > 0 ? A.ptr : (const int64_t*)nullptr), thr, yh.p, y0h.p, yth.p, loh.p,
+                 hih.p, dr.p, sigma, prow);
         if (n_long > 0)
-            hipLaunchKernelGGL((k_pdhg_y_long<true>), dim3((unsigned)n_long), dim3(kLongBlock), 0, stream, d_longrows.p, A, xth.p, xh.p,
-                               yh.p, y0h.p, yth.p, loh.p, hih.p, dr.p, sigma, 0.0, 1.0, prow + (size_t)brow_t * kChkQ);
+            launch(k_pdhg_y_long<true>, (unsigned)n_long, kLongBlock, 0, stream, d_longrows.p, A, xth.p, xh.p, yh.p, y0h.p, yth.p, loh.p, hih.p, dr.p, sigma,
+                   0.0, 1.0, prow + (size_t)brow_t * kChkQ);
         chk_nrow = (int)(brow_t + n_long);
         launch_tiled(tAT, n, m, yth.p, nullptr);
-        LAUNCH_1(k_tile_vec, n, stream, n, tAT.pcnt.p, tpart.p, pv.p);
+        launch_n(k_tile_vec, n, stream, n, tAT.pcnt.p, tpart.p, pv.p);
         if (row_sharded()) allreduce(pv.p, (size_t)n, 0);
-        LAUNCH_1(k_chk_cols_vec, n, stream, n, pv.p, xh.p, xth.p, x0h.p, ch.p, lh.p, uh.p, dc.p, pcol);
+        launch_n(k_chk_cols_vec, n, stream, n, pv.p, xh.p, xth.p, x0h.p, ch.p, lh.p, uh.p, dc.p, pcol);
         chk_ncol = (int)bcol_t;
-        hipLaunchKernelGGL(k_chk_final, dim3(2 * kChkQ), dim3(kRedBlocks), 0, stream, prow, chk_nrow, pcol, chk_ncol, chk_target());
+        launch(k_chk_final, 2 * kChkQ, kRedBlocks, 0, stream, prow, chk_nrow, pcol, chk_ncol, chk_target());
         if (row_sharded()) {                            // row sums: every rank's rows; column sums are identical already
             allreduce(chkout.p, 12, 0);
             allreduce(chkout.p + 12, 4, 1);
@@ -401,29 +417,35 @@ bool Engine::launch_check(const SpMat& A, const SpMat& AT, double tau, double si
     const bool spec = w_next >= 0.0 && m > 0 && !row_sharded() && n_long == 0 && n_longc == 0;
     if (spec) {
         xnext.resize((size_t)n, stream); ynext.resize((size_t)m, stream);
-        LAUNCH_GB(grp_cols, k_pdhg_x, false, n, stream, n, AT, yh.p, xh.p, x0h.p, xth.p, xnext.p, ch.p, lh.p, uh.p, tau, w_next, rho);
+        with_group(grp_cols, [&](auto g) {
+            launch(k_pdhg_x<g(), false>, group_grid(n, g()), kBlock, 0, stream, n, AT, yh.p, xh.p, x0h.p, xth.p, xnext.p, ch.p, lh.p, uh.p, tau, w_next, rho);
+        });
     } else {
         launch_x(AT, tau, 0.0, 1.0, false, nullptr, nullptr);
     }
     if (m > 0) {
-        LAUNCH_G(grp_rows, k_pdhg_y_chk, m, stream, m, A, xth.p, xh.p, yh.p, y0h.p, yth.p, loh.p, hih.p, dr.p, sigma, thr, prow,
-                 spec ? ynext.p : (double*)nullptr, w_next, rho);
+        with_group(grp_rows, [&](auto g) {
+            launch(k_pdhg_y_chk<g()>, group_grid(m, g()), kBlock, 0, stream, m, A, xth.p, xh.p, yh.p, y0h.p, yth.p, loh.p, hih.p, dr.p, sigma, thr, prow,
+                   spec ? ynext.p : (double*)nullptr, w_next, rho);
+        });
         if (n_long > 0)
-            hipLaunchKernelGGL((k_pdhg_y_long<true>), dim3((unsigned)n_long), dim3(kLongBlock), 0, stream, d_longrows.p, A, xth.p, xh.p,
-                               yh.p, y0h.p, yth.p, loh.p, hih.p, dr.p, sigma, 0.0, 1.0, prow + (size_t)brow * kChkQ);
+            launch(k_pdhg_y_long<true>, (unsigned)n_long, kLongBlock, 0, stream, d_longrows.p, A, xth.p, xh.p, yh.p, y0h.p, yth.p, loh.p, hih.p, dr.p, sigma,
+                   0.0, 1.0, prow + (size_t)brow * kChkQ);
     }
     chk_nrow = (m > 0) ? (int)(brow + n_long) : 0;
     if (row_sharded() || n_longc > 0) {
-        if (m == 0) LAUNCH_1(k_fill, n, stream, n, pv.p, 0.0);
+        if (m == 0) launch_n(k_fill, n, stream, n, pv.p, 0.0);
         spmv_cols(AT, yth.p, pv.p);
         allreduce(pv.p, (size_t)n, 0);
-        chk_ncol = ceil_div(n, kBlock);             // <= bcol: the column partials fit the same region
-        LAUNCH_1(k_chk_cols_vec, n, stream, n, pv.p, xh.p, xth.p, x0h.p, ch.p, lh.p, uh.p, dc.p, pcol);
+        chk_ncol = (int)grid_n(n);               // <= bcol: the column partials fit the same region
+        launch_n(k_chk_cols_vec, n, stream, n, pv.p, xh.p, xth.p, x0h.p, ch.p, lh.p, uh.p, dc.p, pcol);
     } else {
-        LAUNCH_G(grp_cols, k_chk_cols, n, stream, n, AT, xh.p, xth.p, x0h.p, yth.p, ch.p, lh.p, uh.p, dc.p, pcol);
+        with_group(grp_cols, [&](auto g) {
+            launch(k_chk_cols<g()>, group_grid(n, g()), kBlock, 0, stream, n, AT, xh.p, xth.p, x0h.p, yth.p, ch.p, lh.p, uh.p, dc.p, pcol);
+        });
         chk_ncol = (int)bcol;
     }
-    hipLaunchKernelGGL(k_chk_final, dim3(2 * kChkQ), dim3(kRedBlocks), 0, stream, prow, chk_nrow, pcol, chk_ncol, chk_target());   // (rows | columns) x quantity
+    launch(k_chk_final, 2 * kChkQ, kRedBlocks, 0, stream, prow, chk_nrow, pcol, chk_ncol, chk_target());   // (rows | columns) x quantity
     if (row_sharded()) {                            // row sums: every rank's rows; column sums are identical already
         allreduce(chkout.p, 12, 0);
         allreduce(chkout.p + 12, 4, 1);
@@ -528,7 +550,7 @@ bool Engine::lp_solve_dense(LpResult* R) {
     P.dense = ds_dense.p; P.W = ds_W.p; P.Wvalid = ds_valid.p; P.x = lp_x.p; P.y = lp_y.p; P.out = ds_out.p;
     P.max_pivots = 200 + 20 * n + (int)std::min<int64_t>(m, 100000);
     P.tol = 1e-9;
-    hipLaunchKernelGGL(k_dense_lp, dim3(1), dim3(256), 0, stream, P);
+    launch(k_dense_lp, 1, 256, 0, stream, P);
     check_launch();
     double out[4];
     KTN_HIP(hipMemcpyAsync(out, ds_out.p, sizeof(out), hipMemcpyDeviceToHost, stream));
@@ -564,7 +586,7 @@ bool Engine::big_bounds_hold() {
     if (!has_big_bound) return true;
     int32_t bad = 0;
     KTN_HIP(hipMemsetAsync(d_anynf.p + 3, 0, sizeof(int32_t), stream));
-    hipLaunchKernelGGL(k_big_bounds_check, dim3((unsigned)ceil_div(n_lp, 256)), dim3(256), 0, stream, (int)n_lp, lp_x.p, lp_l.p, lp_u.p, d_anynf.p + 3);
+    launch(k_big_bounds_check, (unsigned)ceil_div(n_lp, 256), 256, 0, stream, (int)n_lp, lp_x.p, lp_l.p, lp_u.p, d_anynf.p + 3);
     check_launch();
     KTN_HIP(hipMemcpyAsync(&bad, d_anynf.p + 3, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
     sync();
@@ -592,8 +614,8 @@ bool Engine::mid_true_duals(double* y_out) {
     md_y.resize(mm, stream);
     KTN_HIP(hipMemsetAsync(md_y.p, 0, mm * sizeof(double), stream));
     const unsigned g_n = (unsigned)ceil_div(P.n, 256);
-    hipLaunchKernelGGL(k_mid_lambda, dim3(g_n), dim3(256), 0, stream, P, 1);
-    hipLaunchKernelGGL(k_mid_true_duals, dim3(g_n), dim3(256), 0, stream, P, md_y.p);
+    launch(k_mid_lambda, g_n, 256, 0, stream, P, 1);
+    launch(k_mid_true_duals, g_n, 256, 0, stream, P, md_y.p);
     check_launch();
     if (y_out) md_y.download(y_out, (size_t)M, stream);      // (null: the caller reads md_y on the device)
     return true;
@@ -623,26 +645,26 @@ bool Engine::lp_solve_mid(LpResult* R) {
     P.max_pivots = 5000 + 200 * n + (int)std::min<int64_t>(20 * m, 4000000);
     const unsigned g_nn = (unsigned)ceil_div((int64_t)n * n, 256), g_n = (unsigned)ceil_div(n, 256);
     auto refine = [&]() {                               // x = B^-1 h_W + one step of iterative refinement; lambda = -B^-T c
-        hipLaunchKernelGGL(k_mid_resid, dim3(g_n), dim3(256), 0, stream, P, 0);
-        hipLaunchKernelGGL(k_mid_apply, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, stream, P, 0);
-        hipLaunchKernelGGL(k_mid_resid, dim3(g_n), dim3(256), 0, stream, P, 1);
-        hipLaunchKernelGGL(k_mid_apply, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, stream, P, 1);
-        hipLaunchKernelGGL(k_mid_resid, dim3(g_n), dim3(256), 0, stream, P, 1);
-        hipLaunchKernelGGL(k_mid_resid_norm, dim3(1), dim3(256), 0, stream, P, 1);
-        hipLaunchKernelGGL(k_mid_lambda, dim3(g_n), dim3(256), 0, stream, P, 0);
+        launch(k_mid_resid, g_n, 256, 0, stream, P, 0);
+        launch(k_mid_apply, (unsigned)ceil_div(n, 4), 256, 0, stream, P, 0);
+        launch(k_mid_resid, g_n, 256, 0, stream, P, 1);
+        launch(k_mid_apply, (unsigned)ceil_div(n, 4), 256, 0, stream, P, 1);
+        launch(k_mid_resid, g_n, 256, 0, stream, P, 1);
+        launch(k_mid_resid_norm, 1, 256, 0, stream, P, 1);
+        launch(k_mid_lambda, g_n, 256, 0, stream, P, 0);
     };
     // B^-1 afresh from the working set (mid_lp.hpp "refactorisation"), then x and lambda from their definitions
     auto refactor = [&]() {
         md_aug.resize((size_t)n * 2 * n, stream); md_prow.resize((size_t)2 * n, stream); md_fcol.resize((size_t)n, stream);
-        hipLaunchKernelGGL(k_mid_gj_build, dim3((unsigned)n), dim3(256), 0, stream, P, md_aug.p);
+        launch(k_mid_gj_build, (unsigned)n, 256, 0, stream, P, md_aug.p);
         const unsigned g_2n = (unsigned)ceil_div(2 * n, 256), g_aug = (unsigned)ceil_div((int64_t)n * 2 * n, 256);
         for (int col = 0; col < n; ++col) {
-            hipLaunchKernelGGL(k_mid_gj_pivot, dim3(1), dim3(256), 0, stream, P, (const double*)md_aug.p, col);
-            hipLaunchKernelGGL(k_mid_gj_swap, dim3(g_2n), dim3(256), 0, stream, P, md_aug.p, col, md_prow.p);
-            hipLaunchKernelGGL(k_mid_gj_col, dim3(g_n), dim3(256), 0, stream, P, (const double*)md_aug.p, col, md_fcol.p);
-            hipLaunchKernelGGL(k_mid_gj_elim, dim3(g_aug), dim3(256), 0, stream, P, md_aug.p, col, (const double*)md_prow.p, (const double*)md_fcol.p);
+            launch(k_mid_gj_pivot, 1, 256, 0, stream, P, (const double*)md_aug.p, col);
+            launch(k_mid_gj_swap, g_2n, 256, 0, stream, P, md_aug.p, col, md_prow.p);
+            launch(k_mid_gj_col, g_n, 256, 0, stream, P, (const double*)md_aug.p, col, md_fcol.p);
+            launch(k_mid_gj_elim, g_aug, 256, 0, stream, P, md_aug.p, col, (const double*)md_prow.p, (const double*)md_fcol.p);
         }
-        hipLaunchKernelGGL(k_mid_gj_store, dim3(g_nn), dim3(256), 0, stream, P, (const double*)md_aug.p);
+        launch(k_mid_gj_store, g_nn, 256, 0, stream, P, (const double*)md_aug.p);
         refine();
         md_since_refactor = 0;
         stats["mid_lp_refactors"] += 1.0;
@@ -652,11 +674,11 @@ bool Engine::lp_solve_mid(LpResult* R) {
     int total_pivots = 0, status = 4;
     for (int attempt = 0; attempt < 2; ++attempt) {
         if (!md_valid) {
-            hipLaunchKernelGGL(k_mid_init, dim3(g_nn), dim3(256), 0, stream, P);
+            launch(k_mid_init, g_nn, 256, 0, stream, P);
             stats["mid_lp_cold_starts"] += 1.0;
             md_since_refactor = 0;
         } else {
-            hipLaunchKernelGGL(k_mid_rearm, dim3(1), dim3(1), 0, stream, md_st.p);
+            launch(k_mid_rearm, 1, 1, 0, stream, md_st.p);
             if (md_since_refactor >= refactor_every) refactor();
         }
         int refined_at = -1, refinements = 0, pivots_seen = 0;
@@ -664,11 +686,11 @@ bool Engine::lp_solve_mid(LpResult* R) {
         status = 4;
         for (;;) {
             for (int b = 0; b < 8; ++b) {
-                hipLaunchKernelGGL(k_mid_price, dim3(kMidPriceBlocks), dim3(256), 0, stream, P);
-                hipLaunchKernelGGL(k_mid_select, dim3(1), dim3(256), 0, stream, P);
-                hipLaunchKernelGGL(k_mid_u, dim3(g_n), dim3(256), 0, stream, P);
-                hipLaunchKernelGGL(k_mid_ratio, dim3(1), dim3(256), 0, stream, P);
-                hipLaunchKernelGGL(k_mid_rank1, dim3(g_nn), dim3(256), 0, stream, P);
+                launch(k_mid_price, kMidPriceBlocks, 256, 0, stream, P);
+                launch(k_mid_select, 1, 256, 0, stream, P);
+                launch(k_mid_u, g_n, 256, 0, stream, P);
+                launch(k_mid_ratio, 1, 256, 0, stream, P);
+                launch(k_mid_rank1, g_nn, 256, 0, stream, P);
             }
             check_launch();
             KTN_HIP(hipMemcpyAsync(&hs, md_st.p, sizeof(hs), hipMemcpyDeviceToHost, stream));
@@ -705,7 +727,7 @@ bool Engine::lp_solve_mid(LpResult* R) {
     bool ok = false;
     if (status == 0) {
         KTN_HIP(hipMemsetAsync(lp_y.p, 0, (size_t)std::max<int64_t>(m, 1) * sizeof(double), stream));
-        hipLaunchKernelGGL(k_mid_final, dim3(1), dim3(256), 0, stream, P, lp_y.p);
+        launch(k_mid_final, 1, 256, 0, stream, P, lp_y.p);
         KTN_HIP(hipMemcpyAsync(lp_x.p, md_x.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
         KTN_HIP(hipMemcpyAsync(&hs, md_st.p, sizeof(hs), hipMemcpyDeviceToHost, stream));
         check_launch();
@@ -789,8 +811,8 @@ void Engine::lp_set_anchors(bool want_packed) {
     if (dev.packed_trips > 0) packed_trips = dev.packed_trips;
     if (packed_on) {
         d_crec.resize((size_t)n, stream); d_cbl.resize((size_t)n, stream); d_rrec.resize(mm, stream);
-        LAUNCH_1(k_pack_both, std::max(n, m), stream, n, c_ptr.p, ch.p, lh.p, uh.p, xh.p, x0h.p, d_crec.p, d_cbl.p,
-                 m, lp_rowptr.p, loh.p, hih.p, yh.p, y0h.p, d_rrec.p);
+        launch_n(k_pack_both, std::max(n, m), stream, n, c_ptr.p, ch.p, lh.p, uh.p, xh.p, x0h.p, d_crec.p, d_cbl.p, m, lp_rowptr.p, loh.p, hih.p, yh.p, y0h.p,
+                 d_rrec.p);
     } else {
         KTN_HIP(hipMemcpyAsync(x0h.p, xh.p, n * sizeof(double), hipMemcpyDeviceToDevice, stream));
         if (m > 0) KTN_HIP(hipMemcpyAsync(y0h.p, yh.p, m * sizeof(double), hipMemcpyDeviceToDevice, stream));
@@ -812,7 +834,7 @@ void Engine::lp_read_check(double* q) {
 // restart from the point of the last check: z <- T(z), z0 <- T(z), in the arrays and in the packed records
 void Engine::lp_restart() {
     const int64_t n = n_lp, m = M;
-    LAUNCH_1(k_restart_set, std::max(n, m), stream, n, m, xth.p, xh.p, x0h.p, yth.p, yh.p, y0h.p, packed_on ? d_crec.p : (ColRec*)nullptr,
+    launch_n(k_restart_set, std::max(n, m), stream, n, m, xth.p, xh.p, x0h.p, yth.p, yh.p, y0h.p, packed_on ? d_crec.p : (ColRec*)nullptr,
              packed_on ? d_rrec.p : (RowRec*)nullptr);
 }
 
@@ -823,7 +845,7 @@ void Engine::lp_advance(bool spec, int64_t k, double rho) {
         xh.swap(xnext); yh.swap(ynext);
     } else {
         const double w = (double)(k + 1) / (double)(k + 2);
-        LAUNCH_1(k_halpern2, std::max(n, m), stream, n, m, xh.p, xth.p, x0h.p, yh.p, yth.p, y0h.p, w, rho);
+        launch_n(k_halpern2, std::max(n, m), stream, n, m, xh.p, xth.p, x0h.p, yh.p, yth.p, y0h.p, w, rho);
     }
 }
 
@@ -850,12 +872,12 @@ LpResult Engine::lp_solve_core(double tol_p, double tol_g, int mode, bool identi
     const int64_t n = n_lp, m = M;
     lp_resize_iterates();
     const double sgn = (sense == KTN_MAX) ? -1.0 : 1.0;
-    LAUNCH_1(k_prep_both, std::max(n, m), stream,
+    launch_n(k_prep_both, std::max(n, m), stream,
              PrepCols{n, Wc(), lp_l.p, lp_u.p, dc.p, lp_x.p, (mode == 1 ? box.p : (const double*)nullptr), sgn, mode, ch.p, lh.p, uh.p, xh.p},
              PrepRows{m, Wlo(), Whi(), dr.p, lp_y.p, mode, loh.p, hih.p, yh.p});
     if (w_shift) {                                      // the epigraph variable of the start: s = t - a_ref'x - b_ref
         epi_dot(lp_x.p);
-        hipLaunchKernelGGL(k_epi_var, dim3(1), dim3(1), 0, stream, xh.p, (int32_t)n0, epi_scal.p, (const double*)dc.p, -1, have_omega ? 0 : 1, sgn, epi_newest.p);
+        launch(k_epi_var, 1, 1, 0, stream, xh.p, (int32_t)n0, epi_scal.p, (const double*)dc.p, -1, have_omega ? 0 : 1, sgn, epi_newest.p);
     }
     check_launch();
     lp_pick_groups();
@@ -889,17 +911,17 @@ LpResult Engine::lp_solve_core(double tol_p, double tol_g, int mode, bool identi
         // cold estimate plus the back-off safeguard is the better operating point.)
         double* nrm = (chk_pinned() ? h_chk_dev : chkout.p) + 2 * kChkQ + 1;
         auto dot_dev = [&](const double* a, double* out) {
-            hipLaunchKernelGGL(k_dot_partial, dim3(kRedBlocks), dim3(kBlock), 0, stream, n, a, a, partials.p);
-            hipLaunchKernelGGL(k_sum_final, dim3(1), dim3(kRedBlocks), 0, stream, partials.p, kRedBlocks, out);
+            launch(k_dot_partial, kRedBlocks, kBlock, 0, stream, n, a, a, partials.p);
+            launch(k_sum_final, 1, kRedBlocks, 0, stream, partials.p, kRedBlocks, out);
         };
         auto normalize_into = [&](const double* a, double* out) {        // out = a / ||a||: partial sums, then k_normalize_sum adds them up itself
-            hipLaunchKernelGGL(k_dot_partial, dim3(kRedBlocks), dim3(kBlock), 0, stream, n, a, a, partials.p);
-            hipLaunchKernelGGL(k_normalize_sum, dim3(ceil_div(n, (int64_t)kRedBlocks)), dim3(kRedBlocks), 0, stream, n, a, partials.p, out);
+            launch(k_dot_partial, kRedBlocks, kBlock, 0, stream, n, a, a, partials.p);
+            launch(k_normalize_sum, (unsigned)ceil_div(n, kRedBlocks), kRedBlocks, 0, stream, n, a, partials.p, out);
         };
         // the start vector -- hashed, normalised -- depends on n alone: made once per handle (and size), read by the first pass in place
         if (power_v0_n != n) {
             power_v.resize(n, stream); power_v0.resize(n, stream);
-            LAUNCH_1(k_hash_fill, n, stream, n, power_v.p);
+            launch_n(k_hash_fill, n, stream, n, power_v.p);
             normalize_into(power_v.p, power_v0.p);
             power_v0_n = n;
         }
@@ -911,10 +933,10 @@ LpResult Engine::lp_solve_core(double tol_p, double tol_g, int mode, bool identi
         for (int it = 0; it < iters; ++it) {
             const double* vin = (it == 0) ? power_v0.p : pv.p;
             if (n_long > 0) {
-                LAUNCH_G(grp_rows, k_spmv_skip, m, stream, m, A, vin, pw.p, kLongRow);
-                hipLaunchKernelGGL(k_spmv_long, dim3((unsigned)n_long), dim3(1024), 0, stream, d_longrows.p, A, vin, pw.p);
+                with_group(grp_rows, [&](auto g) { launch(k_spmv_skip<g()>, group_grid(m, g()), kBlock, 0, stream, m, A, vin, pw.p, kLongRow); });
+                launch(k_spmv_long, (unsigned)n_long, 1024, 0, stream, d_longrows.p, A, vin, pw.p);
             } else {
-                LAUNCH_G(grp_rows, k_spmv, m, stream, m, A, vin, pw.p);
+                with_group(grp_rows, [&](auto g) { launch(k_spmv<g()>, group_grid(m, g()), kBlock, 0, stream, m, A, vin, pw.p); });
             }
             const bool norm_now = (it % 4 == 3) || it >= iters - 2;
             if (norm_now) {
@@ -937,11 +959,11 @@ LpResult Engine::lp_solve_core(double tol_p, double tol_g, int mode, bool identi
     const bool pin_slots = chk_pinned();
     double* slots = (pin_slots ? h_chk_dev : chkout.p) + 2 * kChkQ;           // [1] power, [2] fro2, [3] nc2, [4] |lo|^2, [5] |hi|^2
     // slots 2..5 (||A^||_F^2, ||c^||^2, finite ||lo^||^2, ||hi^||^2) by one fused pair of launches
-    hipLaunchKernelGGL(k_setup_norms_partial, dim3(kRedBlocks), dim3(kBlock), 0, stream, NNZ, r_sval.p, n, ch.p, m, loh.p, hih.p, partials.p);
-    hipLaunchKernelGGL(k_sum_final_multi, dim3(4), dim3(kRedBlocks), 0, stream, partials.p, kRedBlocks, slots + 2);
+    launch(k_setup_norms_partial, kRedBlocks, kBlock, 0, stream, NNZ, r_sval.p, n, ch.p, m, loh.p, hih.p, partials.p);
+    launch(k_sum_final_multi, 4, kRedBlocks, 0, stream, partials.p, kRedBlocks, slots + 2);
     if (w_shift) {                                      // ||c|| of the STORED cost vector: the scale of the (unscaled) dual-residual tolerance
-        hipLaunchKernelGGL(k_dot_partial, dim3(kRedBlocks), dim3(kBlock), 0, stream, n, lp_c.p, lp_c.p, partials.p);
-        hipLaunchKernelGGL(k_sum_final, dim3(1), dim3(kRedBlocks), 0, stream, partials.p, kRedBlocks, slots + 6);
+        launch(k_dot_partial, kRedBlocks, kBlock, 0, stream, n, lp_c.p, lp_c.p, partials.p);
+        launch(k_sum_final, 1, kRedBlocks, 0, stream, partials.p, kRedBlocks, slots + 6);
     }
     // Initial primal weight of a solve that has none to inherit: ||c^|| / ||b^|| with each norm taken as sqrt(count) x geometric
     // mean of the magnitudes (KTN_OMEGA_ROBUST=0: the plain 2-norms).  A few columns whose only entries are ~1e-6 get column
@@ -952,9 +974,9 @@ LpResult Engine::lp_solve_core(double tol_p, double tol_g, int mode, bool identi
     const bool robust = omega_robust && mode == 0 && !have_omega && !row_sharded() && m > 0;
     if (robust) {                                       // log-magnitude statistics of c^ and of the finite row bounds: slots 8..11
         auto logstat = [&](int64_t cnt, const double* a, const double* b, int slot) {
-            hipLaunchKernelGGL(k_logabs_partial, dim3(kRedBlocks), dim3(kBlock), 0, stream, cnt, a, b, partials.p);
-            hipLaunchKernelGGL(k_sum_final, dim3(1), dim3(kRedBlocks), 0, stream, partials.p, kRedBlocks, slots + slot);
-            hipLaunchKernelGGL(k_sum_final, dim3(1), dim3(kRedBlocks), 0, stream, partials.p + kRedBlocks, kRedBlocks, slots + slot + 1);
+            launch(k_logabs_partial, kRedBlocks, kBlock, 0, stream, cnt, a, b, partials.p);
+            launch(k_sum_final, 1, kRedBlocks, 0, stream, partials.p, kRedBlocks, slots + slot);
+            launch(k_sum_final, 1, kRedBlocks, 0, stream, partials.p + kRedBlocks, kRedBlocks, slots + slot + 1);
         };
         logstat(n, ch.p, nullptr, 8);
         logstat(m, loh.p, hih.p, 10);
@@ -1037,8 +1059,6 @@ LpResult Engine::lp_solve_core(double tol_p, double tol_g, int mode, bool identi
     // split into SpMV + element-wise kernels)
     lp_set_anchors(true);
 
-    const double ky_bytes = (double)NNZ * 12 + 8.0 * (m + 1) + 8.0 * 5 * m + 8.0 * n;
-    const double kx_bytes = (double)NNZ * 12 + 8.0 * (n + 1) + 8.0 * 7 * n + 8.0 * m;
     int64_t k = 0, it = 0;
     const bool dbg_lp = dev.debug_lp;
     R.status = KTN_STATUS_USERLIMIT;
@@ -1073,16 +1093,7 @@ LpResult Engine::lp_solve_core(double tol_p, double tol_g, int mode, bool identi
             if (np <= 0) continue;
             for (int j = 0; j < np; ++j) {
                 const double w = (double)(k + j + 1) / (double)(k + j + 2);
-                if (prm.profile) {
-                    const size_t e0 = ev_get(), e1 = ev_get(), e2 = ev_get(), e3 = ev_get();
-                    launch_x(AT, tau, w, rho, true, ev_pool[e0], ev_pool[e1]);
-                    launch_y(A, sigma, w, rho, ev_pool[e2], ev_pool[e3]);
-                    ev_recs.push_back({0, e0, e1, kx_bytes});
-                    if (m > 0) ev_recs.push_back({1, e2, e3, ky_bytes});
-                } else {
-                    launch_x(AT, tau, w, rho, true, nullptr, nullptr);
-                    launch_y(A, sigma, w, rho, nullptr, nullptr);
-                }
+                pdhg_iteration(A, AT, tau, sigma, w, rho);
             }
             k += np; it += np;
             continue;
@@ -1131,12 +1142,11 @@ LpResult Engine::lp_solve_core(double tol_p, double tol_g, int mode, bool identi
             // PDHG is idling between near-parallel cuts of one NL row (k_consolidate): move the multiplier mass onto the
             // tightest cut at the current point and restart from there
             stats["lp_consolidations"] += 1.0;
-            LAUNCH_1(k_unscale, n, stream, n, xth.p, dc.p, pv.p);
+            launch_n(k_unscale, n, stream, n, xth.p, dc.p, pv.p);
             SpMat Au{lp_rowptr.p, lp_col.p, Wval()};
-            LAUNCH_G(grp_rows, k_spmv, m, stream, m, Au, pv.p, pw.p);
+            with_group(grp_rows, [&](auto g) { launch(k_spmv<g()>, group_grid(m, g()), kBlock, 0, stream, m, Au, pv.p, pw.p); });
             KTN_HIP(hipMemsetAsync(d_anynf.p + 1, 0, sizeof(int32_t), stream));
-            LAUNCH_1(k_consolidate, list_count(), stream, list_count(), list_heads(), d_cutprev.p, pw.p, Wlo(), Whi(), dr.p, tol_p, yth.p,
-                     d_anynf.p + 1);
+            launch_n(k_consolidate, list_count(), stream, list_count(), list_heads(), d_cutprev.p, pw.p, Wlo(), Whi(), dr.p, tol_p, yth.p, d_anynf.p + 1);
         }
         if (nx.action != PDHG_ADVANCE) {
             if (nx.action == PDHG_RESTART) {
@@ -1156,16 +1166,16 @@ LpResult Engine::lp_solve_core(double tol_p, double tol_g, int mode, bool identi
     R.iters = it;
     // un-scale the last PDHG point (xt, yt)
     if (mode == 0) {
-        LAUNCH_1(k_unscale2, std::max(n, m), stream, n, xth.p, dc.p, lp_x.p, m, yth.p, dr.p, lp_y.p);
+        launch_n(k_unscale2, std::max(n, m), stream, n, xth.p, dc.p, lp_x.p, m, yth.p, dr.p, lp_y.p);
         if (w_shift) {                                  // back to the epigraph variable of the stored LP: t = s + a_ref'x + b_ref
             epi_dot(lp_x.p);
-            hipLaunchKernelGGL(k_epi_var, dim3(1), dim3(1), 0, stream, lp_x.p, (int32_t)n0, epi_scal.p, (const double*)nullptr, 1, 0, sgn, epi_newest.p);
+            launch(k_epi_var, 1, 1, 0, stream, lp_x.p, (int32_t)n0, epi_scal.p, (const double*)nullptr, 1, 0, sgn, epi_newest.p);
         }
         omega = om;
         have_omega = true;
         objval = sgn * R.pobj + c0;
     } else {
-        LAUNCH_1(k_unscale, n, stream, n, xth.p, dc.p, d_ray.p);
+        launch_n(k_unscale, n, stream, n, xth.p, dc.p, d_ray.p);
     }
     check_launch();
     sync();
@@ -1189,8 +1199,8 @@ void Engine::pdhg_raw(const double* x0, const double* y0, double eta, double ome
     const double sgn = (sense == KTN_MAX) ? -1.0 : 1.0;
     KTN_HIP(hipMemcpyAsync(lp_x.p, x0, n * sizeof(double), hipMemcpyHostToDevice, stream));
     if (m > 0) KTN_HIP(hipMemcpyAsync(lp_y.p, y0, m * sizeof(double), hipMemcpyHostToDevice, stream));
-    LAUNCH_1(k_prep_cols, n, stream, n, lp_c.p, lp_l.p, lp_u.p, dc.p, lp_x.p, (double*)nullptr, sgn, 0, ch.p, lh.p, uh.p, xh.p);
-    LAUNCH_1(k_prep_rows, m, stream, m, lp_lo.p, lp_hi.p, dr.p, lp_y.p, 0, loh.p, hih.p, yh.p);
+    launch_n(k_prep_cols, n, stream, n, lp_c.p, lp_l.p, lp_u.p, dc.p, lp_x.p, (double*)nullptr, sgn, 0, ch.p, lh.p, uh.p, xh.p);
+    launch_n(k_prep_rows, m, stream, m, lp_lo.p, lp_hi.p, dr.p, lp_y.p, 0, loh.p, hih.p, yh.p);
     grp_rows = pick_group(m ? (double)NNZ / (double)m : 1.0);
     grp_cols = pick_group(n ? (double)NNZ / (double)n : 1.0);
     SpMat A{lp_rowptr.p, lp_col.p, r_sval.p};
@@ -1201,20 +1211,9 @@ void Engine::pdhg_raw(const double* x0, const double* y0, double eta, double ome
     find_long_rows();
     lp_choose_tiled(false);                              // (scaled_version = 0 above: the next solve never reads tiled_built)
     const double tau = eta / omega_, sigma = eta * omega_;
-    const double ky_bytes = (double)NNZ * 12 + 8.0 * (m + 1) + 8.0 * 5 * m + 8.0 * n;
-    const double kx_bytes = (double)NNZ * 12 + 8.0 * (n + 1) + 8.0 * 7 * n + 8.0 * m;
     for (int64_t k = 0; k < iters; ++k) {
         const double w = (double)(k + 1) / (double)(k + 2);
-        if (prm.profile) {
-            const size_t e0 = ev_get(), e1 = ev_get(), e2 = ev_get(), e3 = ev_get();
-            launch_x(AT, tau, w, 1.0, true, ev_pool[e0], ev_pool[e1]);
-            launch_y(A, sigma, w, 1.0, ev_pool[e2], ev_pool[e3]);
-            ev_recs.push_back({0, e0, e1, kx_bytes});
-            if (m > 0) ev_recs.push_back({1, e2, e3, ky_bytes});
-        } else {
-            launch_x(AT, tau, w, 1.0, true, nullptr, nullptr);
-            launch_y(A, sigma, w, 1.0, nullptr, nullptr);
-        }
+        pdhg_iteration(A, AT, tau, sigma, w, 1.0);
         if ((k & 255) == 255) { sync(); if (prm.profile) ev_flush(); }
     }
     sync();
@@ -1242,8 +1241,7 @@ void Engine::lp_script(const LpScriptIO& io) {
     auto prep = [&](const double* xs, const double* ys) {
         KTN_HIP(hipMemcpyAsync(lp_x.p, xs, n * sizeof(double), hipMemcpyHostToDevice, stream));
         if (m > 0) KTN_HIP(hipMemcpyAsync(lp_y.p, ys, m * sizeof(double), hipMemcpyHostToDevice, stream));
-        LAUNCH_1(k_prep_both, std::max(n, m), stream,
-                 PrepCols{n, Wc(), lp_l.p, lp_u.p, dc.p, lp_x.p, (const double*)nullptr, sgn, 0, ch.p, lh.p, uh.p, xh.p},
+        launch_n(k_prep_both, std::max(n, m), stream, PrepCols{n, Wc(), lp_l.p, lp_u.p, dc.p, lp_x.p, (const double*)nullptr, sgn, 0, ch.p, lh.p, uh.p, xh.p},
                  PrepRows{m, Wlo(), Whi(), dr.p, lp_y.p, 0, loh.p, hih.p, yh.p});
     };
     lp_pick_groups();
@@ -1328,15 +1326,15 @@ void Engine::lp_scaling(double* dr_out, double* dc_out, double* drr_out, double*
 // "status == :Unbounded" + getunboundedray: solve the recession-cone LP (oracle/lp.py).
 bool Engine::recession_ray() {
     box.resize((size_t)n_lp, stream);
-    LAUNCH_1(k_fill, n_lp, stream, n_lp, box.p, 1.0);
+    launch_n(k_fill, n_lp, stream, n_lp, box.p, 1.0);
     if (!obj_linear) {
         KTN_HIP(hipMemsetAsync(d_scal.p + 1, 0, sizeof(double), stream));
-        LAUNCH_1(k_aux_box, M, stream, M, lp_rowptr.p, lp_col.p, lp_val.p, (int32_t)n0, d_scal.p + 1);
+        launch_n(k_aux_box, M, stream, M, lp_rowptr.p, lp_col.p, lp_val.p, (int32_t)n0, d_scal.p + 1);
         double w = 0.0;
         KTN_HIP(hipMemcpyAsync(&w, d_scal.p + 1, 8, hipMemcpyDeviceToHost, stream));
         sync();
         allreduce_host(&w, 1, 1);
-        LAUNCH_1(k_fill, 1, stream, (int64_t)1, box.p + n0, 1.0 + w);
+        launch_n(k_fill, 1, stream, (int64_t)1, box.p + n0, 1.0 + w);
     }
     // Small models (the reference's own tests: a handful of free variables): the recession LP by the exact kernel.  It is a
     // degenerate LP with tolerances of 1e-9 -- the first-order method can need more than its iteration limit for six rows and
@@ -1362,13 +1360,13 @@ bool Engine::recession_ray_dense(bool* unbounded) {
     DBuf<double> ones, rl, ru, rc, rx, rlo, rhi, ry, out;
     DBuf<int32_t> W, Wv;
     ones.resize(std::max<size_t>(mm, (size_t)n), stream);
-    LAUNCH_1(k_fill, (int64_t)ones.n, stream, (int64_t)ones.n, ones.p, 1.0);
+    launch_n(k_fill, (int64_t)ones.n, stream, (int64_t)ones.n, ones.p, 1.0);
     rl.resize(n, stream); ru.resize(n, stream); rc.resize(n, stream); rx.resize(n, stream);
     rlo.resize(mm, stream); rhi.resize(mm, stream); ry.resize(mm, stream); out.resize(4, stream);
     W.resize(n, stream); Wv.resize(1, stream); Wv.zero(stream);
     lp_x.resize((size_t)n, stream);
-    LAUNCH_1(k_prep_cols, n, stream, (int64_t)n, lp_c.p, lp_l.p, lp_u.p, ones.p, lp_x.p, box.p, 1.0, 1, rc.p, rl.p, ru.p, rx.p);
-    LAUNCH_1(k_prep_rows, m, stream, m, lp_lo.p, lp_hi.p, ones.p, ones.p, 1, rlo.p, rhi.p, ry.p);
+    launch_n(k_prep_cols, n, stream, (int64_t)n, lp_c.p, lp_l.p, lp_u.p, ones.p, lp_x.p, box.p, 1.0, 1, rc.p, rl.p, ru.p, rx.p);
+    launch_n(k_prep_rows, m, stream, m, lp_lo.p, lp_hi.p, ones.p, ones.p, 1, rlo.p, rhi.p, ry.p);
     ds_dense.resize(mm * (size_t)n, stream);
     d_ray.resize((size_t)n, stream);
     DenseLpIO P;
@@ -1377,7 +1375,7 @@ bool Engine::recession_ray_dense(bool* unbounded) {
     P.dense = ds_dense.p; P.W = W.p; P.Wvalid = Wv.p; P.x = d_ray.p; P.y = ry.p; P.out = out.p;
     P.max_pivots = 200 + 20 * n + (int)std::min<int64_t>(m, 100000);
     P.tol = 1e-9;
-    hipLaunchKernelGGL(k_dense_lp, dim3(1), dim3(256), 0, stream, P);
+    launch(k_dense_lp, 1, 256, 0, stream, P);
     check_launch();
     double o[4];
     KTN_HIP(hipMemcpyAsync(o, out.p, sizeof(o), hipMemcpyDeviceToHost, stream));

@@ -14,12 +14,12 @@ LpRows Engine::lp_view() {
 
 void Engine::append_link(int64_t nrows, const int64_t* nl_id_host) {       // rows [M, M + nrows) just appended from the host
     d_nlid.upload(nl_id_host, (size_t)nrows, stream);
-    LAUNCH_1(k_append_link, nrows, stream, nrows, M, d_nlid.p, nl_total, d_glast.p, d_cutprev.p, lp_y.p, (int)prm.lp_dual_inherit);
+    launch_n(k_append_link, nrows, stream, nrows, M, d_nlid.p, nl_total, d_glast.p, d_cutprev.p, lp_y.p, (int)prm.lp_dual_inherit);
     check_launch();
 }
 
 void Engine::append_link_dev(int64_t nrows) {                              // the same with the ids already in d_nlid (device-resident exchange)
-    LAUNCH_1(k_append_link, nrows, stream, nrows, M, d_nlid.p, nl_total, d_glast.p, d_cutprev.p, lp_y.p, (int)prm.lp_dual_inherit);
+    launch_n(k_append_link, nrows, stream, nrows, M, d_nlid.p, nl_total, d_glast.p, d_cutprev.p, lp_y.p, (int)prm.lp_dual_inherit);
     check_launch();
 }
 
@@ -28,22 +28,21 @@ void Engine::append_link_dev(int64_t nrows) {                              // th
 void Engine::clip_lists(int64_t nrows) {
     if (nrows >= M) return;
     if (glists) {
-        LAUNCH_1(k_list_clip, nl_total, stream, nl_total, nrows, M, d_glast.p, d_cutprev.p);
+        launch_n(k_list_clip, nl_total, stream, nl_total, nrows, M, d_glast.p, d_cutprev.p);
     } else if (lists_ok() && m_nl > 0 && d_lastcut.n >= (size_t)m_nl) {
-        LAUNCH_1(k_list_clip, m_nl, stream, m_nl, nrows, M, d_lastcut.p, d_cutprev.p);
+        launch_n(k_list_clip, m_nl, stream, m_nl, nrows, M, d_lastcut.p, d_cutprev.p);
     }
     check_launch();
 }
 
 void Engine::pack_rows_launch(int64_t nr, int64_t nz, int64_t first_row, int64_t base, bool ids, int64_t id_offset, double* dev_out) {
-    LAUNCH_1(k_pack_rows, std::max(nr, nz), stream, nr, nz, lp_rowptr.p + first_row, lp_col.p + base, lp_val.p + base,
-             lp_lo.p + first_row, lp_hi.p + first_row, ids ? (const int32_t*)d_violslots.p : (const int32_t*)nullptr,
-             id_offset, dev_out);
+    launch_n(k_pack_rows, std::max(nr, nz), stream, nr, nz, lp_rowptr.p + first_row, lp_col.p + base, lp_val.p + base, lp_lo.p + first_row, lp_hi.p + first_row,
+             ids ? (const int32_t*)d_violslots.p : (const int32_t*)nullptr, id_offset, dev_out);
     check_launch();
 }
 void Engine::unpack_rows_launch(int64_t nrows, int64_t nnz, const double* dev_in) {
-    LAUNCH_1(k_unpack_rows, std::max(nrows, nnz), stream, nrows, nnz, dev_in, NNZ, n_lp, lp_rowptr.p + M + 1, lp_col.p + NNZ,
-             lp_val.p + NNZ, lp_lo.p + M, lp_hi.p + M, d_nlid.p, d_anynf.p + 1);
+    launch_n(k_unpack_rows, std::max(nrows, nnz), stream, nrows, nnz, dev_in, NNZ, n_lp, lp_rowptr.p + M + 1, lp_col.p + NNZ, lp_val.p + NNZ, lp_lo.p + M,
+             lp_hi.p + M, d_nlid.p, d_anynf.p + 1);
     check_launch();
 }
 
@@ -91,8 +90,9 @@ void Engine::rebuild_csc() {
         if (NNZ > 0) {
             k_in.resize((size_t)NNZ, stream); k_out.resize((size_t)NNZ, stream);
             p_in.resize((size_t)NNZ, stream); p_out.resize((size_t)NNZ, stream);
-            LAUNCH_G(pick_group((double)NNZ / (double)std::max<int64_t>(M, 1)), k_csc_keys, M, stream, M, lp_rowptr.p, lp_col.p, k_in.p,
-                     p_in.p, c_cnt.p);
+            with_group(pick_group((double)NNZ / (double)std::max<int64_t>(M, 1)), [&](auto g) {
+                launch(k_csc_keys<g()>, group_grid(M, g()), kBlock, 0, stream, M, lp_rowptr.p, lp_col.p, k_in.p, p_in.p, c_cnt.p);
+            });
             check_launch();
         }
         exclusive_scan(c_cnt.p, c_ptr.p, (size_t)n_lp + 1);
@@ -104,12 +104,12 @@ void Engine::rebuild_csc() {
             // keys are (col << 32 | row) in CSR order, i.e. already ascending in row: a STABLE sort on the column bits alone
             // gives (col, row) order in 3 radix passes instead of 7
             KTN_HIP(sort_pairs_u64_u32(d_sorttmp.p, need, k_in.p, k_out.p, p_in.p, p_out.p, (size_t)NNZ, 32, 32 + bits, stream));
-            LAUNCH_1(k_csc_rows_perm, NNZ, stream, NNZ, k_out.p, p_out.p, c_row.p, c_perm.p);
+            launch_n(k_csc_rows_perm, NNZ, stream, NNZ, k_out.p, p_out.p, c_row.p, c_perm.p);
             check_launch();
         }
         stats["lp_csc_sorts"] += 1.0;
     }
-    LAUNCH_1(k_csc_vals, NNZ, stream, NNZ, c_perm.p, Wval(), c_val.p);
+    launch_n(k_csc_vals, NNZ, stream, NNZ, c_perm.p, Wval(), c_val.p);
     check_launch();
     csc_epoch = lp_epoch; csc_M = M; csc_NNZ = NNZ;
     lp_dirty = false;
@@ -126,7 +126,7 @@ void Engine::find_long_cols() {
     if (M <= kLongRow || n_blocks > 0) { col_len_max = std::min<int64_t>(M, kLongRow); col_scan_rows = M; return; }
     d_longcols.resize((size_t)n_lp, stream);
     KTN_HIP(hipMemsetAsync(d_anynf.p + 1, 0, 2 * sizeof(int32_t), stream));
-    LAUNCH_1(k_find_long_max, n_lp, stream, n_lp, c_ptr.p, kLongRow, d_longcols.p, d_anynf.p + 1);
+    launch_n(k_find_long_max, n_lp, stream, n_lp, c_ptr.p, kLongRow, d_longcols.p, d_anynf.p + 1);
     int32_t r[2] = {0, 0};
     KTN_HIP(hipMemcpyAsync(r, d_anynf.p + 1, 8, hipMemcpyDeviceToHost, stream));
     sync();
@@ -152,17 +152,21 @@ void Engine::csc_merge_appended() {
     c_off.resize((size_t)n + 1, stream);
     c_cnt.resize((size_t)n + 1, stream);
     c_cnt.zero(stream);
-    LAUNCH_1(k_cscm_count, nnz_new, stream, csc_NNZ, NNZ, lp_col.p, c_cnt.p);
+    launch_n(k_cscm_count, nnz_new, stream, csc_NNZ, NNZ, lp_col.p, c_cnt.p);
     exclusive_scan(c_cnt.p, c_off.p, (size_t)n + 1);
     c_ptr2.resize((size_t)n + 1, stream);
     c_row2.resize((size_t)NNZ + 1, stream);
     c_perm2.resize((size_t)NNZ + 1, stream);
     const int gc = pick_group((double)csc_NNZ / (double)std::max<int64_t>(n, 1));
-    LAUNCH_G(gc, k_cscm_move, n + 1, stream, n, c_ptr.p, c_off.p, c_row.p, c_perm.p, c_ptr2.p, c_row2.p, c_perm2.p);
+    with_group(gc, [&](auto g) {
+        launch(k_cscm_move<g()>, group_grid(n + 1, g()), kBlock, 0, stream, n, c_ptr.p, c_off.p, c_row.p, c_perm.p, c_ptr2.p, c_row2.p, c_perm2.p);
+    });
     c_cnt.zero(stream);
-    LAUNCH_G(pick_group((double)nnz_new / (double)std::max<int64_t>(M - csc_M, 1)), k_cscm_place, M - csc_M, stream, csc_M, M, lp_rowptr.p, lp_col.p, c_ptr.p,
-             c_off.p, c_cnt.p, c_row2.p, c_perm2.p);
-    LAUNCH_1(k_cscm_order, n, stream, n, c_ptr.p, c_off.p, c_row2.p, c_perm2.p);
+    with_group(pick_group((double)nnz_new / (double)std::max<int64_t>(M - csc_M, 1)), [&](auto g) {
+        launch(k_cscm_place<g()>, group_grid(M - csc_M, g()), kBlock, 0, stream, csc_M, M, lp_rowptr.p, lp_col.p, c_ptr.p, c_off.p, c_cnt.p, c_row2.p,
+               c_perm2.p);
+    });
+    launch_n(k_cscm_order, n, stream, n, c_ptr.p, c_off.p, c_row2.p, c_perm2.p);
     check_launch();
     c_ptr.swap(c_ptr2); c_row.swap(c_row2); c_perm.swap(c_perm2);
 }
@@ -189,21 +193,20 @@ void Engine::build_working() {
     }
     epi_ref.zero(stream); epi_scal.zero(stream); epi_newest.zero(stream);
     const int64_t rows = M - M_lin;
-    LAUNCH_1(k_epi_newest, rows, stream, M_lin, M, lp_rowptr.p, lp_col.p, tcol, epi_newest.p);
+    launch_n(k_epi_newest, rows, stream, M_lin, M, lp_rowptr.p, lp_col.p, tcol, epi_newest.p);
     if (rows > 0) {
-        hipLaunchKernelGGL(k_epi_setref, dim3(64), dim3(kBlock), 0, stream, epi_newest.p, lp_rowptr.p, lp_col.p, lp_val.p, lp_lo.p, lp_hi.p,
-                           tcol, epi_ref.p, epi_scal.p);
-        hipLaunchKernelGGL(k_epi_shift, dim3((unsigned)(rows * kEpiChunks)), dim3(kBlock), 0, stream, M_lin, M, lp_rowptr.p, lp_col.p,
-                           lp_val.p, lp_lo.p, lp_hi.p, tcol, epi_ref.p, epi_scal.p, wval.p, wlo.p, whi.p);
+        launch(k_epi_setref, 64, kBlock, 0, stream, epi_newest.p, lp_rowptr.p, lp_col.p, lp_val.p, lp_lo.p, lp_hi.p, tcol, epi_ref.p, epi_scal.p);
+        launch(k_epi_shift, (unsigned)(rows * kEpiChunks), kBlock, 0, stream, M_lin, M, lp_rowptr.p, lp_col.p, lp_val.p, lp_lo.p, lp_hi.p, tcol, epi_ref.p,
+               epi_scal.p, wval.p, wlo.p, whi.p);
     }
-    LAUNCH_1(k_epi_cost, n_lp, stream, n_lp, lp_c.p, tcol, epi_ref.p, wc.p);
+    launch_n(k_epi_cost, n_lp, stream, n_lp, lp_c.p, tcol, epi_ref.p, wc.p);
     check_launch();
     stats["lp_epi_shifts"] += 1.0;
 }
 
 void Engine::epi_dot(const double* x) {             // epi_scal[1] = a_ref'x  (a_ref is zero at the epigraph variable)
-    hipLaunchKernelGGL(k_dot_partial, dim3(kRedBlocks), dim3(kBlock), 0, stream, n_lp, epi_ref.p, x, partials.p);
-    hipLaunchKernelGGL(k_sum_final, dim3(1), dim3(kRedBlocks), 0, stream, partials.p, kRedBlocks, epi_scal.p + 1);
+    launch(k_dot_partial, kRedBlocks, kBlock, 0, stream, n_lp, epi_ref.p, x, partials.p);
+    launch(k_sum_final, 1, kRedBlocks, 0, stream, partials.p, kRedBlocks, epi_scal.p + 1);
 }
 
 // Cut-pool management after an LP solve (k_purge_mark / k_purge_copy / k_purge_relink).
@@ -213,13 +216,17 @@ void Engine::purge_cuts() {
     d_keep.resize((size_t)m, stream); d_keepnnz.resize((size_t)m, stream);
     d_newidx.resize((size_t)m, stream); d_newptr.resize((size_t)m, stream);
     const int gp = pick_group((double)NNZ / (double)std::max<int64_t>(m, 1));      // lanes per row of the pool kernels
-    LAUNCH_G(gp, k_purge_mark, m, stream, M_base, m, lp_rowptr.p, lp_col.p, lp_val.p, lp_x.p, lp_lo.p, lp_hi.p, lp_y.p, d_age.p,
-             prm.purge_margin, (int)prm.purge_age, d_keep.p, d_keepnnz.p);
+    with_group(gp, [&](auto g) {
+        launch(k_purge_mark<g()>, group_grid(m, g()), kBlock, 0, stream, M_base, m, lp_rowptr.p, lp_col.p, lp_val.p, lp_x.p, lp_lo.p, lp_hi.p, lp_y.p, d_age.p,
+               prm.purge_margin, (int)prm.purge_age, d_keep.p, d_keepnnz.p);
+    });
     bool deduped = false;
     if (prm.dedupe_eps > 0.0 && lists_ok() && list_count() > 0) {
         KTN_HIP(hipMemsetAsync(d_anynf.p + 1, 0, sizeof(int32_t), stream));
-        LAUNCH_G(gp, k_dedupe_mark, list_count(), stream, list_count(), list_heads(), d_cutprev.p, lp_rowptr.p, lp_val.p, lp_lo.p, lp_hi.p, lp_y.p,
-                 prm.dedupe_eps, d_keep.p, d_keepnnz.p, d_anynf.p + 1);
+        with_group(gp, [&](auto g) {
+            launch(k_dedupe_mark<g()>, group_grid(list_count(), g()), kBlock, 0, stream, list_count(), list_heads(), d_cutprev.p, lp_rowptr.p, lp_val.p,
+                   lp_lo.p, lp_hi.p, lp_y.p, prm.dedupe_eps, d_keep.p, d_keepnnz.p, d_anynf.p + 1);
+        });
         deduped = true;
     }
     check_launch();
@@ -229,9 +236,8 @@ void Engine::purge_cuts() {
     int32_t nd = 0;
     if (h_chk_dev) {                                   // the four scan tails and the dedupe count in one round trip
         double* ht = h_chk + 2 * kChkQ + 8;
-        hipLaunchKernelGGL(k_host_tail, dim3(1), dim3(1), 0, stream, h_chk_dev + 2 * kChkQ + 8, d_keep.p + (m - 1), d_newidx.p + (m - 1),
-                           d_keepnnz.p + (m - 1), d_newptr.p + (m - 1), (const double*)nullptr,
-                           deduped ? (const int32_t*)(d_anynf.p + 1) : (const int32_t*)nullptr, (const int32_t*)nullptr);
+        launch(k_host_tail, 1, 1, 0, stream, h_chk_dev + 2 * kChkQ + 8, d_keep.p + (m - 1), d_newidx.p + (m - 1), d_keepnnz.p + (m - 1), d_newptr.p + (m - 1),
+               (const double*)nullptr, deduped ? (const int32_t*)(d_anynf.p + 1) : (const int32_t*)nullptr, (const int32_t*)nullptr);
         sync();
         for (int k = 0; k < 4; ++k) t[k] = (int64_t)ht[k];
         nd = (int32_t)ht[5];
@@ -251,10 +257,10 @@ void Engine::purge_cuts() {
     lp_y2.resize((size_t)m_new, stream); d_age2.resize((size_t)m_new, stream); d_cutprev2.resize((size_t)m_new, stream);
     LpRows Old = lp_view();
     LpRows New{lp_rowptr2.p, lp_col2.p, lp_val2.p, lp_lo2.p, lp_hi2.p, lp_y2.p};
-    LAUNCH_G(gp, k_purge_copy, m, stream, m, d_keep.p, d_newidx.p, d_newptr.p, Old, d_age.p, New, d_age2.p);
+    with_group(gp, [&](auto g) { launch(k_purge_copy<g()>, group_grid(m, g()), kBlock, 0, stream, m, d_keep.p, d_newidx.p, d_newptr.p, Old, d_age.p, New, d_age2.p); });
     KTN_HIP(hipMemcpyAsync(lp_rowptr2.p + m_new, &nnz_new, 8, hipMemcpyHostToDevice, stream));
     if (lists_ok()) {
-        LAUNCH_1(k_purge_relink, list_count(), stream, list_count(), list_heads(), d_cutprev.p, d_keep.p, d_newidx.p, d_cutprev2.p);
+        launch_n(k_purge_relink, list_count(), stream, list_count(), list_heads(), d_cutprev.p, d_keep.p, d_newidx.p, d_cutprev2.p);
     } else {
         // rows appended from the host (multi-GPU exchange) are not threaded into the per-row cut lists, and the
         // lists are unused in that mode (no dual inheritance, no consolidation): void them
@@ -263,7 +269,7 @@ void Engine::purge_cuts() {
     }
     if (scal_rows == m && prm.lp_ruiz_warm > 0 && dr_r.n >= (size_t)m) {   // keep the row scaling of the surviving rows (warm start of the next solve)
         statr.resize((size_t)m, stream);
-        LAUNCH_1(k_compact_vec, m, stream, m, d_keep.p, d_newidx.p, dr_r.p, statr.p);
+        launch_n(k_compact_vec, m, stream, m, d_keep.p, d_newidx.p, dr_r.p, statr.p);
         dr_r.swap(statr);
         scal_rows = m_new;
     } else {
@@ -278,7 +284,7 @@ void Engine::purge_cuts() {
     if (ds_valid.n) ds_valid.zero(stream);          // row indices changed: the dense path's working set is void
     if (md_valid) {                                 // the mid-size solver's working rows move with the compaction (dropped one: cold start)
         md_lost.zero(stream);
-        hipLaunchKernelGGL(k_mid_remap, dim3((unsigned)ceil_div(n_lp, 256)), dim3(256), 0, stream, (int)n_lp, md_W.p, d_keep.p, d_newidx.p, md_lost.p);
+        launch(k_mid_remap, (unsigned)ceil_div(n_lp, 256), 256, 0, stream, (int)n_lp, md_W.p, d_keep.p, d_newidx.p, md_lost.p);
         int32_t lost = 0;
         KTN_HIP(hipMemcpyAsync(&lost, md_lost.p, 4, hipMemcpyDeviceToHost, stream));
         sync();
@@ -298,7 +304,7 @@ void Engine::find_long_rows() {
     if (M == 0 || max_row_len <= kLongRow) return;      // no row of this problem can be long: no scan, no round trip
     d_longrows.resize((size_t)M, stream);
     KTN_HIP(hipMemsetAsync(d_anynf.p + 1, 0, sizeof(int32_t), stream));
-    LAUNCH_1(k_find_long, M, stream, M, lp_rowptr.p, kLongRow, d_longrows.p, d_anynf.p + 1);
+    launch_n(k_find_long, M, stream, M, lp_rowptr.p, kLongRow, d_longrows.p, d_anynf.p + 1);
     int32_t cnt = 0;
     KTN_HIP(hipMemcpyAsync(&cnt, d_anynf.p + 1, 4, hipMemcpyDeviceToHost, stream));
     sync();

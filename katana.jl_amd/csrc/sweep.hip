@@ -85,7 +85,7 @@ void Engine::host_eval(const double* d_x) {
     d_jh.upload(h_jh.data(), (size_t)nnz_ext, stream);
     NlpDev P = nlp_view();
     SweepOut O = sweep_view();
-    LAUNCH_1(k_host_scatter, n_host, stream, P, d_hostrows.p, n_host, d_gh.p, d_jh.p, O);
+    launch_n(k_host_scatter, n_host, stream, P, d_hostrows.p, n_host, d_gh.p, d_jh.p, O);
     check_launch();
     stats["host_evals"] += 1.0;
 }
@@ -275,7 +275,7 @@ void Engine::launch_tape_classed(bool nl_only, const int32_t* mslot, const doubl
         if (nl_only && !q.nl) continue;
         TapeClassDev T = tape_class_view();
         T.wave_cls += q.wave0; T.wave_first += q.wave0;
-        hipLaunchKernelGGL(k_tape_classed, dim3((unsigned)q.nwaves), dim3(kTapeClassWave), q.lds, stream, P, T, mslot, d_x, f_tol, O);
+        launch(k_tape_classed, (unsigned)q.nwaves, kTapeClassWave, q.lds, stream, P, T, mslot, d_x, f_tol, O);
     }
 }
 
@@ -402,8 +402,8 @@ void Engine::launch_quad(bool nl_only, const double* d_x, double f_tol) {
     size_t ta = 0, tb = 0;
     const bool ev = prm.profile && nl_only;
     if (ev) { ta = ev_get(); tb = ev_get(); KTN_HIP(hipEventRecord(ev_pool[ta], stream)); }
-    LAUNCH_G(grp_quad, k_quad_jac, ne, stream, P, Q, L, d_x, O);
-    LAUNCH_G(grp_quad_rows, k_quad_stats, nr, stream, P, Q, L, d_x, f_tol, nl_only ? 1 : 0, O);
+    with_group(grp_quad, [&](auto g) { launch(k_quad_jac<g()>, group_grid(ne, g()), kBlock, 0, stream, P, Q, L, d_x, O); });
+    with_group(grp_quad_rows, [&](auto g) { launch(k_quad_stats<g()>, group_grid(nr, g()), kBlock, 0, stream, P, Q, L, d_x, f_tol, nl_only ? 1 : 0, O); });
     if (ev) { KTN_HIP(hipEventRecord(ev_pool[tb], stream)); ev_recs.push_back({5, ta, tb, quad_bytes}); }
 }
 
@@ -614,7 +614,7 @@ void Engine::loadproblem(int64_t num_var, int64_t num_constr, const double* l_va
         DBuf<double> t_p0, t_p1;
         t_ak.upload(akind, stream); t_p0.upload(p0, stream); t_p1.upload(p1, stream);
         d_colk.resize((size_t)ne, stream); d_pp.resize((size_t)ne, stream);
-        LAUNCH_1(k_pack_atoms, ne, stream, ne, d_col.p, t_ak.p, t_p0.p, t_p1.p, d_colk.p, d_pp.p);
+        launch_n(k_pack_atoms, ne, stream, ne, d_col.p, t_ak.p, t_p0.p, t_p1.p, d_colk.p, d_pp.p);
         check_launch();
         sync();                                         // the temporaries are freed on leaving the scope
     }
@@ -841,8 +841,8 @@ void Engine::loadproblem(int64_t num_var, int64_t num_constr, const double* l_va
         lp_lo.resize((size_t)n_lin + 1, stream); lp_hi.resize((size_t)n_lin + 1, stream);
         DBuf<int32_t> t_lr;
         t_lr.upload(lr, stream);
-        LAUNCH_1(k_lin_rows, n_lin, stream, n_lin, t_lr.p, d_rowptr.p, d_col.p, d_jac.p, d_g.p, d_lb.p, d_ub.p, lp_rowptr.p, lp_col.p,
-                 lp_val.p, lp_lo.p, lp_hi.p);
+        launch_n(k_lin_rows, n_lin, stream, n_lin, t_lr.p, d_rowptr.p, d_col.p, d_jac.p, d_g.p, d_lb.p, d_ub.p, lp_rowptr.p, lp_col.p, lp_val.p, lp_lo.p,
+                 lp_hi.p);
         check_launch();
         sync();
     }
@@ -1016,21 +1016,16 @@ void Engine::precompute_all(const double* d_x) {
     // many short rows: the R-rows-per-lane-group form of the sweep with the Jacobian store (same sums, same bits); the
     // selection is the sweep's, made once in loadproblem (pre_multirow)
     if (pre_multirow) {
-#define KTN_PRE_LAUNCH(G) hipLaunchKernelGGL((k_sep_sweep<G, 4, true>), dim3(ceil_div(ceil_div(m_ext, (int64_t)4) * G, kBlock)), dim3(kBlock), 0, stream, P, d_allrows.p, m_ext, d_x, 0.0, O)
-        switch (grp_sweep) {
-            case 8: KTN_PRE_LAUNCH(8); break;
-            case 16: KTN_PRE_LAUNCH(16); break;
-            case 32: KTN_PRE_LAUNCH(32); break;
-            default: KTN_PRE_LAUNCH(64); break;
-        }
-#undef KTN_PRE_LAUNCH
+        with_value<8, 16, 32, 64>(grp_sweep, [&](auto g) {            // (grp_sweep >= 8: loadproblem)
+            launch(k_sep_sweep<g(), 4, true>, group_grid(m_ext, g(), 4), kBlock, 0, stream, P, d_allrows.p, m_ext, d_x, 0.0, O);
+        });
     } else {
-        LAUNCH_G(grp_sweep, k_sep_eval, m_ext, stream, P, d_allrows.p, m_ext, d_x, 0.0, 1, 0, O);
+        with_group(grp_sweep, [&](auto g) { launch(k_sep_eval<g()>, group_grid(m_ext, g()), kBlock, 0, stream, P, d_allrows.p, m_ext, d_x, 0.0, 1, 0, O); });
     }
     if (n_longev > 0)
-        hipLaunchKernelGGL(k_sep_eval_long, dim3((unsigned)n_longev), dim3(1024), 0, stream, P, d_longev_rows.p, d_longev_slots.p, d_x, 0.0, 0, O);
+        launch(k_sep_eval_long, (unsigned)n_longev, 1024, 0, stream, P, d_longev_rows.p, d_longev_slots.p, d_x, 0.0, 0, O);
     launch_quad(false, d_x, 0.0);
-    LAUNCH_1(k_tape_eval, (int64_t)d_tapeint_all.n, stream, P, d_tapeint_all.p, (int64_t)d_tapeint_all.n, d_x, O);
+    launch_n(k_tape_eval, (int64_t)d_tapeint_all.n, stream, P, d_tapeint_all.p, (int64_t)d_tapeint_all.n, d_x, O);
     if (n_host > 0) host_eval(d_x);
     // cut constants / maxima of tape rows from the materialised Jacobian (flags unused here)
     KTN_HIP(hipMemsetAsync(d_scal.p, 0, sizeof(double), stream));
@@ -1038,8 +1033,7 @@ void Engine::precompute_all(const double* d_x) {
     // rows of the classed shapes: value, Jacobian and those constants / maxima in one pass (flags by row, as k_gj_stats' here)
     launch_tape_classed(false, d_tc_mrow.p, d_x, 0.0);
     if (tc_rows == 0 || d_tapeint_all.n > 0 || n_host > 0)
-        LAUNCH_1(k_gj_stats, m_ext, stream, P, d_allrows.p, m_ext, d_x, 0.0, (int)KTN_ROW_TAPE,
-                 (const uint8_t*)(tc_rows > 0 ? d_tc_rowflag.p : nullptr), O);
+        launch_n(k_gj_stats, m_ext, stream, P, d_allrows.p, m_ext, d_x, 0.0, (int)KTN_ROW_TAPE, (const uint8_t*)(tc_rows > 0 ? d_tc_rowflag.p : nullptr), O);
     check_launch();
 }
 
@@ -1061,7 +1055,7 @@ void Engine::kkt_build_mirror() {
     if (nnz_ext > 0) {
         kin.resize((size_t)nnz_ext, stream); kout.resize((size_t)nnz_ext, stream);
         pin.resize((size_t)nnz_ext, stream); pout.resize((size_t)nnz_ext, stream);
-        LAUNCH_1(k_kkt_keys, nnz_ext, stream, nnz_ext, m_ext, d_rowptr.p, d_col.p, kin.p, pin.p, cnt.p);
+        launch_n(k_kkt_keys, nnz_ext, stream, nnz_ext, m_ext, d_rowptr.p, d_col.p, kin.p, pin.p, cnt.p);
         check_launch();
     }
     exclusive_scan(cnt.p, d_kkt_cptr.p, (size_t)nc + 1);
@@ -1071,7 +1065,7 @@ void Engine::kkt_build_mirror() {
         const size_t need = sort_pairs_temp_bytes((size_t)nnz_ext);
         tmp.resize(need + 16, stream);
         KTN_HIP(sort_pairs_u64_u32(tmp.p, need, kin.p, kout.p, pin.p, pout.p, (size_t)nnz_ext, 32, 32 + bits, stream));
-        LAUNCH_1(k_csc_rows_perm, nnz_ext, stream, nnz_ext, kout.p, pout.p, d_kkt_crow.p, d_kkt_cperm.p);
+        launch_n(k_csc_rows_perm, nnz_ext, stream, nnz_ext, kout.p, pout.p, d_kkt_crow.p, d_kkt_cperm.p);
         check_launch();
     }
     sync();                                             // the temporaries are freed on leaving the scope
@@ -1099,12 +1093,12 @@ void Engine::kkt_compute() {
     if (kkt_arena) {
         S.y = e_y.p; S.a_last = e_last.p; S.a_prev = e_prev.p; S.arena = d_ar.p;
         S.blk_lin = d_blklin.p; S.blk_nl = d_blknl.p; S.nb = (int64_t)h_ar_row0.size();
-        LAUNCH_1(k_row_duals<true>, m0, stream, m0, d_kkt_rowmap.p, S, sgn, (int64_t)0, (int64_t)0, (int64_t)-1, (double*)nullptr, d_kkt_d.p);
+        launch_n(k_row_duals<true>, m0, stream, m0, d_kkt_rowmap.p, S, sgn, (int64_t)0, (int64_t)0, (int64_t)-1, (double*)nullptr, d_kkt_d.p);
     } else {
         // what ktn_lp_get_duals returns: the true-cost multipliers of an exact mid-size solve while they stand, lp_y otherwise
         S.y = (!dev.raw_duals && mid_true_duals(nullptr)) ? md_y.p : lp_y.p;
         S.heads = list_heads(); S.prev = d_cutprev.p; S.n_heads = list_count(); S.n_rows = M;
-        LAUNCH_1(k_row_duals<false>, std::max<int64_t>(m0, 1), stream, m0, d_kkt_rowmap.p, S, sgn, M_lin, M_base, epi ? m_nl - 1 : (int64_t)-1,
+        launch_n(k_row_duals<false>, std::max<int64_t>(m0, 1), stream, m0, d_kkt_rowmap.p, S, sgn, M_lin, M_base, epi ? m_nl - 1 : (int64_t)-1,
                  epi ? d_kkt_out.p + 2 : (double*)nullptr, d_kkt_d.p);
     }
     check_launch();
@@ -1125,13 +1119,16 @@ void Engine::kkt_compute() {
     // ---- 3. reduced costs
     int G = dev.kkt_group;
     if (!(G == 4 || G == 8 || G == 16 || G == 32 || G == 64)) G = pick_group((double)nnz_ext / (double)(n0 + 1));
-    LAUNCH_G(G, k_lagr_grad, n0, stream, n0, (int32_t)m0, d_kkt_cptr.p, d_kkt_crow.p, d_kkt_cperm.p, d_kkt_jac.p, d_kkt_d.p, d_kkt_z.p);
+    with_group(G, [&](auto g) {
+        launch(k_lagr_grad<g()>, group_grid(n0, g()), kBlock, 0, stream, n0, (int32_t)m0, d_kkt_cptr.p, d_kkt_crow.p, d_kkt_cperm.p, d_kkt_jac.p, d_kkt_d.p,
+               d_kkt_z.p);
+    });
     // ---- 4. the bound
-    LAUNCH_1(k_dual_terms, m0 + n0, stream, m0, n0, sgn, d_kkt_rowmap.p, kkt_n_lin, d_kkt_d.p, d_kkt_z.p, d_kkt_g.p, d_lb.p, d_ub.p, d_kkt_x.p,
-             lp_l.p, lp_u.p, d_kkt_t.p);
-    if (m0 + n0 > 0) hipLaunchKernelGGL(k_sum_partial, dim3(kRedBlocks), dim3(kBlock), 0, stream, m0 + n0, d_kkt_t.p, partials.p);
+    launch_n(k_dual_terms, m0 + n0, stream, m0, n0, sgn, d_kkt_rowmap.p, kkt_n_lin, d_kkt_d.p, d_kkt_z.p, d_kkt_g.p, d_lb.p, d_ub.p, d_kkt_x.p, lp_l.p, lp_u.p,
+             d_kkt_t.p);
+    if (m0 + n0 > 0) launch(k_sum_partial, kRedBlocks, kBlock, 0, stream, m0 + n0, d_kkt_t.p, partials.p);
     else KTN_HIP(hipMemsetAsync(partials.p, 0, kRedBlocks * sizeof(double), stream));
-    hipLaunchKernelGGL(k_dual_final, dim3(1), dim3(64), 0, stream, partials.p, (int)kRedBlocks, d_kkt_g.p, d_kkt_x.p, m0, n0, d_kkt_out.p);
+    launch(k_dual_final, 1, 64, 0, stream, partials.p, (int)kRedBlocks, d_kkt_g.p, d_kkt_x.p, m0, n0, d_kkt_out.p);
     check_launch();
     h_kkt_d.assign((size_t)m0, 0.0); h_kkt_z.assign((size_t)n0, 0.0);
     std::vector<double> out(d_kkt_out.n, 0.0);
@@ -1185,7 +1182,7 @@ void Engine::kkt_blocks() {
         kkt_seg_ok = true;
     }
     d_kkt_blk.resize((size_t)(2 * nb), stream);
-    hipLaunchKernelGGL(k_dual_bound, dim3((unsigned)nb), dim3(kBlock), 0, stream, d_kkt_seg.p, d_kkt_t.p, lp_c.p, d_kkt_x.p, m0, d_kkt_blk.p);
+    launch(k_dual_bound, (unsigned)nb, kBlock, 0, stream, d_kkt_seg.p, d_kkt_t.p, lp_c.p, d_kkt_x.p, m0, d_kkt_blk.p);
     check_launch();
     const std::vector<double> out = d_kkt_blk.to_host(stream);
     h_kkt_blk.assign((size_t)(2 * nb), 0.0);
@@ -1210,50 +1207,42 @@ void Engine::sweep(const double* d_x, double f_tol, int64_t* nviol_out, double* 
     SweepOut O = sweep_view();
     KTN_HIP(hipMemsetAsync(d_scal.p, 0, sizeof(double), stream));
     KTN_HIP(hipMemsetAsync(d_anynf.p, 0, sizeof(int32_t), stream));
+    hipEvent_t e0 = nullptr, e1 = nullptr;         // profile: the separable evaluation carries its own start / stop events
+    if (prm.profile) {
+        const size_t ea = ev_get(), eb = ev_get();
+        e0 = ev_pool[ea]; e1 = ev_pool[eb];
+        ev_recs.push_back({2, ea, eb, sweep_bytes});
+    }
     if (blk_on) {
         // long rows: column-blocked evaluation through LDS, then the block-order combination
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (prm.profile) {
-            const size_t ea = ev_get(), eb = ev_get();
-            e0 = ev_pool[ea]; e1 = ev_pool[eb];
-            ev_recs.push_back({2, ea, eb, sweep_bytes});
+        with_value<1, 2, 0>(blk_cfg, [&](auto c) {       // KTN_BLK_CFG: tuning variants kept for the next round's experiments
+            constexpr int G = c() == 0 ? 8 : 16, BC = c() == 2 ? 16384 : 8192, BS = c() == 2 ? 1024 : 512;
+            launch_ev(k_sep_eval_blk<G, BC, BS, 4>, (unsigned)(num_cus * blk_wg_per_cu), BS, 0, stream, e0, nullptr, d_bcolk.p, d_bpp.p, d_bseg.p, d_bkind.p,
+                      m_nl, blk_nb, d_x, n_lp, d_part.p);
+        });
+        launch_ev(k_sep_combine, grid_n(m_nl), kBlock, 0, stream, nullptr, e1, d_slots.p, m_nl, blk_nb, d_part.p, f_tol, O);
+    } else if (sb_on) {
+        if (!sb_lds_set) {
+            KTN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sep_sweep_batch), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSbLds));
+            sb_lds_set = true;
         }
-#define KTN_BLK_LAUNCH(G, BC, BS, U)                                                                                      \
-hipExtLaunchKernelGGL((k_sep_eval_blk<G, BC, BS, U>), dim3((unsigned)(num_cus * blk_wg_per_cu)), dim3(BS), 0, stream, e0, nullptr, 0, \
-                      d_bcolk.p, d_bpp.p, d_bseg.p, d_bkind.p, m_nl, blk_nb, d_x, n_lp, d_part.p)
-        switch (blk_cfg) {       // KTN_BLK_CFG: tuning variants kept for the next round's experiments
-            case 1: KTN_BLK_LAUNCH(16, 8192, 512, 4); break;
-            case 2: KTN_BLK_LAUNCH(16, 16384, 1024, 4); break;
-            default: KTN_BLK_LAUNCH(8, 8192, 512, 4); break;
-        }
-#undef KTN_BLK_LAUNCH
-        hipExtLaunchKernelGGL(k_sep_combine, dim3(ceil_div(m_nl, kBlock)), dim3(kBlock), 0, stream, nullptr, e1, 0, d_slots.p, m_nl, blk_nb,
-                              d_part.p, f_tol, O);
+        SbView V{d_sbck.p, d_sbrow.p, d_sbpp.p, d_sbseg.p, sb_nb};
+        launch_ev(k_sep_sweep_batch, (unsigned)sb_batches, kSbThreads, kSbLds, stream, e0, e1, V, P, d_nlrows.p, m_nl, d_x, n_lp, f_tol, O);
     } else {
         // many short rows: several rows per lane group (k_sep_sweep) once one row per group would make more wavefronts
         // than the chip holds several times over; small sweeps keep one row per group and all the parallelism (the
         // choice is made once in loadproblem)
         const int R = sweep_rows_per_group;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (prm.profile) {
-            const size_t ea = ev_get(), eb = ev_get();
-            e0 = ev_pool[ea]; e1 = ev_pool[eb];
-            ev_recs.push_back({2, ea, eb, sweep_bytes});
-        }
-        if (sb_on) {
-            if (!sb_lds_set) {
-                KTN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sep_sweep_batch), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSbLds));
-                sb_lds_set = true;
-            }
-            SbView V{d_sbck.p, d_sbrow.p, d_sbpp.p, d_sbseg.p, sb_nb};
-            hipExtLaunchKernelGGL(k_sep_sweep_batch, dim3((unsigned)sb_batches), dim3(kSbThreads), kSbLds, stream, e0, e1, 0, V, P, d_nlrows.p, m_nl, d_x, n_lp, f_tol, O);
-        } else
-        if (R >= 4) LAUNCH_GB_EV(grp_sweep, k_sep_sweep, 4, ceil_div(m_nl, (int64_t)4), stream, e0, e1, P, d_nlrows.p, m_nl, d_x, f_tol, O);
-        else if (R >= 2) LAUNCH_GB_EV(grp_sweep, k_sep_sweep, 2, ceil_div(m_nl, (int64_t)2), stream, e0, e1, P, d_nlrows.p, m_nl, d_x, f_tol, O);
-        else LAUNCH_G_EV(grp_sweep, k_sep_eval, m_nl, stream, e0, e1, P, d_nlrows.p, m_nl, d_x, f_tol, 0, 1, O);
+        with_value<4, 2, 1>(R >= 4 ? 4 : R >= 2 ? 2 : 1, [&](auto r) {
+            with_group(grp_sweep, [&](auto g) {
+                constexpr int G = g(), RR = r();
+                if constexpr (RR == 1) launch_ev(k_sep_eval<G>, group_grid(m_nl, G), kBlock, 0, stream, e0, e1, P, d_nlrows.p, m_nl, d_x, f_tol, 0, 1, O);
+                else launch_ev(k_sep_sweep<G, RR>, group_grid(m_nl, G, RR), kBlock, 0, stream, e0, e1, P, d_nlrows.p, m_nl, d_x, f_tol, O);
+            });
+        });
     }
     if (n_longev_nl > 0)
-        hipLaunchKernelGGL(k_sep_eval_long, dim3((unsigned)n_longev_nl), dim3(1024), 0, stream, P, d_longev_nlrows.p, d_longev_nlslots.p, d_x, f_tol, 1, O);
+        launch(k_sep_eval_long, (unsigned)n_longev_nl, 1024, 0, stream, P, d_longev_nlrows.p, d_longev_nlslots.p, d_x, f_tol, 1, O);
     launch_quad(true, d_x, f_tol);
     if (n_tape_nl > 0 || n_host_nl > 0) {
         // tape rows: the classed shapes in one launch (k_tape_classed, statistics folded in), the others through the interpreter
@@ -1262,12 +1251,12 @@ hipExtLaunchKernelGGL((k_sep_eval_blk<G, BC, BS, U>), dim3((unsigned)(num_cus * 
         const bool ev = prm.profile && n_tape_nl > 0;
         if (ev) { ta = ev_get(); tb = ev_get(); KTN_HIP(hipEventRecord(ev_pool[ta], stream)); }
         const int64_t n_int = (int64_t)d_tapeint_nl.n;
-        LAUNCH_1(k_tape_eval, n_int, stream, P, d_tapeint_nl.p, n_int, d_x, O);
+        launch_n(k_tape_eval, n_int, stream, P, d_tapeint_nl.p, n_int, d_x, O);
         if (n_host_nl > 0) host_eval(d_x);
         launch_tape_classed(true, d_tc_mslot.p, d_x, f_tol);
         if (n_int > 0 || n_host_nl > 0)
-            LAUNCH_1(k_gj_stats, m_nl, stream, P, d_nlrows.p, m_nl, d_x, f_tol, (int)KTN_ROW_TAPE,
-                     (const uint8_t*)(tc_rows_nl > 0 ? d_tc_rowflag.p : nullptr), O);
+            launch_n(k_gj_stats, m_nl, stream, P, d_nlrows.p, m_nl, d_x, f_tol, (int)KTN_ROW_TAPE, (const uint8_t*)(tc_rows_nl > 0 ? d_tc_rowflag.p : nullptr),
+                     O);
         if (ev) { KTN_HIP(hipEventRecord(ev_pool[tb], stream)); ev_recs.push_back({4, ta, tb, tape_bytes}); }
     }
     check_launch();
@@ -1278,9 +1267,8 @@ hipExtLaunchKernelGGL((k_sep_eval_blk<G, BC, BS, U>), dim3((unsigned)(num_cus * 
     int32_t anynf = 0;
     if (h_chk_dev) {                               // one thread gathers the six scalars into pinned host memory
         double* ht = h_chk + 2 * kChkQ;
-        hipLaunchKernelGGL(k_host_tail, dim3(1), dim3(1), 0, stream, h_chk_dev + 2 * kChkQ, d_flag.p + (m_nl - 1), d_rank.p + (m_nl - 1),
-                           d_cnt.p + (m_nl - 1), d_cntscan.p + (m_nl - 1), (const double*)d_scal.p, (const int32_t*)d_anynf.p,
-                           (const int32_t*)nullptr);
+        launch(k_host_tail, 1, 1, 0, stream, h_chk_dev + 2 * kChkQ, d_flag.p + (m_nl - 1), d_rank.p + (m_nl - 1), d_cnt.p + (m_nl - 1),
+               d_cntscan.p + (m_nl - 1), (const double*)d_scal.p, (const int32_t*)d_anynf.p, (const int32_t*)nullptr);
         sync();
         for (int k = 0; k < 4; ++k) tail[k] = (int64_t)ht[k];
         mv = ht[4]; anynf = (int32_t)ht[5];
@@ -1305,11 +1293,11 @@ hipExtLaunchKernelGGL((k_sep_eval_blk<G, BC, BS, U>), dim3((unsigned)(num_cus * 
     if (cap > 0 && row_sharded()) cap = std::max<int64_t>(cap / dist.world, 1);      // every rank selects among ITS rows
     if (cap > 0 && V > cap && !anynf) {
         d_dkeys.resize((size_t)m_nl, stream); d_dsorted.resize((size_t)m_nl, stream);
-        LAUNCH_1(k_depth_keys, m_nl, stream, P, d_nlrows.p, m_nl, d_g.p, d_flag.p, d_dkeys.p);
+        launch_n(k_depth_keys, m_nl, stream, P, d_nlrows.p, m_nl, d_g.p, d_flag.p, d_dkeys.p);
         const size_t need = sort_keys_desc_temp_bytes((size_t)m_nl);
         d_sorttmp.resize(need + 16, stream);
         KTN_HIP(sort_keys_desc_u64(d_sorttmp.p, need, d_dkeys.p, d_dsorted.p, (size_t)m_nl, stream));
-        LAUNCH_1(k_depth_reflag, m_nl, stream, m_nl, d_dkeys.p, d_dsorted.p, cap, d_flag.p, d_cnt.p);
+        launch_n(k_depth_reflag, m_nl, stream, m_nl, d_dkeys.p, d_dsorted.p, cap, d_flag.p, d_cnt.p);
         check_launch();
         exclusive_scan(d_flag.p, d_rank.p, (size_t)m_nl);
         exclusive_scan(d_cnt.p, d_cntscan.p, (size_t)m_nl);
@@ -1341,11 +1329,12 @@ hipExtLaunchKernelGGL((k_sep_eval_blk<G, BC, BS, U>), dim3((unsigned)(num_cus * 
         lp_val.resize((size_t)(NNZ + nnzV), stream);
         d_violslots.resize((size_t)V, stream);
         LpRows L = lp_view();
-        LAUNCH_1(k_compact, m_nl, stream, P, d_nlrows.p, m_nl, d_flag.p, d_rank.p, d_cntscan.p, d_bconst.p, M, NNZ, L,
-                 d_violslots.p, d_lastcut.p, d_cutprev.p, (int)(prm.lp_dual_inherit && !glists));
+        launch_n(k_compact, m_nl, stream, P, d_nlrows.p, m_nl, d_flag.p, d_rank.p, d_cntscan.p, d_bconst.p, M, NNZ, L, d_violslots.p, d_lastcut.p, d_cutprev.p,
+                 (int)(prm.lp_dual_inherit && !glists));
         if (esh_mode()) esh_emit(d_x, V);
-        else LAUNCH_G(grp_sweep, k_emit, V, stream, P, d_nlrows.p, d_violslots.p, V, d_x, d_jac.p, d_maxc.p,
-                      prm.cut_coef_rng, 1, M, L);
+        else with_group(grp_sweep, [&](auto g) {
+            launch(k_emit<g()>, group_grid(V, g()), kBlock, 0, stream, P, d_nlrows.p, d_violslots.p, V, d_x, d_jac.p, d_maxc.p, prm.cut_coef_rng, 1, M, L);
+        });
         check_launch();
         M += V;
         NNZ += nnzV;
