@@ -1685,6 +1685,14 @@ static __global__ __launch_bounds__(kBlock) void k_restart_set(int64_t n, int64_
     if (i < n) { const double v = xt[i]; x[i] = v; x0[i] = v; if (crec) crec[i].x0 = v; }
     if (i < m) { const double v = yt[i]; y[i] = v; y0[i] = v; if (rrec) rrec[i].y0 = v; }
 }
+// The point a solve goes back to after its iterates ran away under a step that was too long: xt <- the point of the box nearest
+// to 0, yt <- 0 (k_restart_set then takes it as T(z)).
+static __global__ __launch_bounds__(kBlock) void k_cold_point(int64_t n, int64_t m, const double* __restrict__ l, const double* __restrict__ u,
+                                                      double* __restrict__ xt, double* __restrict__ yt) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i < n) xt[i] = clampd(0.0, l[i], u[i]);
+    if (i < m) yt[i] = 0.0;
+}
 // Halpern update of the primal and the dual part in one launch (after a check iteration that neither terminated nor
 // restarted); also refreshes xbar = 2 xt - x_old for nobody: the next x-step recomputes it
 static __global__ __launch_bounds__(kBlock) void k_halpern2(int64_t n, int64_t m, double* __restrict__ x, const double* __restrict__ xt,

@@ -1013,6 +1013,7 @@ LpResult Engine::lp_solve_core(double tol_p, double tol_g, int mode, bool identi
         stats["lp_omega_robust"] += 1.0;
     }
     double om = (have_omega && mode == 0) ? omega : omega_ref;
+    const double om_start = om;
     const double rho = 1.0;
     // The rules of this loop's checks (pdhg_check.hpp; DESIGN.md section 5 sets them beside the device-side loops').
     PdhgRules rules{};
@@ -1073,7 +1074,8 @@ LpResult Engine::lp_solve_core(double tol_p, double tol_g, int mode, bool identi
     bool blocks_done = false;
     if (n_blocks > 0 && mode == 0 && !row_sharded() && n_long == 0 && m > 0 && !prm.profile) {
         if (blocks_built_rows != M) build_blocks();
-        blocks_done = lp_solve_blocks(tol_p, tol_g, eta, &R, max_it);
+        // (the block kernel has no growing-residual back-off: next to columns without a bound it starts with the safe step)
+        blocks_done = lp_solve_blocks(tol_p, tol_g, has_inf_bound ? eta_safe : eta, &R, max_it);
         if (blocks_done) it = R.iters;
     }
     const int near_env = dev.near_chunk;
@@ -1154,6 +1156,17 @@ LpResult Engine::lp_solve_core(double tol_p, double tol_g, int mode, bool identi
                 stats["lp_restarts"] += 1.0;
             }
             om = nx.om;
+            if (nx.backoff == PDHG_BACKOFF_GROW && has_inf_bound) {
+                // The residual grew check after check: the power iteration gave a sigma_max below the true one (a block-diagonal
+                // matrix has one near-largest singular value per block, which 8 passes do not separate) and the iterates ran
+                // away.  A box clamps them back once the step is safe; a column without a bound keeps what it picked up
+                // (seen: |x| 1e13 after 65 iterations at eta sigma_max = 1.08, not back after 400 000).  Such a solve starts
+                // again, from the point of the box nearest to 0, with the safe step and the weight it began with.
+                launch_n(k_cold_point, std::max(n, m), stream, n, m, lh.p, uh.p, xth.p, yth.p);
+                eta = eta_safe;
+                om = om_start;
+                stats["lp_cold_restarts"] += 1.0;
+            }
             lp_restart();
             k = 0;
             ++it;
