@@ -317,6 +317,10 @@ __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B, EshArg..
             const double xh = clampd(xg[j] / d, ll[j] / d, uu[j] / d);
             xs[j] = xh; x0s[j] = xh; xts[j] = xh;
         }
+        // An LP without rows (an instance without linear rows, before its first cut): ecp_spmv multiplies the entries a lane does
+        // not have by element 0 of the vector -- 0.0 * v[0] -- and no row has defined ys[0], y0s[0], yts[0]: a NaN that an earlier
+        // workgroup left in this LDS would reach every A'y.  (mmax >= 1: the element exists.)
+        if (M == 0 && tid == 0) { ys[0] = 0.0; y0s[0] = 0.0; yts[0] = 0.0; }
         __syncthreads();
 
         // ============================================================ sigma_max: 20 power passes (hashed start vector) ==

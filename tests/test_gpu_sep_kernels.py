@@ -3,6 +3,8 @@ k_sep_eval_long, k_sep_eval_blk + k_sep_combine, k_sep_sweep_batch, the passes i
 high-precision reference of tests/sep_ref.py, on the cases of tests/sep_cases.py (whose input conditions
 tests/test_sep_ref.py asserts).  Every case asserts the load-time statistics that name the form it means to run.
 Tolerances come from sep_ref alone; the only literal is f_tol = 2^-20 (sep_ref.F_TOL).
+The passes inside k_ecp_blocks are covered here by whole solves only; their cuts are compared entry by entry with the reference
+in tests/test_gpu_blocks_kelley.py.
 
 Per case, three models: edges = 0 (maxviol finite, from a lower-sided row), edges = 1 (rows whose value is NaN with finite
 partials: cut rows with NaN bounds) and edges = 2 (a non-finite coefficient in a violated row: status Error, nothing appended).
