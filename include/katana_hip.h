@@ -349,6 +349,59 @@ int ktn_get_constr_duals(ktn_handle h, double* d_out, int64_t m);
 int ktn_get_reduced_costs(ktn_handle h, double* z_out, int64_t n);
 int ktn_get_dual_bound(ktn_handle h, double* bound, double* gap);
 
+/* ---- a feasible point and the primal bound it certifies --------------
+ * ktn_get_solution returns the LP optimum x*, an OUTER point: it may violate every active nonlinear row by up to f_tol.
+ * ktn_get_feasible_point returns x_feas on the segment from a reference point x_in to x* with every taking-part row satisfied, so
+ * that for a convex problem   bound of ktn_get_dual_bound <= f* <= f(x_feas)   (Min; mirrored for Max).
+ *   x_in           the caller's point (ktn_set_interior_point, accepted under every cut_algo); under KTN_CUT_SUPPORTING[_QUAD]
+ *                  without one, the engine's own (found first if that has not happened yet, as by ktn_get_interior_point).  Under
+ *                  KTN_CUT_KELLEY without a caller's point there is none: found = 0.  x_in must lie in [l, u] and satisfy every
+ *                  taking-part row (found = -1 otherwise); the engine's own point, which meets the bounds only to its auxiliary
+ *                  LP's tolerance, is clamped into [l, u] first.
+ *   taking part    every row i < num_constr that is not declared linear, of kind SEP, TAPE or QUAD, with exactly one finite side
+ *                  (sigma_i = +1: g_i <= ub_i, -1: g_i >= lb_i; b_i that bound), under every cut_algo.  Not the epigraph row, not
+ *                  a free nonlinear row.  phi_i(lambda) = sigma_i (g_i(x_in + lambda (x* - x_in)) - b_i).
+ *   lambda_i       1 where phi_i(1) <= 0 and is finite; otherwise a point of [0, 1) with -tau <= phi_i(lambda_i) <= 0,
+ *                  tau = esh_root_tol * f_tol, found by bracketed Newton on phi + tau / 2 from lambda = 1 (bisection when a step
+ *                  leaves the bracket or the derivative is not positive and finite), esh_root_iters passes at most.  A row that
+ *                  runs out of passes takes the bracket's lower end -- the last point with a finite phi <= 0, 0 to begin with -- and
+ *                  is counted in info[6]: validity never depends on convergence.
+ *   lambda*        min_i lambda_i; the blocking row is the smallest row index attaining a minimum below 1.
+ *   x_feas         clamp(x_in_j + lambda* (x*_j - x_in_j), l_j, u_j)  (lambda* = 1: x*_j itself)
+ *   verification   every row is evaluated at x_feas; found = 1 only if every taking-part row has sigma (g - b) <= 0 there.  If one
+ *                  has not (rounding, the clamp), back-off k = 1 .. 8 takes lambda* (1 - 2^(6 k - 48)) and verifies again -- the
+ *                  eighth is x_in itself --; found = -2 after eight failures.  Linear rows and bounds are not searched: info[4]
+ *                  reports the largest violation of a linear row at x_feas, which convexity bounds by those at x_in and x*.
+ * info[KTN_FEAS_INFO_LEN]:
+ *   [0] found      1 found; 0 no reference point; -1 the reference point is outside [l, u], violates a taking-part row, or a row is
+ *                  not finite there; -2 verification failed
+ *   [1] lambda*    (the one x_feas was formed with, back-offs included)
+ *   [2] f(x_feas)  the objective row's own value at x_feas, in the caller's sense: f* <= f(x_feas) for Min, >= for Max
+ *   [3] max_i sigma_i (g_i - b_i) at x_feas over the taking-part rows: <= 0; -inf when there are none  (found = -1: at x_in)
+ *   [4] the largest violation of a linear row at x_feas, >= 0                                          (found = -1: at x_in)
+ *   [5] the blocking row, -1 if none; found = -1: the first offending row (-1: the point is outside [l, u])
+ *   [6] rows that ended unconverged        [7] back-offs
+ * When found != 1, x_out is NaN.  ktn_get_feasible_row_lambdas: lambda_i by caller row (1 for a row that does not take part).
+ * Computed on the first call and cached; dropped by ktn_loadproblem, ktn_reset, any LP solve, any change of the LP rows and
+ * ktn_set_interior_point.  A solve that is followed by no getter launches nothing for this (stat "feas_evals" stays 0), and what
+ * ktn_sep_*, the objective certificate, the KKT report and a following ktn_ecp_step read is left bit for bit.
+ * KTN_E_UNSUPPORTED (with a message): KTN_ROW_HOST rows or objective, a nonlinear row with two finite sides, a row-sharded handle
+ * or one with a cut exchange.  KTN_E_INVALID: while ktn_get_dual_bound would refuse (no LP solve since load or reset), n < num_var,
+ * cap < KTN_FEAS_INFO_LEN.  After ktn_optimize_blocks[_ex] x* is the fused problem's point, as for ktn_get_dual_bound.
+ * Stats: "feas_evals" times the kernels ran; "feas_passes" evaluation passes of the last search; "feas_group" lanes per row. */
+#define KTN_FEAS_INFO_LEN 8
+int ktn_get_feasible_point(ktn_handle h, double* x_out, int64_t n, double* info, int64_t cap);
+int ktn_get_feasible_row_lambdas(ktn_handle h, double* lam_out, int64_t m);
+/* The same per instance of a fused batch (ktn_set_blocks; rows and columns grouped by instance, refused otherwise as by
+ * ktn_blocks_get_dual_bounds): *count = KTN_FEAS_INFO_LEN * n_blocks; info[KTN_FEAS_INFO_LEN b ..] is instance b's record, with
+ * lambda_b = the minimum over the instance's own rows (1 for an instance without nonlinear rows), [2] the instance's share c_b'x_b of
+ * the fused objective as ktn_blocks_get_dual_bounds forms it, [5] a row index of the fused problem; x_out [num_var] holds every
+ * instance's segment of x_feas = clamp(x_in + lambda_b (x* - x_in), l, u), NaN for an instance whose found != 1.  An instance whose
+ * reference point fails gets its own code and does not affect the others; back-offs are per instance.  The reference points are the
+ * segments of the fused problem's point (ktn_set_interior_point), x* is the fused problem's point also after ktn_optimize_blocks[_ex].
+ * x_out == NULL and info == NULL only asks for the count.  One workgroup per instance for lambda_b and for the verification. */
+int ktn_blocks_get_feasible_points(ktn_handle h, double* x_out, int64_t n, double* info, int64_t cap, int64_t* count);
+
 /* ---- supporting-hyperplane cuts (cut_algo = KTN_CUT_SUPPORTING or KTN_CUT_SUPPORTING_QUAD) ------
  * The interior point x_int [num_var, without the epigraph variable]: ktn_set_interior_point hands one over (NULL clears
  * it, and the engine then looks for one itself when it next needs it); ktn_loadproblem forgets it, ktn_reset keeps it.

@@ -13,6 +13,7 @@ ROW_SEP, ROW_TAPE, ROW_HOST, ROW_QUAD = 0, 1, 2, 3
 ATOM_LIN, ATOM_QUAD, ATOM_EXP, ATOM_NEGLOG = 0, 1, 2, 3
 CUT_KELLEY, CUT_SUPPORTING, CUT_SUPPORTING_QUAD = 0, 1, 2          # ktn_params.cut_algo
 BLOCKS_SUPPORTING, BLOCKS_NO_FALLBACK = 1, 2                       # ktn_optimize_blocks_ex flags
+FEAS_INFO_LEN = 8                                                  # KTN_FEAS_INFO_LEN (ktn_get_feasible_point)
 LPOP_STEP, LPOP_CHECK, LPOP_ADVANCE, LPOP_RESTART = range(4)      # ktn_lp_script ops
 LPS_IDENTITY, LPS_PACKED, LPS_NO_SPEC = 1, 2, 4                   # ktn_lp_script flags
 (OP_CONST, OP_VAR, OP_ADD, OP_SUB, OP_MUL, OP_DIV, OP_NEG, OP_POWC, OP_EXP, OP_LOG, OP_SQRT, OP_SIN,
@@ -84,6 +85,9 @@ PROTOTYPES = {
     "ktn_get_dual_bound": (c_i32, [C.c_void_p, P(c_f64), P(c_f64)]),
     "ktn_blocks_get_duals": (c_i32, [C.c_void_p, c_i64, P(c_f64), c_i64, P(c_i64)]),
     "ktn_blocks_get_dual_bounds": (c_i32, [C.c_void_p, P(c_f64), c_i64, P(c_i64)]),
+    "ktn_get_feasible_point": (c_i32, [C.c_void_p, P(c_f64), c_i64, P(c_f64), c_i64]),
+    "ktn_get_feasible_row_lambdas": (c_i32, [C.c_void_p, P(c_f64), c_i64]),
+    "ktn_blocks_get_feasible_points": (c_i32, [C.c_void_p, P(c_f64), c_i64, P(c_f64), c_i64, P(c_i64)]),
     "ktn_set_interior_point": (c_i32, [C.c_void_p, P(c_f64), c_i64]),
     "ktn_get_interior_point": (c_i32, [C.c_void_p, P(c_f64), c_i64, P(c_i32)]),
     "ktn_sep_precompute": (c_i32, [C.c_void_p, P(c_f64), c_i64]),

@@ -220,6 +220,41 @@ class FusedBatch:
         return out
 
 
+    # ---- a feasible point per instance ----
+    def feasible_points(self):
+        """one FeasiblePoint per instance (KatanaNonlinearModel.feasible_point), in the instance's own variables -- the epigraph
+        variable that fusion gave a quadratic objective left out --, rows and sense: x_feas on the segment from the instance's
+        reference point (set_interior_points) to its part of the solution, lambda_b over the instance's own rows (1 for an
+        instance without nonlinear rows), objval its share of the fused objective in its own sense with its own constant.  An
+        instance whose reference point fails gets found = -1 and a NaN x; the others are not affected.  A batch solved by the host
+        loop has no blocks set: they are set for the call and cleared again.
+        (The epigraph column of a quadratic objective is padded with 0 in the reference point, so such an instance has a usable
+        reference point only where its objective is <= 0 there; its objval is the epigraph variable at x_feas, an upper estimate.)"""
+        import numpy as np
+        from .solver import FeasiblePoint
+        m = self.m
+        temp = not (self.per_instance_lp or self.device_loop)
+        if temp:
+            m.set_blocks(self.offs)
+        try:
+            x, info = m.blocks_feasible_points()
+        finally:
+            if temp:
+                m.set_blocks([0])
+        nv = self._nvar if self._objinfo is not None else [int(self.offs[k + 1] - self.offs[k]) for k in range(len(self.instances))]
+        out = []
+        for k, (idx, sgn) in enumerate(self._row_ranges()):
+            r = info[k]
+            c0 = float(self._objinfo[k][2]) if self._objinfo is not None else float(self.instances[k].obj_const)
+            row = int(r[5])
+            if row >= 0:                                            # a row of the fused problem -> the instance's own row index
+                own = np.flatnonzero(idx == row)
+                row = int(own[0]) if len(own) else -1
+            out.append(FeasiblePoint(int(r[0]), x[int(self.offs[k]):int(self.offs[k]) + int(nv[k])].copy(), float(r[1]), sgn * float(r[2]) + c0,
+                                     float(r[3]), float(r[4]), row, int(r[6]), int(r[7])))
+        return out
+
+
 def _solve_fused(solver, instances, per_instance_lp=False, device_loop=False):
     t0 = time.perf_counter()
     out = FusedBatch(solver, instances, per_instance_lp, device_loop).solve()

@@ -154,6 +154,41 @@ int ktn_get_dual_bound(ktn_handle h, double* bound, double* gap) {
     })
 }
 
+// ---- a feasible point and the primal bound it certifies (Engine::feas_compute, feas.hip: computed on the first call, cached)
+int ktn_get_feasible_point(ktn_handle h, double* x_out, int64_t n, double* info, int64_t cap) {
+    KTN_TRY(h, {
+        Engine* e = h->eng;
+        KTN_REQUIRE(e->loaded && x_out && info && n >= e->n0 && cap >= KTN_FEAS_INFO_LEN, "ktn_get_feasible_point: buffer missing or too small");
+        e->feas_compute();
+        if (e->n0 > 0) std::memcpy(x_out, e->h_feas_x.data(), (size_t)e->n0 * sizeof(double));
+        std::memcpy(info, e->feas_info, KTN_FEAS_INFO_LEN * sizeof(double));
+        return KTN_OK;
+    })
+}
+int ktn_blocks_get_feasible_points(ktn_handle h, double* x_out, int64_t n, double* info, int64_t cap, int64_t* count) {
+    KTN_TRY(h, {
+        Engine* e = h->eng;
+        KTN_REQUIRE(e->loaded && count && e->n_blocks > 0, "ktn_blocks_get_feasible_points: after ktn_loadproblem and ktn_set_blocks");
+        *count = KTN_FEAS_INFO_LEN * e->n_blocks;
+        if (x_out || info) {
+            KTN_REQUIRE(x_out && info && n >= e->n0 && cap >= *count, "ktn_blocks_get_feasible_points: buffer missing or too small");
+            e->feas_blocks();
+            if (e->n0 > 0) std::memcpy(x_out, e->h_feas_blk_x.data(), (size_t)e->n0 * sizeof(double));
+            std::memcpy(info, e->h_feas_blk_info.data(), (size_t)*count * sizeof(double));
+        }
+        return KTN_OK;
+    })
+}
+int ktn_get_feasible_row_lambdas(ktn_handle h, double* lam_out, int64_t m) {
+    KTN_TRY(h, {
+        Engine* e = h->eng;
+        KTN_REQUIRE(e->loaded && lam_out && m >= e->m0, "ktn_get_feasible_row_lambdas: buffer missing or too small");
+        e->feas_compute();
+        if (e->m0 > 0) std::memcpy(lam_out, e->h_feas_lam.data(), (size_t)e->m0 * sizeof(double));
+        return KTN_OK;
+    })
+}
+
 // ---- supporting-hyperplane cuts: the interior point
 int ktn_set_interior_point(ktn_handle h, const double* x, int64_t n) {
     KTN_TRY(h, {
@@ -169,6 +204,7 @@ int ktn_set_interior_point(ktn_handle h, const double* x, int64_t n) {
         }
         e->esh_ready = false;
         e->xint_found = 0;
+        e->feas_cached = false; e->feas_blk_cached = false;
         return KTN_OK;
     })
 }
@@ -198,6 +234,7 @@ int ktn_sep_precompute(ktn_handle h, const double* xstar, int64_t n) {
         e->precompute_all(e->d_xs.p);
         e->sync();
         e->have_precompute = true;
+        if (e->dev.feas_xstar_pre) { e->feas_cached = false; e->feas_blk_cached = false; }      // (x* of the feasible point is this point then)
         return KTN_OK;
     })
 }
@@ -525,6 +562,7 @@ int ktn_set_blocks(ktn_handle h, int64_t nblocks, const int64_t* col_offsets) {
     KTN_TRY(h, {
         Engine* e = h->eng;
         KTN_REQUIRE(e->loaded && nblocks >= 0, "ktn_set_blocks: after loadproblem");
+        e->feas_blk_cached = false;
         if (nblocks == 0) { e->n_blocks = 0; e->kkt_seg_ok = false; e->h_kkt_blk.clear(); return KTN_OK; }
         KTN_REQUIRE(col_offsets && e->obj_linear, "ktn_set_blocks: needs a linear objective (no shared epigraph variable)");
         KTN_REQUIRE(col_offsets[0] == 0 && col_offsets[nblocks] == e->n_lp, "ktn_set_blocks: offsets must cover the columns");

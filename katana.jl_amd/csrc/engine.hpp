@@ -92,6 +92,8 @@ struct DevParams {
     bool raw_duals = false;        // KTN_RAW_DUALS        ktn_lp_get_duals returns lp_y as the loop sees it, also after an exact mid-size solve
     int mid_refactor = 0;          // KTN_MID_REFACTOR     pivots between refactorisations of the mid-size exact LP (<= 0: kMidRefactor, mid_lp.hpp)
     int kkt_group = 0;             // KTN_KKT_GROUP        lanes per column of k_lagr_grad (0 = by mean column length)
+    int feas_group = 0;            // KTN_FEAS_GROUP       lanes per row of k_feas_sep and k_feas_quad (0 = those of the sweep / of k_quad_stats)
+    bool feas_xstar_pre = false;   // KTN_FEAS_XSTAR_PRECOMPUTE   the feasible point takes x* from the last ktn_sep_precompute instead of lp_x (tests)
     static bool flag(const char* k) { return std::getenv(k) != nullptr; }
     static int geti(const char* k, int d) { const char* v = std::getenv(k); return v ? std::atoi(v) : d; }
     static double getd(const char* k, double d) { const char* v = std::getenv(k); return v ? std::atof(v) : d; }
@@ -114,7 +116,8 @@ struct DevParams {
         omega_art_clamp = getd("KTN_OMEGA_ART_CLAMP", omega_art_clamp); omega_clamp = getd("KTN_OMEGA_CLAMP", omega_clamp);
         omega_clamp_down = getd("KTN_OMEGA_CLAMP_DOWN", omega_clamp_down); ipc_timeout_s = getd("KTN_IPC_TIMEOUT_S", ipc_timeout_s);
         mid_refactor = geti("KTN_MID_REFACTOR", mid_refactor); raw_duals = flag("KTN_RAW_DUALS");
-        kkt_group = geti("KTN_KKT_GROUP", kkt_group);
+        kkt_group = geti("KTN_KKT_GROUP", kkt_group); feas_group = geti("KTN_FEAS_GROUP", feas_group);
+        feas_xstar_pre = flag("KTN_FEAS_XSTAR_PRECOMPUTE");
     }
 };
 
@@ -622,8 +625,10 @@ struct Engine {
     DBuf<int32_t> d_kkt_rowmap;                  // [m0] position among the linear rows (= LP row), or -1 - NL slot; built at load
     int64_t kkt_n_lin = 0;
     // column mirror of the extended NLP structure, built on first use per loaded problem: 8 (n0 + 2) + (4 + 4) nnz_ext bytes
-    DBuf<int64_t> d_kkt_cptr, d_kkt_seg;
-    DBuf<int32_t> d_kkt_crow, d_kkt_nonfin;
+    DBuf<int64_t> d_kkt_cptr, d_kkt_seg, d_kkt_browptr;
+    DBuf<int32_t> d_kkt_crow, d_kkt_nonfin, d_kkt_brows;
+    std::vector<int64_t> h_kkt_seg;              // six offsets per instance (k_dual_bound); with them the caller rows of each instance
+    void kkt_build_seg();                        // once per ktn_set_blocks (kkt_seg_ok); refuses rows that are not grouped by instance
     DBuf<uint32_t> d_kkt_cperm;
     DBuf<double> d_kkt_x, d_kkt_g, d_kkt_jac, d_kkt_bconst, d_kkt_maxc, d_kkt_d, d_kkt_z, d_kkt_t, d_kkt_out, d_kkt_blk;
     std::vector<double> h_kkt_d, h_kkt_z, h_kkt_blk;      // results on the host; h_kkt_blk: (bound, gap) per instance of a fused batch
@@ -632,6 +637,28 @@ struct Engine {
     void kkt_build_mirror();
     void kkt_compute();
     void kkt_blocks();
+
+    // ================================================================ feasible point (feas.hpp, feas.hip) ===
+    // x_feas on the segment from the reference point x_in to x* = lp_x, and what it certifies; computed on the first
+    // ktn_get_feasible_point after a solve and kept until the LP is solved again, its rows change or the interior point is set.
+    // Answers while the KKT report would (kkt_solved).  The taking-part rows are found once per loaded problem (feas_sides_ok),
+    // under every cut_algo.
+    bool feas_cached = false, feas_blk_cached = false, feas_sides_ok = false;
+    uint64_t feas_key_version = 0, feas_key_solves = 0, feas_blk_key_version = 0, feas_blk_key_solves = 0;
+    int64_t feas_n_part = 0, feas_two_sided = -1;       // feas_two_sided: the first nonlinear row with two finite sides, or -1
+    DBuf<int8_t> d_feas_sig;
+    DBuf<int32_t> d_feas_tslots, d_feas_nonfin, d_feas_unc;
+    DBuf<double> d_feas_xin, d_feas_xs, d_feas_x, d_feas_g0, d_feas_j0, d_feas_g1, d_feas_j1, d_feas_bconst, d_feas_maxc, d_feas_lam,
+                 d_feas_part, d_feas_res, d_feas_out, d_feas_shrink;
+    DBuf<unsigned long long> d_feas_cnt;
+    std::vector<double> h_feas_x, h_feas_lam;           // x_feas [n0] (NaN unless found == 1); lambda_i by caller row (1: not taking part)
+    double feas_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // KTN_FEAS_INFO_LEN
+    std::vector<double> h_feas_blk_x, h_feas_blk_info;  // the blocks form: x_feas [n0] with NaN segments, info [8 per instance]
+    void feas_sides();
+    void feas_eval(const double* d_x, DBuf<double>& g, DBuf<double>& jac);      // precompute_all into the feature's own buffers
+    void feas_run(bool blocks);
+    void feas_compute() { feas_run(false); }
+    void feas_blocks() { feas_run(true); }
 
     // ================================================================ LP ============
     void rebuild_csc();

@@ -646,6 +646,7 @@ void Engine::loadproblem(int64_t num_var, int64_t num_constr, const double* l_va
         d_kkt_rowmap.upload(rowmap, stream);
         kkt_n_lin = (int64_t)lin_rows.size();
         kkt_mirror = false; kkt_seg_ok = false;
+        feas_cached = false; feas_blk_cached = false; feas_sides_ok = false;
     }
     build_tape_classes(nodeptr, nop, na, nb, nc, tape_all);
     lapl("tape shape classes");
@@ -975,7 +976,7 @@ void Engine::reset() {
     d_age.zero(stream);
     lp_dirty = true; ++lp_version; ++lp_epoch; have_omega = false; have_precompute = false; sharded_rows = false; scal_rows = 0; smax_rows = 0; n_longc = 0; col_len_max = -1; col_scan_rows = 0; col_removed_rows = 0;
     blocks_built_rows = -1;
-    kkt_solved = false; kkt_arena = false; kkt_cached = false;
+    kkt_solved = false; kkt_arena = false; kkt_cached = false; feas_cached = false; feas_blk_cached = false;
     if (d_blkomega.n) d_blkomega.zero(stream);
     if (ds_valid.n) ds_valid.zero(stream);
     dense_credit = dense_run = 0;
@@ -1146,41 +1147,59 @@ void Engine::kkt_compute() {
     kkt_key_version = lp_version; kkt_key_solves = kkt_solves; kkt_cached = true;
 }
 
+// The instances' ranges of a fused batch -- linear rows, NL slots, columns, each grouped by instance, instance after instance -- and
+// the caller rows of each instance, found once per ktn_set_blocks (kkt_seg_ok); shared by kkt_blocks and the feasible points per
+// instance (feas.hip).
+void Engine::kkt_build_seg() {
+    const int64_t nb = n_blocks;
+    if (kkt_seg_ok) return;
+    std::vector<int64_t> seg((size_t)nb * 6), bl((size_t)nb + 1, 0), bn((size_t)nb + 1, 0), bptr((size_t)nb + 1, 0);
+    std::vector<int32_t> blk_of((size_t)std::max<int64_t>(m0, 1), 0);
+    auto block_of_col = [&](int64_t c) { return (int64_t)(std::upper_bound(h_blkcol.begin(), h_blkcol.end(), c) - h_blkcol.begin()) - 1; };
+    std::vector<char> is_nl((size_t)std::max<int64_t>(m0, 1), 0);
+    for (auto r : h_nlrows) if (r < m0) is_nl[(size_t)r] = 1;
+    int64_t prev_l = 0, prev_n = 0;
+    bool grouped = true;
+    for (int64_t i = 0; i < m0; ++i) {
+        if (h_rowptr[i + 1] == h_rowptr[i]) { grouped = false; break; }
+        const int64_t b = std::min<int64_t>(std::max<int64_t>(block_of_col(h_col[(size_t)h_rowptr[i]]), 0), nb - 1);
+        int64_t& prev = is_nl[(size_t)i] ? prev_n : prev_l;
+        if (b < prev) { grouped = false; break; }
+        prev = b;
+        (is_nl[(size_t)i] ? bn : bl)[(size_t)b + 1] += 1;
+        blk_of[(size_t)i] = (int32_t)b; bptr[(size_t)b + 1] += 1;
+    }
+    if (!grouped) throw Error(KTN_E_UNSUPPORTED, "KKT report: the rows of the fused batch are not grouped by instance");
+    for (int64_t b = 0; b < nb; ++b) { bl[(size_t)b + 1] += bl[(size_t)b]; bn[(size_t)b + 1] += bn[(size_t)b]; bptr[(size_t)b + 1] += bptr[(size_t)b]; }
+    for (int64_t b = 0; b < nb; ++b) {
+        int64_t* s = seg.data() + 6 * b;
+        s[0] = bl[(size_t)b]; s[1] = bl[(size_t)b + 1];
+        s[2] = kkt_n_lin + bn[(size_t)b]; s[3] = kkt_n_lin + bn[(size_t)b + 1];
+        s[4] = m0 + h_blkcol[(size_t)b]; s[5] = m0 + std::min<int64_t>(h_blkcol[(size_t)b + 1], n0);
+    }
+    // the caller rows of each instance, ascending (the feasible point's per-instance verification, feas.hpp)
+    std::vector<int32_t> brows((size_t)std::max<int64_t>(m0, 1), 0);
+    {
+        std::vector<int64_t> cur(bptr.begin(), bptr.end() - 1);
+        for (int64_t i = 0; i < m0; ++i) brows[(size_t)cur[(size_t)blk_of[(size_t)i]]++] = (int32_t)i;
+    }
+    d_kkt_seg.upload(seg, stream);
+    d_kkt_browptr.upload(bptr, stream);
+    d_kkt_brows.upload(brows, stream);
+    sync();
+    h_kkt_seg = seg;
+    kkt_seg_ok = true;
+}
+
 // The bound per instance of a fused batch (ktn_blocks_get_dual_bounds) from the terms the last evaluation left in d_kkt_t: one
-// launch of k_dual_bound, no re-evaluation.  The instances' ranges -- linear rows, NL slots, columns, each grouped by instance,
-// instance after instance -- are found once per ktn_set_blocks (kkt_seg_ok).
+// launch of k_dual_bound, no re-evaluation.
 void Engine::kkt_blocks() {
     kkt_compute();
     const int64_t nb = n_blocks;
     KTN_REQUIRE(nb > 0, "KKT report: no blocks set (ktn_set_blocks)");
     if ((int64_t)h_kkt_blk.size() == 2 * nb) return;
     const double sgn = (sense == KTN_MAX) ? -1.0 : 1.0;
-    if (!kkt_seg_ok) {
-        std::vector<int64_t> seg((size_t)nb * 6), bl((size_t)nb + 1, 0), bn((size_t)nb + 1, 0);
-        auto block_of_col = [&](int64_t c) { return (int64_t)(std::upper_bound(h_blkcol.begin(), h_blkcol.end(), c) - h_blkcol.begin()) - 1; };
-        std::vector<char> is_nl((size_t)std::max<int64_t>(m0, 1), 0);
-        for (auto r : h_nlrows) if (r < m0) is_nl[(size_t)r] = 1;
-        int64_t prev_l = 0, prev_n = 0;
-        bool grouped = true;
-        for (int64_t i = 0; i < m0; ++i) {
-            if (h_rowptr[i + 1] == h_rowptr[i]) { grouped = false; break; }
-            const int64_t b = std::min<int64_t>(std::max<int64_t>(block_of_col(h_col[(size_t)h_rowptr[i]]), 0), nb - 1);
-            int64_t& prev = is_nl[(size_t)i] ? prev_n : prev_l;
-            if (b < prev) { grouped = false; break; }
-            prev = b;
-            (is_nl[(size_t)i] ? bn : bl)[(size_t)b + 1] += 1;
-        }
-        if (!grouped) throw Error(KTN_E_UNSUPPORTED, "KKT report: the rows of the fused batch are not grouped by instance");
-        for (int64_t b = 0; b < nb; ++b) { bl[(size_t)b + 1] += bl[(size_t)b]; bn[(size_t)b + 1] += bn[(size_t)b]; }
-        for (int64_t b = 0; b < nb; ++b) {
-            int64_t* s = seg.data() + 6 * b;
-            s[0] = bl[(size_t)b]; s[1] = bl[(size_t)b + 1];
-            s[2] = kkt_n_lin + bn[(size_t)b]; s[3] = kkt_n_lin + bn[(size_t)b + 1];
-            s[4] = m0 + h_blkcol[(size_t)b]; s[5] = m0 + std::min<int64_t>(h_blkcol[(size_t)b + 1], n0);
-        }
-        d_kkt_seg.upload(seg, stream);
-        kkt_seg_ok = true;
-    }
+    kkt_build_seg();
     d_kkt_blk.resize((size_t)(2 * nb), stream);
     launch(k_dual_bound, (unsigned)nb, kBlock, 0, stream, d_kkt_seg.p, d_kkt_t.p, lp_c.p, d_kkt_x.p, m0, d_kkt_blk.p);
     check_launch();

@@ -20,7 +20,7 @@ using JuMP
 import ..KatanaSolver, ..AbstractKatanaSeparator, ..EpigraphNLPEvaluator          # src/solver.jl:6, src/separators.jl:8, src/nlpeval.jl:6
 import ..initialize!, ..precompute!, ..gencut, ..isconstrsat                      # the separator API, src/separators.jl:23-53
 
-export KatanaHipSeparator, supporting_hyperplane_cut, supporting_hyperplane_quad_cut
+export KatanaHipSeparator, supporting_hyperplane_cut, supporting_hyperplane_quad_cut, feasible_point, blocks_feasible_points
 
 const LIB = get(ENV, "KATANA_HIP_LIB", joinpath(dirname(@__FILE__), "..", "libkatana_hip.so"))
 
@@ -373,6 +373,30 @@ function MathProgBase.getobjbound(m::KatanaHipModel)
     b, g = Ref{Cdouble}(0.0), Ref{Cdouble}(0.0)
     check(m, ccall((:ktn_get_dual_bound, LIB), Cint, (Ptr{Void}, Ref{Cdouble}, Ref{Cdouble}), m.handle, b, g))
     b[]
+end
+# A feasible point and the primal bound it certifies (include/katana_hip.h; DESIGN.md section 13): x_feas on the segment from the
+# reference point (the caller's interior point, or the engine's own under supporting_hyperplane_cut) to getsolution, and the record
+# (found, lambda, f(x_feas), margin of the nonlinear rows, largest linear violation, blocking row -- 1-based, 0 if none --,
+# rows unconverged, back-offs).  found: 1 found, 0 no reference point, -1 the reference point is not feasible, -2 verification failed.
+const KTN_FEAS_INFO_LEN = 8
+function feasible_point(m::KatanaHipModel)
+    x = fill(NaN, max(m.num_var, 1))
+    info = zeros(Float64, KTN_FEAS_INFO_LEN)
+    check(m, ccall((:ktn_get_feasible_point, LIB), Cint, (Ptr{Void}, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Int64),
+                   m.handle, x, length(x), info, length(info)))
+    Dict(:found => Int(info[1]), :x => x[1:m.num_var], :lam => info[2], :objval => info[3], :nl_margin => info[4], :lin_viol => info[5],
+         :blocking_row => Int(info[6]) + 1, :unconverged => Int(info[7]), :backoffs => Int(info[8]))
+end
+# the per-instance form of a fused batch (ktn_set_blocks): x over all columns (NaN segments where found != 1), info 8 x n_blocks
+function blocks_feasible_points(m::KatanaHipModel)
+    cnt = Ref{Int64}(0)
+    check(m, ccall((:ktn_blocks_get_feasible_points, LIB), Cint, (Ptr{Void}, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Int64, Ref{Int64}),
+                   m.handle, C_NULL, 0, C_NULL, 0, cnt))
+    x = fill(NaN, max(m.num_var, 1))
+    info = zeros(Float64, max(cnt[], 1))
+    check(m, ccall((:ktn_blocks_get_feasible_points, LIB), Cint, (Ptr{Void}, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Int64, Ref{Int64}),
+                   m.handle, x, length(x), info, length(info), cnt))
+    x[1:m.num_var], reshape(info[1:cnt[]], KTN_FEAS_INFO_LEN, :)
 end
 MathProgBase.getsolvetime(m::KatanaHipModel) = ccall((:ktn_get_solvetime, LIB), Cdouble, (Ptr{Void},), m.handle)
 MathProgBase.setwarmstart!(m::KatanaHipModel, x) = fill(0.0, length(x))                      # src/model.jl:335

@@ -1,6 +1,7 @@
 """Host mirror of Katana's plugin surface over the C ABI (src/solver.jl, src/model.jl,
 src/separators.jl, src/util.jl).  Names, argument meaning and status vocabulary follow the
 reference; indices are 0-based."""
+import collections
 import ctypes as C
 import os
 
@@ -15,6 +16,10 @@ _SUPPORTED_FEATURES = ("VisData",)   # src/solver.jl:31-32
 CUT_ALGOS = {"kelley": L.CUT_KELLEY, "linear_oa_cut": L.CUT_KELLEY,
              "supporting_hyperplane": L.CUT_SUPPORTING, "supporting_hyperplane_cut": L.CUT_SUPPORTING,
              "supporting_hyperplane_quad": L.CUT_SUPPORTING_QUAD, "supporting_hyperplane_quad_cut": L.CUT_SUPPORTING_QUAD}
+
+
+# the answer of feasible_point() (ktn_get_feasible_point: x and info[0..7])
+FeasiblePoint = collections.namedtuple("FeasiblePoint", "found x lam objval nl_margin lin_viol blocking_row unconverged backoffs")
 
 
 def _cut_algo_code(cut_algo):
@@ -196,6 +201,46 @@ class KatanaNonlinearModel:
     def getobjgap(self):
         """f(x*) - bound (Min) / bound - f(x*) (Max)"""
         return self._dual_bound()[1]
+
+    # ---- a feasible point and the primal bound it certifies (include/katana_hip.h; DESIGN.md section 13) ----
+    def feasible_point(self):
+        """x_feas on the segment from the reference point (set_interior_point, or the engine's own under the supporting-hyperplane
+        modes) to getsolution(), with every taking-part nonlinear row satisfied (ktn_get_feasible_point).  found: 1 found, 0 no
+        reference point, -1 the reference point is not feasible, -2 verification failed; x is NaN unless found == 1."""
+        x, info = np.zeros(max(self._n0, 1)), np.zeros(L.FEAS_INFO_LEN)
+        L.check(self._h, self._lib.ktn_get_feasible_point(self._h, _p(x), len(x), _p(info), len(info)))
+        return FeasiblePoint(int(info[0]), x[:self._n0].copy(), float(info[1]), float(info[2]), float(info[3]), float(info[4]), int(info[5]),
+                             int(info[6]), int(info[7]))
+
+    def feasible_row_lambdas(self):
+        """lambda_i of feasible_point() by caller row; 1 for a row that does not take part (ktn_get_feasible_row_lambdas)"""
+        lam = np.ones(max(self._m0, 1))
+        L.check(self._h, self._lib.ktn_get_feasible_row_lambdas(self._h, _p(lam), len(lam)))
+        return lam[:self._m0]
+
+    def blocks_feasible_points(self):
+        """(x [num_var], info [n_blocks, 8]) of a fused batch: every instance's segment of x_feas (NaN where its found != 1) and its
+        record (ktn_blocks_get_feasible_points; needs set_blocks)"""
+        n = C.c_int64(0)
+        null = C.POINTER(C.c_double)()
+        L.check(self._h, self._lib.ktn_blocks_get_feasible_points(self._h, null, 0, null, 0, C.byref(n)))
+        x, info = np.zeros(max(self._n0, 1)), np.zeros(max(n.value, 1))
+        L.check(self._h, self._lib.ktn_blocks_get_feasible_points(self._h, _p(x), len(x), _p(info), len(info), C.byref(n)))
+        return x[:self._n0], info[:n.value].reshape(-1, L.FEAS_INFO_LEN)
+
+    def getfeasiblesolution(self):
+        """x_feas, or None when there is none (feasible_point().found != 1)"""
+        fp = self.feasible_point()
+        return fp.x if fp.found == 1 else None
+
+    def getprimalbound(self):
+        """f(x_feas): an upper bound of the optimum for Min, a lower bound for Max; NaN when no feasible point was found"""
+        fp = self.feasible_point()
+        return fp.objval if fp.found == 1 else float("nan")
+
+    def getcertifiedgap(self):
+        """|f(x_feas) - getobjbound()|: for a convex problem the optimum lies between the two"""
+        return abs(self.getprimalbound() - self.getobjbound())
 
     def blocks_duals(self, block):
         """the unscaled multiplier of each cut row of instance `block` after the last device launch, row for row as in
