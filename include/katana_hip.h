@@ -299,6 +299,40 @@ int ktn_optimize_end(ktn_handle h);             /* src/model.jl:311-318         
 /* forget all cuts and iterates: back to the state right after ktn_loadproblem */
 int ktn_reset(ktn_handle h);
 
+/* ---- re-solve after a change of variable bounds or of a linear cost, from the kept cut pool (no
+ * counterpart in the reference, whose model is loaded once).  Every row of the pool is a tangent of a convex function or a
+ * linear row of the problem and holds whatever the box or the cost is, so both setters keep the rows, their multipliers, the
+ * cut lists and ages, x and the LP's scaling, and re-open the run state as ktn_reset does: status :None, ktn_numiters 0, the
+ * KKT report and the feasible point answer KTN_E_INVALID until the next solve.  ktn_optimize and ktn_optimize_begin /
+ * ktn_ecp_step / ktn_optimize_end then run the ordinary loop from the kept pool; ktn_numcuts goes on counting the pool;
+ * ktn_optimize_blocks[_ex] starts from the loaded rows, as always.  Both may be called after ktn_loadproblem, solved or not.
+ * KTN_E_INVALID on a handle whose status is :Error (ktn_reset or ktn_loadproblem first); KTN_E_UNSUPPORTED on a row-sharded
+ * handle and on one with a transport or a cut exchange installed.
+ *
+ * ktn_set_var_bounds: n == num_var of ktn_loadproblem (the epigraph variable keeps -inf, +inf); l == NULL or u == NULL keeps
+ *   that side; a NaN bound is KTN_E_INVALID.  x (ktn_get_solution) is clamped into the new box, stat "warm_clamped_cols" counts
+ *   the columns moved.  The engine's own interior point (cut_algo = KTN_CUT_SUPPORTING) is searched again in the new box; the
+ *   caller's (ktn_set_interior_point) is kept as given.  Crossed bounds l_j > u_j are accepted: the next ktn_optimize[_begin]
+ *   screens every LP row k against the new box once --
+ *     amin_k = sum_e (v_e > 0 ? v_e l_c : v_e < 0 ? v_e u_c : 0),  amax_k mirrored (a zero coefficient contributes 0, an infinite
+ *     term makes the value -inf / +inf),  S_k = sum_e of the larger finite one of the entry's two absolute terms,
+ *     tau_k(b) = lp_tol_floor f_tol + (len_k + 2) 2^-52 (S_k + |b|);   row k proves the box infeasible when
+ *     amin_k - hi_k > tau_k(hi_k)  or  lo_k - amax_k > tau_k(lo_k)
+ *   -- and a proving row or a crossed column ends the solve with status :Infeasible before any LP is solved.  Stats:
+ *   "screen_runs", "screen_infeasible_rows", "screen_first_row" (smallest proving row, or -1), "screen_crossed_cols",
+ *   "screen_redundant_rows" (amax_k <= hi_k and amin_k >= lo_k; counted, not removed), "warm_solves".
+ * ktn_set_linear_objective: c[n] dense, n == num_var, and the constant c0.  Accepted when the loaded objective was declared
+ *   linear and is a KTN_ROW_SEP row of KTN_ATOM_LIN atoms or a KTN_ROW_QUAD row (whose Q is then empty); any other objective is
+ *   KTN_E_UNSUPPORTED.  A non-zero (or NaN) c_j on a column outside the objective row's structure is KTN_E_INVALID.  The LP's
+ *   cost, the constant and the objective row of the device NLP are rewritten: the KKT report, the objective certificate and
+ *   f(x_feas) evaluate the new objective.
+ * ktn_lp_row_activity: amin[M], amax[M] (M = ktn_lp_num_rows; m < M is KTN_E_INVALID) of the current rows over the current
+ *   bounds, at any time; stats "activity_infeasible_rows", "activity_first_row", "activity_redundant_rows" hold what the screen
+ *   would count. */
+int ktn_set_var_bounds(ktn_handle h, const double* l, const double* u, int64_t n);
+int ktn_set_linear_objective(ktn_handle h, const double* c, int64_t n, double c0);
+int ktn_lp_row_activity(ktn_handle h, double* amin, double* amax, int64_t m);
+
 /* MathProgBase.status / getobjval / getsolution / getsolvetime  src/model.jl:337-343;
  * numiters / numcuts src/model.jl:326,333; setwarmstart! (a no-op) :335 */
 int     ktn_get_status(ktn_handle h);

@@ -72,6 +72,9 @@ PROTOTYPES = {
     "ktn_ecp_step": (c_i32, [C.c_void_p, P(c_i32)]),
     "ktn_optimize_end": (c_i32, [C.c_void_p]),
     "ktn_reset": (c_i32, [C.c_void_p]),
+    "ktn_set_var_bounds": (c_i32, [C.c_void_p, P(c_f64), P(c_f64), c_i64]),
+    "ktn_set_linear_objective": (c_i32, [C.c_void_p, P(c_f64), c_i64, c_f64]),
+    "ktn_lp_row_activity": (c_i32, [C.c_void_p, P(c_f64), P(c_f64), c_i64]),
     "ktn_get_status": (c_i32, [C.c_void_p]),
     "ktn_get_objval": (c_f64, [C.c_void_p]),
     "ktn_get_num_var": (c_i64, [C.c_void_p]),

@@ -102,7 +102,8 @@ class FusedBatch:
         import numpy as np
         from .instances import fuse_instances
         self.instances = instances
-        if not _all_instances(instances):                          # Problems / Models, tape and QUAD rows allowed (nlp.fuse_problems)
+        self._bounds = None                                         # (set_var_bounds: the fused bounds in force, once they differ from the loaded ones)
+        if not _all_instances(instances):                         # Problems / Models, tape and QUAD rows allowed (nlp.fuse_problems)
             probs = [_as_problem(i) for i in instances]
             self.big, self.offs, self._objinfo = fuse_problems(probs, allow_quad=True)
             self._nvar = [int(p.num_var) for p in probs]            # (a quadratic objective adds its epigraph variable behind them)
@@ -133,6 +134,77 @@ class FusedBatch:
         xi = fuse_points(points, self.offs, self._nvar if self._objinfo is not None else None)
         self.m.set_interior_point(xi)
         return xi
+
+    # ---- new bounds or costs on the loaded batch (ktn_set_var_bounds / ktn_set_linear_objective) ----
+    def _own_nvar(self):
+        return self._nvar if self._objinfo is not None else [int(self.offs[k + 1] - self.offs[k]) for k in range(len(self.instances))]
+
+    def set_var_bounds(self, l_list, u_list):
+        """New variable bounds per instance, each vector in the instance's own variables; None (for a side, or for one instance
+        of a side) keeps what is loaded.  The vectors are concatenated in the fused column order and set in place; the next
+        solve() runs every instance with them.  Where fusion gave an instance an epigraph variable (a quadratic objective), its
+        interval [-R, R] is worked out again for the new box (nlp.quad_objective_bound)."""
+        import numpy as np
+        from .nlp import quad_objective_bound
+        nv, offs = self._own_nvar(), self.offs
+        cur = [np.array(self.big.l_var, dtype=np.float64).reshape(-1), np.array(self.big.u_var, dtype=np.float64).reshape(-1)]
+        if getattr(self, "_bounds", None) is not None:
+            cur = [self._bounds[0].copy(), self._bounds[1].copy()]
+        touched = set()
+        for side, lst in enumerate((l_list, u_list)):
+            if lst is None:
+                continue
+            if len(lst) != len(self.instances):
+                raise ValueError("one bound vector per instance: %d for %d instances" % (len(lst), len(self.instances)))
+            for k, v in enumerate(lst):
+                if v is None:
+                    continue
+                v = np.asarray(v, dtype=np.float64).reshape(-1)
+                if len(v) != int(nv[k]):
+                    raise ValueError("instance %d has %d variables, its bound vector %d entries" % (k, int(nv[k]), len(v)))
+                cur[side][int(offs[k]):int(offs[k]) + int(nv[k])] = v
+                touched.add(k)
+        for k in sorted(touched):
+            o, n_k = int(offs[k]), int(nv[k])
+            if self._objinfo is not None and int(offs[k + 1]) - o > n_k:          # the instance's own epigraph variable
+                R = quad_objective_bound(_as_problem(self.instances[k]).d, cur[0][o:o + n_k], cur[1][o:o + n_k], k)
+                cur[0][o + n_k], cur[1][o + n_k] = -R, R
+        self.m.setvarbounds(cur[0], cur[1])
+        self._bounds = cur
+        return cur
+
+    def set_costs(self, c_list):
+        """New linear cost vectors per instance, each dense over the instance's own variables and in its own sense (None keeps an
+        instance's cost); constants stay.  The fused objective is separable of linear atoms, so the engine's cost setter applies;
+        an instance whose quadratic objective became an epigraph row at fusion keeps its objective (ValueError)."""
+        import numpy as np
+        nv, offs, m = self._own_nvar(), self.offs, self.m
+        if len(c_list) != len(self.instances):
+            raise ValueError("one cost vector per instance: %d for %d instances" % (len(c_list), len(self.instances)))
+        c, c0 = m.lp_objective()
+        c = np.array(c[:int(offs[-1])], dtype=np.float64)
+        own = {}
+        for k, ck in enumerate(c_list):
+            if ck is None:
+                continue
+            ck = np.asarray(ck, dtype=np.float64).reshape(-1)
+            o, n_k = int(offs[k]), int(nv[k])
+            if len(ck) != n_k:
+                raise ValueError("instance %d has %d variables, its cost vector %d entries" % (k, n_k, len(ck)))
+            if int(offs[k + 1]) - o > n_k:
+                raise ValueError("instance %d: its quadratic objective is an epigraph row of the fused problem, not a cost vector" % k)
+            sgn = -1.0 if (self._objinfo is not None and _as_problem(self.instances[k]).sense == "Max") else 1.0
+            c[o:o + n_k] = sgn * ck
+            own[k] = ck
+        m.setobj(c, c0)
+        if self._objinfo is not None:
+            for k, ck in own.items():
+                cols, _, c0k = self._objinfo[k]
+                self._objinfo[k] = (cols, ck[cols].copy(), c0k)
+        else:
+            kind, _, p1, col = self._obj
+            self._obj = (kind, c[col], p1, col)
+        return c
 
     def solve(self, cut_capacity=0, supporting=None):
         """cut_capacity: cuts per NL row an instance's arena has room for in the device-side loop (0: the engine's default, 12);

@@ -106,6 +106,30 @@ int ktn_optimize(ktn_handle h) {
 
 int ktn_reset(ktn_handle h) { KTN_TRY(h, { KTN_REQUIRE(h->eng->loaded, "reset before loadproblem"); h->eng->reset(); return KTN_OK; }) }
 
+// ---- re-solve from the kept cut pool (Engine::set_var_bounds / set_linear_objective / row_activity, rebound.hip)
+int ktn_set_var_bounds(ktn_handle h, const double* l, const double* u, int64_t n) {
+    KTN_TRY(h, { h->eng->set_var_bounds(l, u, n); return KTN_OK; })
+}
+int ktn_set_linear_objective(ktn_handle h, const double* c, int64_t n, double c0) {
+    KTN_TRY(h, { h->eng->set_linear_objective(c, n, c0); return KTN_OK; })
+}
+int ktn_lp_row_activity(ktn_handle h, double* amin, double* amax, int64_t m) {
+    KTN_TRY(h, {
+        Engine* e = h->eng;
+        KTN_REQUIRE(e->loaded && amin && amax && m >= e->M, "ktn_lp_row_activity: buffers missing or shorter than ktn_lp_num_rows");
+        if (e->M == 0) return KTN_OK;
+        e->row_activity();
+        e->d_act_min.download(amin, (size_t)e->M, e->stream);
+        e->d_act_max.download(amax, (size_t)e->M, e->stream);
+        unsigned long long cnt[3] = {0ull, 0ull, 0ull};      // what the screen of the next begin() would count at these rows and bounds
+        e->d_act_cnt.download(cnt, 3, e->stream);
+        e->stats["activity_infeasible_rows"] = (double)cnt[0];
+        e->stats["activity_first_row"] = cnt[0] ? (double)cnt[1] : -1.0;
+        e->stats["activity_redundant_rows"] = (double)cnt[2];
+        return KTN_OK;
+    })
+}
+
 int ktn_get_status(ktn_handle h) { return (h && h->eng) ? h->eng->status : KTN_E_INVALID; }
 double ktn_get_objval(ktn_handle h) { return (h && h->eng) ? h->eng->objval : NAN; }
 int64_t ktn_get_num_var(ktn_handle h) { return (h && h->eng) ? h->eng->n_lp : -1; }
@@ -599,7 +623,7 @@ int ktn_optimize_blocks(ktn_handle h, int32_t cut_capacity) {
         KTN_REQUIRE(e->loaded && e->n_blocks > 0, "ktn_optimize_blocks: after ktn_loadproblem and ktn_set_blocks");
         if (e->esh_mode())
             throw ktn::Error(KTN_E_UNSUPPORTED, "ktn_optimize_blocks: not available with cut_algo = KTN_CUT_SUPPORTING");
-        if (e->M != e->M_base || e->iter != 0) e->reset();
+        if (e->M != e->M_base || e->iter != 0 || e->reopened) e->reset();
         if (e->optimize_blocks_device(cut_capacity > 0 ? cut_capacity : 12, 0) == Engine::kBlocksDone) return e->status;
         // an instance did not finish on the device (or the problem does not qualify): the ordinary loop, from the loaded state
         return ordinary_loop(e);
@@ -613,7 +637,7 @@ int ktn_optimize_blocks_ex(ktn_handle h, int32_t cut_capacity, int32_t flags) {
         KTN_REQUIRE((flags & ~(KTN_BLOCKS_SUPPORTING | KTN_BLOCKS_NO_FALLBACK)) == 0, "ktn_optimize_blocks_ex: unknown flag");
         if (e->esh_mode() && !(flags & KTN_BLOCKS_SUPPORTING))
             throw ktn::Error(KTN_E_UNSUPPORTED, "ktn_optimize_blocks_ex: cut_algo = KTN_CUT_SUPPORTING needs KTN_BLOCKS_SUPPORTING");
-        if (e->M != e->M_base || e->iter != 0) e->reset();
+        if (e->M != e->M_base || e->iter != 0 || e->reopened) e->reset();
         if (e->esh_mode() && !e->esh_ready) e->esh_prepare();          // x_int: the caller's, or the auxiliary problem of the fused batch
         const int r = e->optimize_blocks_device(cut_capacity > 0 ? cut_capacity : 12, flags);
         if (r == Engine::kBlocksDone) return e->status;

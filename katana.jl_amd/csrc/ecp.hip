@@ -258,6 +258,13 @@ void Engine::begin() {
     begun = true;
     lp_status = KTN_STATUS_OPTIMAL;
     if (status == KTN_STATUS_ERROR) return;
+    screened_out = false;
+    if (screen_pending) {      // once per ktn_set_var_bounds: the pool's rows against the new box (rebound.hip)
+        screen_pending = false;
+        screened_out = screen();
+        if (screened_out) { lp_status = KTN_STATUS_INFEASIBLE; status = KTN_STATUS_INFEASIBLE; return; }
+    }
+    if (reopened) stats["warm_solves"] += 1.0;
     if (esh_mode() && !esh_ready) esh_prepare();      // x_int, once per loaded problem (esh.hip)
     if (has_inf_bound) {       // presolve: resolve an initially-unbounded LP  model.jl:228-247
         int64_t i = 0;
@@ -287,7 +294,7 @@ void Engine::begin() {
 void Engine::step(int32_t* done) {
     KTN_REQUIRE(begun, "ktn_ecp_step before ktn_optimize_begin");
     *done = 1;
-    if (status == KTN_STATUS_ERROR || status == KTN_STATUS_UNBOUNDED) return;
+    if (status == KTN_STATUS_ERROR || status == KTN_STATUS_UNBOUNDED || screened_out) return;
     if (polishing) { polish_step(done); return; }
     if (allsat || iter >= prm.iter_cap) return;          // while !allsat && m.iter < iter_cap  model.jl:257
     iter += 1;

@@ -5,6 +5,7 @@
 //   lp.hip      the LP solves: scaling, tiled copies, PDHG steps and checks, exact small / mid-size LPs, per-block LPs, recession ray
 //   ecp.hip     the cutting-plane loop: begin / step / polish_step / end, objective certificate, device-side batch loop
 //   dist.hip    collectives of the row-sharded LP: RCCL, peer buffers, host callback
+//   rebound.hip the re-solve from the kept pool: bound and cost setters, reopen, the screen of the rows against a new box
 //   abi.hip     the C ABI of include/katana_hip.h
 // (until the middle of round 4 all of it was engine.hip, one translation unit of 4 100 lines).
 //
@@ -444,6 +445,7 @@ struct Engine {
         if (dist.comm) (void)ncclCommDestroy(dist.comm);
         ipc_release();
         for (auto e : ev_pool) (void)hipEventDestroy(e);
+        for (auto e : ev_screen) if (e) (void)hipEventDestroy(e);
         if (stream) (void)hipStreamDestroy(stream);
         if (h_chk) (void)hipHostFree(h_chk);
     }
@@ -659,6 +661,24 @@ struct Engine {
     void feas_run(bool blocks);
     void feas_compute() { feas_run(false); }
     void feas_blocks() { feas_run(true); }
+
+    // ================================================================ re-solve from the kept pool (rebound.hpp, rebound.hip) ===
+    // ktn_set_var_bounds / ktn_set_linear_objective change the box or the linear cost in place and re-open the run state; every
+    // row of the pool stays.  After a change of bounds the next begin() screens the pool once: a row whose smallest (largest)
+    // value over the new box lies beyond its upper (lower) bound, or a crossed column, ends the solve :Infeasible without an LP.
+    bool obj_settable = false;        // the loaded objective is a linear row the cost setter can rewrite (SEP of LIN atoms, or QUAD without Q)
+    bool screen_pending = false;      // bounds were set since the last begin()
+    bool screened_out = false;        // that begin()'s screen proved the box infeasible: step() reports done
+    bool reopened = false;            // a setter ran since the last reset(): ktn_optimize_blocks[_ex] starts from the loaded rows
+    int64_t crossed_cols = 0;         // columns with l_j > u_j at the last ktn_set_var_bounds
+    DBuf<double> d_act_min, d_act_max;
+    DBuf<unsigned long long> d_act_cnt;
+    hipEvent_t ev_screen[2] = {nullptr, nullptr};
+    void reopen();                    // reset() without the items that make up the pool
+    void set_var_bounds(const double* l, const double* u, int64_t n);
+    void set_linear_objective(const double* c, int64_t n, double c0_new);
+    void row_activity(hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);      // k_row_activity over the current rows and bounds, into d_act_*
+    bool screen();                    // true: the box is empty or contradicts a row
 
     // ================================================================ LP ============
     void rebuild_csc();

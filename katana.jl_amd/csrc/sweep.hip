@@ -501,6 +501,11 @@ void Engine::loadproblem(int64_t num_var, int64_t num_constr, const double* l_va
     }
     h_rowptr.push_back((int64_t)h_col.size());
     nnz_ext = (int64_t)h_col.size();
+    // what ktn_set_linear_objective can rewrite in place: a linear row of LIN atoms, or a QUAD row (obj_linear: its Q is empty)
+    obj_settable = obj_linear && (d->obj_kind == KTN_ROW_SEP || d->obj_kind == KTN_ROW_QUAD);
+    for (int64_t e = h_rowptr[(size_t)m0]; e < nnz_ext && d->obj_kind == KTN_ROW_SEP; ++e)
+        if (akind[(size_t)e] != KTN_ATOM_LIN) obj_settable = false;
+    screen_pending = false; crossed_cols = 0;
     for (int64_t i = 0; i < m0; ++i) {                   // atom_kind and p1 are ignored for QUAD rows
         if (h_rowkind[i] != KTN_ROW_QUAD) continue;
         for (int64_t e = h_rowptr[i]; e < h_rowptr[i + 1]; ++e) { akind[(size_t)e] = 0; p1[(size_t)e] = 0.0; }
@@ -990,6 +995,7 @@ void Engine::reset() {
     log_cuts_lastprnt = 0; log_max_viol = 0; purged_total = 0;
     polishing = false; polish_done = false; polish_count = 0; best_viol = kInf; best_obj = 0.0; cert_target = 0.0;
     lp_sols.clear();
+    screened_out = false; reopened = false;
     sync();
 }
 

@@ -21,6 +21,7 @@ import ..KatanaSolver, ..AbstractKatanaSeparator, ..EpigraphNLPEvaluator        
 import ..initialize!, ..precompute!, ..gencut, ..isconstrsat                      # the separator API, src/separators.jl:23-53
 
 export KatanaHipSeparator, supporting_hyperplane_cut, supporting_hyperplane_quad_cut, feasible_point, blocks_feasible_points
+export setvarbounds!, lp_row_activity
 
 const LIB = get(ENV, "KATANA_HIP_LIB", joinpath(dirname(@__FILE__), "..", "libkatana_hip.so"))
 
@@ -397,6 +398,29 @@ function blocks_feasible_points(m::KatanaHipModel)
     check(m, ccall((:ktn_blocks_get_feasible_points, LIB), Cint, (Ptr{Void}, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Int64, Ref{Int64}),
                    m.handle, x, length(x), info, length(info), cnt))
     x[1:m.num_var], reshape(info[1:cnt[]], KTN_FEAS_INFO_LEN, :)
+end
+# Re-solve from the kept cut pool (include/katana_hip.h; DESIGN.md section 14): new variable bounds or a new linear cost in place.
+# The cuts, their multipliers and the point stay; the next optimize! runs the ordinary loop from them.  Crossed bounds are accepted
+# and end that solve :Infeasible through the screen of the rows against the new box.  `nothing` keeps a side.
+function setvarbounds!(m::KatanaHipModel, l, u)
+    (l === nothing || length(l) == m.num_var) && (u === nothing || length(u) == m.num_var) || error("setvarbounds!: one bound per variable")
+    lv = l === nothing ? C_NULL : convert(Vector{Float64}, l)       # (the arrays themselves go to ccall, which keeps them rooted)
+    uv = u === nothing ? C_NULL : convert(Vector{Float64}, u)
+    check(m, ccall((:ktn_set_var_bounds, LIB), Cint, (Ptr{Void}, Ptr{Cdouble}, Ptr{Cdouble}, Int64), m.handle, lv, uv, m.num_var))
+end
+MathProgBase.setvarLB!(m::KatanaHipModel, l) = setvarbounds!(m, l, nothing)
+MathProgBase.setvarUB!(m::KatanaHipModel, u) = setvarbounds!(m, nothing, u)
+# (a loaded objective that is linear: separable of linear atoms or a quadratic row without Q; the constant is kept at 0)
+function MathProgBase.setobj!(m::KatanaHipModel, c)
+    length(c) == m.num_var || error("setobj!: one coefficient per variable")
+    check(m, ccall((:ktn_set_linear_objective, LIB), Cint, (Ptr{Void}, Ptr{Cdouble}, Int64, Cdouble), m.handle, convert(Vector{Float64}, c), m.num_var, 0.0))
+end
+# (amin, amax): the smallest and the largest value of every LP row over the current variable bounds
+function lp_row_activity(m::KatanaHipModel)
+    rows = ccall((:ktn_lp_num_rows, LIB), Int64, (Ptr{Void},), m.handle)
+    amin, amax = zeros(Float64, max(rows, 1)), zeros(Float64, max(rows, 1))
+    check(m, ccall((:ktn_lp_row_activity, LIB), Cint, (Ptr{Void}, Ptr{Cdouble}, Ptr{Cdouble}, Int64), m.handle, amin, amax, rows))
+    amin[1:rows], amax[1:rows]
 end
 MathProgBase.getsolvetime(m::KatanaHipModel) = ccall((:ktn_get_solvetime, LIB), Cdouble, (Ptr{Void},), m.handle)
 MathProgBase.setwarmstart!(m::KatanaHipModel, x) = fill(0.0, length(x))                      # src/model.jl:335

@@ -159,6 +159,39 @@ class KatanaNonlinearModel:
     def reset(self):
         L.check(self._h, self._lib.ktn_reset(self._h))
 
+    # ---- re-solve from the kept cut pool (MathProgBase.setvarLB! / setvarUB! / setobj!) ----------------
+    def setvarbounds(self, l, u):
+        """New variable bounds in place (None keeps that side); the cuts, their multipliers and x stay, the next optimize()
+        runs from them.  Crossed bounds are accepted and end that solve "Infeasible" through the screen."""
+        l = None if l is None else _f64(l)
+        u = None if u is None else _f64(u)
+        for v in (l, u):
+            if v is not None and len(v) != self._n0:
+                raise ValueError("setvarbounds: %d entries for %d variables" % (len(v), self._n0))
+        null = C.POINTER(C.c_double)()
+        L.check(self._h, self._lib.ktn_set_var_bounds(self._h, null if l is None else _p(l), null if u is None else _p(u), self._n0))
+
+    def setvarLB(self, l):
+        self.setvarbounds(l, None)
+
+    def setvarUB(self, u):
+        self.setvarbounds(None, u)
+
+    def setobj(self, c, c0=0.0):
+        """A new linear cost c'x + c0 in place, for a loaded objective that is linear (separable of linear atoms, or a QuadNLP
+        without obj_Q); non-zeros must stay inside the loaded objective's pattern."""
+        c = _f64(c)
+        if len(c) != self._n0:
+            raise ValueError("setobj: %d entries for %d variables" % (len(c), self._n0))
+        L.check(self._h, self._lib.ktn_set_linear_objective(self._h, _p(c), self._n0, float(c0)))
+
+    def lp_row_activity(self):
+        """(amin, amax): the smallest and largest value of every LP row over the current variable bounds."""
+        m = int(self._lib.ktn_lp_num_rows(self._h))
+        amin, amax = np.zeros(max(m, 1)), np.zeros(max(m, 1))
+        L.check(self._h, self._lib.ktn_lp_row_activity(self._h, _p(amin), _p(amax), m))
+        return amin[:m], amax[:m]
+
     # ---- getters  src/model.jl:326-343 ---------------------------------------------------
     def status(self):
         return STATUS_SYMBOLS[self._lib.ktn_get_status(self._h)]
@@ -637,6 +670,48 @@ class LinearQuadraticModel(KatanaNonlinearModel):
         self._xint_pending = x
         if not q["dirty"]:                               # already loaded and unchanged since: the engine can take it now
             super().set_interior_point(x)
+
+    # the 7-argument path keeps the problem on this object: a change before the load (or while it is dirty) goes into it alone,
+    # a change after the load also goes to the engine, which keeps its cuts (setobj: as long as the new cost's non-zeros lie where
+    # the loaded cost's did; otherwise the LP is loaded again at the next optimize())
+    def setvarbounds(self, l, u):
+        q = self._lq
+        if q is None:
+            return super().setvarbounds(l, u)
+        l = None if l is None else _f64(l).copy()
+        u = None if u is None else _f64(u).copy()
+        for v in (l, u):
+            if v is not None and len(v) != q["n"]:
+                raise ValueError("setvarbounds: %d entries for %d variables" % (len(v), q["n"]))
+        if not q["dirty"]:
+            super().setvarbounds(l, u)
+        if l is not None:
+            q["collb"] = l
+        if u is not None:
+            q["colub"] = u
+
+    def setobj(self, c, c0=0.0):
+        q = self._lq
+        if q is None:
+            return super().setobj(c, c0)
+        c = _f64(c).copy()
+        if len(c) != q["n"]:
+            raise ValueError("setobj: %d entries for %d variables" % (len(c), q["n"]))
+        if c0 != 0.0:
+            raise ValueError("setobj: the 7-argument loadproblem has no objective constant")
+        if np.any(np.isnan(c)):
+            raise ValueError("setobj: a coefficient is NaN")
+        if not q["dirty"]:
+            # The engine keeps the loaded cost's sparsity pattern (QuadNLP stores the non-zeros of obj) and refuses a non-zero
+            # outside it.  This object holds the whole LP, so such a cost is not an error here: the problem is marked for a
+            # re-load, and the next optimize() solves it cold with the new cost.
+            try:
+                super().setobj(c, 0.0)
+            except L.KatanaHipError as e:
+                if e.code != L.E_INVALID:
+                    raise
+                q["dirty"] = True
+        q["obj"] = c
 
     def _need_lq(self):
         if self._lq is None:
