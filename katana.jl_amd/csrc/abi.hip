@@ -14,6 +14,7 @@ struct ktn_handle_s {
 
 #define KTN_TRY(h, ...)                                                      \
     if (!(h) || !(h)->eng) return KTN_E_INVALID;                             \
+    ktn::PoisonScope poison_scope__(&(h)->eng->poison);                      \
     try {                                                                    \
         __VA_ARGS__                                                          \
     } catch (const ktn::Error& e) {                                          \
@@ -426,6 +427,7 @@ int ktn_get_lp_sol(ktn_handle h, int64_t k, double* x_out, int64_t n) {
 
 double ktn_get_stat(ktn_handle h, const char* name) {
     if (!h || !h->eng || !name) return NAN;
+    if (!std::strcmp(name, "poison_fills")) return (double)h->eng->poison.fills;      // (KTN_POISON, common.hpp)
     auto it = h->eng->stats.find(name);
     return it == h->eng->stats.end() ? 0.0 : it->second;
 }

@@ -8,6 +8,7 @@
 #include <utility>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/katana_hip.h"
@@ -34,6 +35,39 @@ struct Error : public std::runtime_error {
         if (!(cond)) throw ::ktn::Error(KTN_E_INVALID, (msg));   \
     } while (0)
 
+// KTN_POISON (development switch, DevParams in engine.hpp; DESIGN.md "Reproducibility"): every NEW allocation of DBuf::reserve is
+// filled over its whole capacity before the old contents are copied in, so that a kernel that reads an element nobody wrote reads
+// the same thing in every run -- and, under `nan`, something that shows in the numbers.  mode 1 (`zero`): all bytes 0.  mode 2
+// (`nan`): buffers of floating-point element type get a quiet NaN in every element (all bytes 0xFF is one, for float and for
+// double), buffers of EVERY integer element type -- and of structs, which may hold indices -- get 0.  Integer buffers are never
+// filled with anything but 0, under either value: an uninitialised index must not become an out-of-range address.  The switch
+// exists to turn a silent wrong read into a changed number, never to make anything fault.
+// The state belongs to a handle; the ABI layer names the handle whose call is running on this thread (PoisonScope), because a
+// DBuf does not know its engine.  Unset: no state is named or its mode is 0, and reserve() makes the calls it always made.
+// The limit of that: an allocation made while no scope is open -- an entry point of the C ABI that does not go through KTN_TRY,
+// a thread of the caller's that the engine did not enter through the ABI -- is not filled and raises no error, and
+// `poison_fills > 0` does not notice a partial miss.  Every entry point that allocates goes through KTN_TRY today.
+struct PoisonState {
+    int mode = 0;         // 0 off, 1 zero, 2 nan
+    int64_t fills = 0;    // allocations filled (stat "poison_fills")
+};
+inline PoisonState*& poison_current() {
+    static thread_local PoisonState* cur = nullptr;
+    return cur;
+}
+struct PoisonScope {
+    PoisonState* prev;
+    explicit PoisonScope(PoisonState* p) : prev(poison_current()) { poison_current() = p; }
+    ~PoisonScope() { poison_current() = prev; }
+    PoisonScope(const PoisonScope&) = delete;
+    PoisonScope& operator=(const PoisonScope&) = delete;
+};
+template <typename T> struct poison_float : std::false_type {};
+template <> struct poison_float<float> : std::true_type {};
+template <> struct poison_float<double> : std::true_type {};
+template <> struct poison_float<float2> : std::true_type {};
+template <> struct poison_float<double2> : std::true_type {};
+
 // Growable device array.  resize() keeps the first min(old,new) elements.
 template <typename T>
 struct DBuf {
@@ -57,6 +91,12 @@ struct DBuf {
         while (ncap < want) ncap += ncap / 2 + 256;
         T* q = nullptr;
         KTN_HIP(hipMalloc(&q, ncap * sizeof(T)));
+        if (PoisonState* ps = poison_current(); ps && ps->mode) {
+            const hipError_t e = hipMemsetAsync(q, (ps->mode == 2 && poison_float<T>::value) ? 0xFF : 0, ncap * sizeof(T), s);
+            if (e != hipSuccess) (void)hipFree(q);
+            KTN_HIP(e);
+            ++ps->fills;
+        }
         if (p && n) KTN_HIP(hipMemcpyAsync(q, p, n * sizeof(T), hipMemcpyDeviceToDevice, s));
         if (p) {
             KTN_HIP(hipStreamSynchronize(s));

@@ -326,7 +326,18 @@ static __global__ __launch_bounds__(256) void k_dense_lp(DenseLpIO P) {
             P.x[t] = xs[t];
             P.W[t] = Ws[t];
             const int k = Ws[t];
-            if (k >= 0) P.y[k >> 1] = (k & 1) ? fmax(lam[t], 0.0) : -fmax(lam[t], 0.0);
+            if (k >= 0) {
+                // a row held at two positions of the working set (mid_lp.hpp, mid_row_owner): the first position stores the signed
+                // sum, in position order -- never two stores to one row
+                bool first = true;
+                for (int a = 0; a < t; ++a) first = first && !(Ws[a] >= 0 && (Ws[a] >> 1) == (k >> 1));
+                if (first) {
+                    double tot = (k & 1) ? fmax(lam[t], 0.0) : -fmax(lam[t], 0.0);
+                    for (int a = t + 1; a < n; ++a)
+                        if (Ws[a] >= 0 && (Ws[a] >> 1) == (k >> 1)) tot += (Ws[a] & 1) ? fmax(lam[a], 0.0) : -fmax(lam[a], 0.0);
+                    P.y[k >> 1] = tot;
+                }
+            }
         }
         if (t == 0) {
             double obj = 0.0;

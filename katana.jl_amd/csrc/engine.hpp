@@ -95,6 +95,8 @@ struct DevParams {
     int kkt_group = 0;             // KTN_KKT_GROUP        lanes per column of k_lagr_grad (0 = by mean column length)
     int feas_group = 0;            // KTN_FEAS_GROUP       lanes per row of k_feas_sep and k_feas_quad (0 = those of the sweep / of k_quad_stats)
     bool feas_xstar_pre = false;   // KTN_FEAS_XSTAR_PRECOMPUTE   the feasible point takes x* from the last ktn_sep_precompute instead of lp_x (tests)
+    int poison = 0;                // KTN_POISON           fill every new device allocation (common.hpp): 0 unset, 1 `zero`, 2 `nan` (floating-point
+                                   //                      buffers NaN, integer buffers 0), -1 a value that is neither (ktn_create refuses it)
     static bool flag(const char* k) { return std::getenv(k) != nullptr; }
     static int geti(const char* k, int d) { const char* v = std::getenv(k); return v ? std::atoi(v) : d; }
     static double getd(const char* k, double d) { const char* v = std::getenv(k); return v ? std::atof(v) : d; }
@@ -119,6 +121,7 @@ struct DevParams {
         mid_refactor = geti("KTN_MID_REFACTOR", mid_refactor); raw_duals = flag("KTN_RAW_DUALS");
         kkt_group = geti("KTN_KKT_GROUP", kkt_group); feas_group = geti("KTN_FEAS_GROUP", feas_group);
         feas_xstar_pre = flag("KTN_FEAS_XSTAR_PRECOMPUTE");
+        if (const char* v = std::getenv("KTN_POISON"); v && *v) poison = !std::strcmp(v, "zero") ? 1 : !std::strcmp(v, "nan") ? 2 : -1;
     }
 };
 
@@ -410,8 +413,14 @@ struct Engine {
     std::vector<EvRec> ev_recs;
     size_t ev_used = 0;
 
-    explicit Engine(const ktn_params& p) : prm(p) {
+    PoisonState poison;            // KTN_POISON of this handle and its count of fills; named by the ABI layer around every call (KTN_TRY)
+    // parent: the engine that makes this one for a sub-problem of its own (esh_find_interior); the fill mode is the parent's
+    explicit Engine(const ktn_params& p, const Engine* parent = nullptr) : prm(p) {
         dev.from_env();
+        if (parent) dev.poison = parent->dev.poison;
+        if (dev.poison < 0) throw Error(KTN_E_INVALID, "KTN_POISON must be `zero` or `nan`");
+        poison.mode = dev.poison;
+        PoisonScope poison_scope(&poison);
         if (prm.cut_algo != KTN_CUT_KELLEY && !esh_mode())
             throw Error(KTN_E_INVALID, "cut_algo must be KTN_CUT_KELLEY (0), KTN_CUT_SUPPORTING (1) or KTN_CUT_SUPPORTING_QUAD (2)");
         int ndev = 0;

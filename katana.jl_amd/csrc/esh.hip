@@ -113,7 +113,7 @@ void Engine::esh_find_interior() {
     bool ok = false;
     std::vector<double> xk((size_t)A.n, 0.0);
     try {
-        child = new Engine(cp);
+        child = new Engine(cp, this);
         ktn_nlp_desc dd{};
         dd.num_var = A.n; dd.num_constr = A.m;
         dd.rowptr = A.rowptr.data(); dd.col = A.col.data(); dd.row_kind = A.kind.data(); dd.row_linear = A.lin.data();

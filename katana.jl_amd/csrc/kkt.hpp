@@ -67,7 +67,7 @@ __device__ __forceinline__ double kkt_list_sum(const KktSrc& S, int64_t s) {
 template <bool ARENA>
 __global__ __launch_bounds__(kBlock) void k_row_duals(int64_t m0, const int32_t* __restrict__ rowmap, KktSrc S, double sgn,
                                                       int64_t epi_lo, int64_t epi_hi, int64_t epi_slot, double* __restrict__ epi,
-                                                      double* __restrict__ d) {
+                                                      const double* __restrict__ lb, const double* __restrict__ ub, double* __restrict__ clamped, double* __restrict__ d) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i == 0 && epi != nullptr && !ARENA) {
         double a = kkt_list_sum(S, epi_slot);
@@ -95,6 +95,19 @@ __global__ __launch_bounds__(kBlock) void k_row_duals(int64_t m0, const int32_t*
     } else {
         if (k >= 0) a = S.y[k];
         else a = kkt_list_sum(S, -1 - (int64_t)k);
+        // The residue of prox_y: yt = v + sigma clip(-v / sigma, lo, hi) is v + sigma (-v / sigma) on a slack row, zero up to a
+        // rounding error of either sign (1e-18 ... 1e-15 seen).  With the wrong sign it is a multiplier on a side the row does not
+        // have, and times that side's infinite bound it makes the dual bound minus infinity.  A row without that side has no
+        // such multiplier: the report gives 0.  (a is the Min-form multiplier, as dm in k_dual_terms; the arenas of the
+        // device-side loop keep theirs: their aggregation is compared bit for bit with ktn_blocks_get_duals.)
+        // Every magnitude is zeroed, so the rule could hide a real sign error of lp_y or of the lists: clamped[0] counts the
+        // entries (an integer sum: exact in any order) and clamped[1] keeps the largest |a| (the bits of a non-negative double
+        // order like the number), statistics kkt_clamped_duals / kkt_clamped_max, which the tests bound.
+        if ((a > 0.0 && !(lb[i] > -__builtin_inf())) || (a < 0.0 && !(ub[i] < __builtin_inf()))) {
+            atomicAdd(&clamped[0], 1.0);
+            atomicMax(reinterpret_cast<unsigned long long*>(&clamped[1]), (unsigned long long)__double_as_longlong(fabs(a)));
+            a = 0.0;
+        }
     }
     d[i] = sgn * a;
 }

@@ -732,6 +732,7 @@ bool Engine::lp_solve_mid(LpResult* R) {
         KTN_HIP(hipMemcpyAsync(&hs, md_st.p, sizeof(hs), hipMemcpyDeviceToHost, stream));
         check_launch();
         sync();
+        stats["mid_lp_dup_sides"] += (double)hs.dup_sides;      // positions of the working set that repeated a side (k_mid_final sums them)
         if (hs.art_left == 0 && big_bounds_hold()) {
             R->status = KTN_STATUS_OPTIMAL;
             R->iters = total_pivots;

@@ -49,6 +49,8 @@ struct MidState {            // device-resident control block of a solve
     int32_t art_left;        // (final) artificial sides still carrying a multiplier
     int32_t gj_p;            // refactorisation: pivot row of the current column
     int32_t gj_singular;     // ... a pivot below 1e-13 of the column's scale: the working set is (numerically) dependent
+    int32_t dup_sides;       // (final) positions of the working set that hold a row an earlier position holds (mid_row_owner)
+    int32_t pad_;
     double viol, excess, hq, up, theta, scale, obj, resid, gj_piv;
 };
 
@@ -116,7 +118,7 @@ static __global__ __launch_bounds__(256) void k_mid_init(MidLpIO P) {
         P.Binv[idx] = v;
     }
     if (idx == 0) {
-        P.st->status = 0; P.st->pivots = 0; P.st->degen_run = 0; P.st->art_left = 0; P.st->resid = 0.0; P.st->p = -1; P.st->gj_singular = 0; P.st->gj_p = 0;
+        P.st->status = 0; P.st->pivots = 0; P.st->degen_run = 0; P.st->art_left = 0; P.st->resid = 0.0; P.st->p = -1; P.st->gj_singular = 0; P.st->gj_p = 0; P.st->dup_sides = 0;
     }
 }
 
@@ -380,14 +382,38 @@ static __global__ __launch_bounds__(256) void k_mid_resid_norm(MidLpIO P, int re
     if (t == 0) { P.st->resid = sv[0]; if (rearm && P.st->status == 1) P.st->status = 0; }
 }
 
+// The working set can hold one row side at two positions (seen on cutting-plane LPs after runs of degenerate pivots: the side is
+// priced again while it is in W, and the ratio test lets another position with a zero multiplier leave).  The multiplier of the
+// ROW is then the sum over those positions -- stationarity c + sum_r lambda_r g_r = 0 sees only the sum -- and a scatter
+// y[row] = lambda_r from every position leaves whichever store lands last: the value changed from run to run.  So the FIRST position
+// that holds a side of a row owns the row: it adds the clamped multipliers of all positions that hold a side of that row, in position
+// order (a fixed order, no atomics on values), in the engine's convention -- + lower side, - upper side, so that the two sides of an
+// equality row at two positions are one signed sum as well -- and stores once.  Returns that sum and in *extra the number of later
+// positions (-1: position r is not the first, nothing to store).  O(n) reads of W per position, once per solve.
+__device__ __forceinline__ double mid_row_owner(const MidLpIO& P, int r, const double* __restrict__ mult, int* extra) {
+    const int k = P.W[r], row = k >> 1;
+    for (int a = 0; a < r; ++a) {
+        const int ka = P.W[a];
+        if (ka >= 0 && (ka >> 1) == row) { *extra = -1; return 0.0; }
+    }
+    double tot = (k & 1) ? fmax(mult[r], 0.0) : -fmax(mult[r], 0.0);
+    int cnt = 0;
+    for (int a = r + 1; a < P.n; ++a) {
+        const int ka = P.W[a];
+        if (ka >= 0 && (ka >> 1) == row) { tot += (ka & 1) ? fmax(mult[a], 0.0) : -fmax(mult[a], 0.0); ++cnt; }
+    }
+    *extra = cnt;
+    return tot;
+}
+
 // outputs: row multipliers in the engine's convention (> 0 lower side, < 0 upper side), objective, leftover artificial sides.
 // The multipliers are those of the perturbed cost the pivoting worked with: what the cutting-plane loop consumes (dual inheritance,
 // purge, certificate).  Those of the TRUE cost are computed only when ktn_lp_get_duals asks for them (k_mid_true_duals below).
 static __global__ __launch_bounds__(256) void k_mid_final(MidLpIO P, double* y) {
     __shared__ double sv[256];
-    __shared__ int s_art;
+    __shared__ int s_art, s_dup;
     const int t = threadIdx.x, n = P.n;
-    if (t == 0) s_art = 0;
+    if (t == 0) { s_art = 0; s_dup = 0; }
     __syncthreads();
     double cmax = 1.0;
     for (int j = t; j < n; j += 256) cmax = fmax(cmax, fabs(P.c[j]));
@@ -404,11 +430,15 @@ static __global__ __launch_bounds__(256) void k_mid_final(MidLpIO P, double* y) 
     for (int r = t; r < n; r += 256) {
         const int k = P.W[r];
         const double lm = fmax(P.lam[r], 0.0);
-        if (k >= 0) y[k >> 1] = (k & 1) ? lm : -lm;
-        else if (!(mid_bound_rhs(P, k) < __builtin_inf()) && lm > 1e-9 * cmax) atomicAdd(&s_art, 1);
+        if (k >= 0) {
+            int extra = 0;
+            const double tot = mid_row_owner(P, r, P.lam, &extra);
+            if (extra >= 0) y[k >> 1] = tot;
+            if (extra > 0) atomicAdd(&s_dup, extra);
+        } else if (!(mid_bound_rhs(P, k) < __builtin_inf()) && lm > 1e-9 * cmax) atomicAdd(&s_art, 1);
     }
     __syncthreads();
-    if (t == 0) { P.st->obj = sv[0]; P.st->art_left = s_art; }
+    if (t == 0) { P.st->obj = sv[0]; P.st->art_left = s_art; P.st->dup_sides = s_dup; }
 }
 
 // The row multipliers of the TRUE cost, after k_mid_lambda(P, 1) left -B^-T s c in uvec (yt zeroed by the caller).  Engine::
@@ -419,7 +449,10 @@ static __global__ __launch_bounds__(256) void k_mid_true_duals(MidLpIO P, double
     const int r = blockIdx.x * 256 + threadIdx.x;
     if (r >= P.n) return;
     const int k = P.W[r];
-    if (k >= 0) yt[k >> 1] = (k & 1) ? P.uvec[r] : -P.uvec[r];
+    if (k < 0) return;
+    int extra = 0;
+    const double tot = mid_row_owner(P, r, P.uvec, &extra);      // (a row held at two positions: k_mid_final)
+    if (extra >= 0) yt[k >> 1] = tot;
 }
 
 // ---- refactorisation: B^-1 afresh from the working set ----------------------------------------------------------------

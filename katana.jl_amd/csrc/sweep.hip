@@ -1096,17 +1096,18 @@ void Engine::kkt_compute() {
     d_kkt_out.resize(8, stream);
     // ---- 1. constraint duals
     KktSrc S{};
+    KTN_HIP(hipMemsetAsync(d_kkt_out.p + 4, 0, 2 * sizeof(double), stream));      // k_row_duals: entries zeroed on an infinite side, their largest
     const bool epi = !obj_linear && !kkt_arena;
     if (kkt_arena) {
         S.y = e_y.p; S.a_last = e_last.p; S.a_prev = e_prev.p; S.arena = d_ar.p;
         S.blk_lin = d_blklin.p; S.blk_nl = d_blknl.p; S.nb = (int64_t)h_ar_row0.size();
-        launch_n(k_row_duals<true>, m0, stream, m0, d_kkt_rowmap.p, S, sgn, (int64_t)0, (int64_t)0, (int64_t)-1, (double*)nullptr, d_kkt_d.p);
+        launch_n(k_row_duals<true>, m0, stream, m0, d_kkt_rowmap.p, S, sgn, (int64_t)0, (int64_t)0, (int64_t)-1, (double*)nullptr, (const double*)d_lb.p, (const double*)d_ub.p, (double*)nullptr, d_kkt_d.p);
     } else {
         // what ktn_lp_get_duals returns: the true-cost multipliers of an exact mid-size solve while they stand, lp_y otherwise
         S.y = (!dev.raw_duals && mid_true_duals(nullptr)) ? md_y.p : lp_y.p;
         S.heads = list_heads(); S.prev = d_cutprev.p; S.n_heads = list_count(); S.n_rows = M;
         launch_n(k_row_duals<false>, std::max<int64_t>(m0, 1), stream, m0, d_kkt_rowmap.p, S, sgn, M_lin, M_base, epi ? m_nl - 1 : (int64_t)-1,
-                 epi ? d_kkt_out.p + 2 : (double*)nullptr, d_kkt_d.p);
+                 epi ? d_kkt_out.p + 2 : (double*)nullptr, (const double*)d_lb.p, (const double*)d_ub.p, d_kkt_out.p + 4, d_kkt_d.p);
     }
     check_launch();
     // ---- 2. g and J of every row at x* = lp_x, into buffers of the report's own: what ktn_sep_* and the certificate read stays
@@ -1150,6 +1151,7 @@ void Engine::kkt_compute() {
     stats["kkt_evals"] += 1.0;
     stats["kkt_epi_dual"] = epi ? out[2] : std::numeric_limits<double>::quiet_NaN();
     stats["kkt_group"] = (double)G;
+    stats["kkt_clamped_duals"] = out[4]; stats["kkt_clamped_max"] = out[5];      // (0, 0 after a device launch of the batch loop: the arenas are not clamped)
     kkt_key_version = lp_version; kkt_key_solves = kkt_solves; kkt_cached = true;
 }
 

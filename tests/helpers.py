@@ -48,6 +48,17 @@ def hip_load_instance(ktn, inst, **solver_kw):
     return m
 
 
+def pool_arrays(m):
+    """the cut pool as a caller reads it: ((rowptr, col, val, lo, hi), duals, number of rows, number of cuts)"""
+    return m.lp_rows(), m.lp_duals(), m.lp_num_rows(), m.numcuts()
+
+
+def pool_bits(m):
+    """pool_arrays with every array as its bytes: two pools are equal bit for bit when these lists are"""
+    rows, duals, nrows, ncuts = pool_arrays(m)
+    return [a.tobytes() for a in rows] + [duals.tobytes(), nrows, ncuts]
+
+
 def planted_obj_bound(inst, f_tol=1e-6, lp_gap=1e-7):
     """Per-instance bound on |objective - planted optimum| at a point that meets the stop rule (src/model.jl:257,273).
     xhat is a KKT point with multipliers lambda_i (NL rows), mu_r (linear rows) and bound multipliers, so for the convex

@@ -13,7 +13,7 @@ import pytest
 
 import katana_jl_amd as ktn
 import kat_util
-from helpers import hip_load_instance, hip_model_from_kat, max_nl_violation, oracle_solve_instance, oracle_solve_kat
+from helpers import hip_load_instance, hip_model_from_kat, max_nl_violation, oracle_solve_instance, oracle_solve_kat, pool_bits
 from oracle.evaluators import SexprNLPEvaluator
 from test_gpu_quad_rows import lpqp_parts
 
@@ -115,10 +115,6 @@ def changes(x, l0, u0):
     out.append(("fixed", l, u))
     out.append(("original", l0.copy(), u0.copy()))
     return out
-
-
-def pool_bits(m):
-    return [a.tobytes() for a in m.lp_rows()] + [m.lp_duals().tobytes(), m.lp_num_rows(), m.numcuts()]
 
 
 def run_case(name):
