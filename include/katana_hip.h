@@ -305,7 +305,9 @@ int ktn_reset(ktn_handle h);
  * cut lists and ages, x and the LP's scaling, and re-open the run state as ktn_reset does: status :None, ktn_numiters 0, the
  * KKT report and the feasible point answer KTN_E_INVALID until the next solve.  ktn_optimize and ktn_optimize_begin /
  * ktn_ecp_step / ktn_optimize_end then run the ordinary loop from the kept pool; ktn_numcuts goes on counting the pool;
- * ktn_optimize_blocks[_ex] starts from the loaded rows, as always.  Both may be called after ktn_loadproblem, solved or not.
+ * ktn_optimize_blocks[_ex] starts from the loaded rows, as always -- unless ktn_optimize_blocks_ex is given KTN_BLOCKS_WARM: both
+ * setters keep the arenas, the records and the x of the last device launch, and that flag re-solves every instance from its own
+ * cuts (below, at ktn_optimize_blocks_ex).  Both may be called after ktn_loadproblem, solved or not.
  * KTN_E_INVALID on a handle whose status is :Error (ktn_reset or ktn_loadproblem first); KTN_E_UNSUPPORTED on a row-sharded
  * handle and on one with a transport or a cut exchange installed.
  *
@@ -625,11 +627,28 @@ int ktn_optimize_blocks(ktn_handle h, int32_t cut_capacity);
  *   KTN_BLOCKS_NO_FALLBACK  return after the device launch: the status is :Optimal only if every instance's is, otherwise the first
  *       other instance's status; ktn_get_solution returns the x the launch wrote; "ecp_blocks_fallbacks" does not count the call; a
  *       batch that does not qualify for the device loop returns KTN_E_UNSUPPORTED.
+ *   KTN_BLOCKS_WARM         re-solve the batch from the arenas of the last device launch on the loaded problem (DESIGN.md section 14
+ *       "In the device-side loop"): the per-instance LPs with their cuts, multipliers, cut lists and x are still resident, and
+ *       after ktn_set_var_bounds / ktn_set_linear_objective every cut is still valid.  Used when a previous device launch stands
+ *       (no ktn_reset, ktn_loadproblem, ktn_set_blocks or host fallback since) and cut_capacity is the one it ran with; nothing is
+ *       uploaded or resized then.  First k_blocks_rewarm (csrc/batch_warm.hpp, one workgroup per instance) does what
+ *       ktn_blocks_rewarm describes, then each instance starts by its state: 1 from its arena, the first LP at the tolerance its
+ *       last solve ended at; 2 ends :Infeasible without an LP (0 PDHG iterations), the others are not affected; 0 (the last
+ *       record was not :Optimal, or overflowed) from its linear rows, cold.  An instance the screen ends :Infeasible does NOT send
+ *       the batch to the ordinary loop, which could not help it: when such instances are the only ones not :Optimal the call
+ *       returns the first one's status, as under KTN_BLOCKS_NO_FALLBACK, and "ecp_blocks_fallbacks" does not move.  An instance that
+ *       overflows or runs out of LP iterations falls back as always (and the host loop then starts cold, warm state dropped).
+ *       Without a usable previous launch the call is the cold launch, bit for bit, and "ecp_blocks_warm_launches" does not move.
+ *       A Kelley launch after a supporting one reports lambda = 1 for every row; a supporting launch after a Kelley one has no
+ *       lambda for the kept rows and is the cold launch.  ktn_optimize[_begin] (the host loop) drops the warm state too.  Stats: "ecp_blocks_warm_launches" (cumulative); of the last k_blocks_rewarm
+ *       "ecp_blocks_warm_instances" (state 1), "ecp_blocks_warm_cold_instances" (state 0), "ecp_blocks_warm_infeasible" (state 2),
+ *       "ecp_blocks_warm_dropped_rows", "ecp_blocks_warm_clamped_cols", "ecp_blocks_rewarm_kernel_s" (the kernel's own time).
  * Stats: "esh_rows" "esh_fallback_rows" "esh_newton_steps" "esh_quad_rows" accumulate the instances' counters of a k_ecp_blocks<1>
  * launch; "ecp_blocks_esh_rows" rows moved by the last launch (0 after a Kelley launch).  ktn_last_sweep_lambdas keeps describing
  * the sweeps of the host-driven loop only: the lambdas of a device launch come from ktn_blocks_get_cuts. */
 #define KTN_BLOCKS_SUPPORTING  1   /* cut_algo 1 / 2 run inside the device loop (without it: refused, as ktn_optimize_blocks does) */
 #define KTN_BLOCKS_NO_FALLBACK 2   /* do not run the ordinary loop when the batch does not qualify or an instance does not end :Optimal */
+#define KTN_BLOCKS_WARM        (4) /* start every instance from the arena of the last device launch (cold where there is none) */
 int ktn_optimize_blocks_ex(ktn_handle h, int32_t cut_capacity, int32_t flags);
 /* The records of the last device launch on the loaded problem, [n_blocks x 8] doubles, instance after instance:
  *   0 status (KTN_STATUS_*)   1 cutting-plane iterations   2 objective (without the loaded problem's constant)
@@ -649,6 +668,22 @@ int ktn_blocks_get_cuts(ktn_handle h, int64_t block, int64_t* rowptr, int32_t* c
 /* The multiplier of each cut row of instance `block` after the last device launch, row for row as in ktn_blocks_get_cuts, unscaled
  * (the arenas keep the multipliers unscaled between LP solves: y = y^ dr).  y_out == NULL only reports *count. */
 int ktn_blocks_get_duals(ktn_handle h, int64_t block, double* y_out, int64_t cap, int64_t* count);
+/* What has to happen between two device launches on the same arenas, alone (k_blocks_rewarm, csrc/batch_warm.hpp; a warm
+ * ktn_optimize_blocks_ex runs it first).  Per instance, in this order: (a) warm only if its last record is :Optimal without
+ * overflow, else state 0 and nothing is touched; (b) a crossed column l_j > u_j: state 2; (c) its slice of x is clamped into the
+ * box; (d) every arena row, linear rows and cuts, is screened against the box by the test of ktn_set_var_bounds (amin_k, amax_k,
+ * S_k, tau_k, 4 lanes per row in a fixed order): a proving row gives state 2, redundant rows are counted; (e) only when the cut
+ * rows fill more than half of the cut room, M - m_lin > (cap_rows - m_lin) / 2, cut rows that are idle by the pool's rule
+ * (y == 0 and slack > purge_margin * max(1, |finite bounds|) at the clamped x; no ageing) are dropped, the survivors keep their
+ * order, multipliers and lambdas, and the cut lists are re-threaded over them (linear rows never move; a dropped row has y == 0, so
+ * every list's multiplier sum stands).  out: [n_blocks x 8] doubles, instance after instance:
+ *   0 state (0 cold, 1 warm, 2 infeasible)   1 LP rows   2 non-zeros   3 rows dropped   4 columns clamped
+ *   5 smallest proving row of the arena (-1: none)   6 crossed columns   7 redundant rows
+ * ktn_blocks_get_results / _get_cuts / _get_duals describe the compacted arenas afterwards (slot 6 of a record follows).  Idempotent:
+ * until the next setter or launch a second call returns the same records and moves nothing.  Size convention of
+ * ktn_blocks_get_results (out == NULL only reports *count = 8 n_blocks and runs nothing).  KTN_E_INVALID without a previous device
+ * launch on the loaded problem, or after ktn_reset, ktn_set_blocks or a host fallback. */
+int ktn_blocks_rewarm(ktn_handle h, double* out, int64_t cap, int64_t* count);
 /* The dual bound of ktn_get_dual_bound per instance of a fused batch (ktn_set_blocks; rows and columns grouped by instance):
  * out[2 b] = bound of instance b from its own rows, columns and share c_b'x_b of the objective (without the loaded problem's
  * constant), out[2 b + 1] = its gap.  One workgroup per instance.  States and errors as ktn_get_dual_bound; out == NULL only

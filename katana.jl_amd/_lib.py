@@ -13,6 +13,7 @@ ROW_SEP, ROW_TAPE, ROW_HOST, ROW_QUAD = 0, 1, 2, 3
 ATOM_LIN, ATOM_QUAD, ATOM_EXP, ATOM_NEGLOG = 0, 1, 2, 3
 CUT_KELLEY, CUT_SUPPORTING, CUT_SUPPORTING_QUAD = 0, 1, 2          # ktn_params.cut_algo
 BLOCKS_SUPPORTING, BLOCKS_NO_FALLBACK = 1, 2                       # ktn_optimize_blocks_ex flags
+BLOCKS_WARM = 4                                                    # ... start from the arenas of the last device launch
 FEAS_INFO_LEN = 8                                                  # KTN_FEAS_INFO_LEN (ktn_get_feasible_point)
 LPOP_STEP, LPOP_CHECK, LPOP_ADVANCE, LPOP_RESTART = range(4)      # ktn_lp_script ops
 LPS_IDENTITY, LPS_PACKED, LPS_NO_SPEC = 1, 2, 4                   # ktn_lp_script flags
@@ -133,6 +134,7 @@ PROTOTYPES = {
     "ktn_optimize_blocks": (c_i32, [C.c_void_p, c_i32]),
     "ktn_optimize_blocks_ex": (c_i32, [C.c_void_p, c_i32, c_i32]),
     "ktn_blocks_get_results": (c_i32, [C.c_void_p, P(c_f64), c_i64, P(c_i64)]),
+    "ktn_blocks_rewarm": (c_i32, [C.c_void_p, P(c_f64), c_i64, P(c_i64)]),
     "ktn_blocks_get_cuts": (c_i32, [C.c_void_p, c_i64, P(c_i64), P(c_i32), P(c_f64), P(c_f64), P(c_f64), P(c_i64), P(c_f64),
                                     c_i64, c_i64, P(c_i64), P(c_i64)]),
     "ktn_dist_unique_id": (c_i32, [C.c_char_p]),

@@ -206,21 +206,30 @@ class FusedBatch:
             self._obj = (kind, c[col], p1, col)
         return c
 
-    def solve(self, cut_capacity=0, supporting=None):
+    def solve(self, cut_capacity=0, supporting=None, warm=False, fallback=True):
         """cut_capacity: cuts per NL row an instance's arena has room for in the device-side loop (0: the engine's default, 12);
         an instance that outgrows it sends the batch to the host-driven loop (stat ecp_blocks_fallbacks).
         supporting: supporting-hyperplane cuts inside the device-side loop (ktn_optimize_blocks_ex, KTN_BLOCKS_SUPPORTING); None =
         on when the solver's cut_algo is not Kelley's and device_loop is set.  (m.last_sweep_lambdas() describes host-loop sweeps
-        only; the cuts of a device launch and their lambdas are m.blocks_cuts(k).)"""
+        only; the cuts of a device launch and their lambdas are m.blocks_cuts(k).)
+        warm: every instance starts from its own cuts, multipliers and x of the last device launch on this handle (KTN_BLOCKS_WARM;
+        after set_var_bounds / set_costs, or with unchanged data); the handle is NOT reset in between.  An instance whose new box is
+        empty ends "Infeasible" alone: the statuses per instance are column 0 of m.blocks_results(), the status returned is the
+        first that is not "Optimal".
+        fallback=False: KTN_BLOCKS_NO_FALLBACK."""
         import numpy as np
         from .instances import atom_value_deriv
         m, big, offs = self.m, self.big, self.offs
         if supporting is None:
             supporting = bool(self.device_loop) and int(m.params.cut_algo) != 0
-        if self._solved:
+        warm = bool(warm) and bool(self.device_loop)
+        if self._solved and not warm:
             m.reset()
         self._solved = True
-        status = m.optimize_blocks(cut_capacity, supporting=bool(supporting)) if self.device_loop else m.optimize()
+        if self.device_loop:
+            status = m.optimize_blocks(cut_capacity, supporting=bool(supporting), fallback=bool(fallback), warm=warm)
+        else:
+            status = m.optimize()
         x = m.getsolution()
         common = dict(status=status, iters=m.numiters(), numcuts=None, pdhg_iters=m.stat("pdhg_iters"),
                       blk_lp_launches=m.stat("blk_lp_launches"), blk_lp_fallbacks=m.stat("blk_lp_fallbacks"),

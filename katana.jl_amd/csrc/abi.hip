@@ -105,7 +105,7 @@ int ktn_optimize(ktn_handle h) {
     })
 }
 
-int ktn_reset(ktn_handle h) { KTN_TRY(h, { KTN_REQUIRE(h->eng->loaded, "reset before loadproblem"); h->eng->reset(); return KTN_OK; }) }
+int ktn_reset(ktn_handle h) { KTN_TRY(h, { KTN_REQUIRE(h->eng->loaded, "reset before loadproblem"); h->eng->blocks_drop_warm(); h->eng->reset(); return KTN_OK; }) }
 
 // ---- re-solve from the kept cut pool (Engine::set_var_bounds / set_linear_objective / row_activity, rebound.hip)
 int ktn_set_var_bounds(ktn_handle h, const double* l, const double* u, int64_t n) {
@@ -589,6 +589,7 @@ int ktn_set_blocks(ktn_handle h, int64_t nblocks, const int64_t* col_offsets) {
         Engine* e = h->eng;
         KTN_REQUIRE(e->loaded && nblocks >= 0, "ktn_set_blocks: after loadproblem");
         e->feas_blk_cached = false;
+        e->blocks_drop_warm();                    // (arenas laid out for other blocks are of no use to a warm launch)
         if (nblocks == 0) { e->n_blocks = 0; e->kkt_seg_ok = false; e->h_kkt_blk.clear(); return KTN_OK; }
         KTN_REQUIRE(col_offsets && e->obj_linear, "ktn_set_blocks: needs a linear objective (no shared epigraph variable)");
         KTN_REQUIRE(col_offsets[0] == 0 && col_offsets[nblocks] == e->n_lp, "ktn_set_blocks: offsets must cover the columns");
@@ -611,6 +612,7 @@ int ktn_set_blocks(ktn_handle h, int64_t nblocks, const int64_t* col_offsets) {
 
 // the ordinary loop from the loaded state (what a batch the device loop could not finish falls back to)
 static int ordinary_loop(Engine* e) {
+    e->blocks_drop_warm();                        // (x and the records are the host loop's from here on)
     e->reset();
     e->begin();
     int32_t done = (e->status == KTN_STATUS_ERROR || e->status == KTN_STATUS_UNBOUNDED) ? 1 : 0;
@@ -636,13 +638,18 @@ int ktn_optimize_blocks_ex(ktn_handle h, int32_t cut_capacity, int32_t flags) {
     KTN_TRY(h, {
         Engine* e = h->eng;
         KTN_REQUIRE(e->loaded && e->n_blocks > 0, "ktn_optimize_blocks_ex: after ktn_loadproblem and ktn_set_blocks");
-        KTN_REQUIRE((flags & ~(KTN_BLOCKS_SUPPORTING | KTN_BLOCKS_NO_FALLBACK)) == 0, "ktn_optimize_blocks_ex: unknown flag");
+        KTN_REQUIRE((flags & ~(KTN_BLOCKS_SUPPORTING | KTN_BLOCKS_NO_FALLBACK | KTN_BLOCKS_WARM)) == 0, "ktn_optimize_blocks_ex: unknown flag");
         if (e->esh_mode() && !(flags & KTN_BLOCKS_SUPPORTING))
             throw ktn::Error(KTN_E_UNSUPPORTED, "ktn_optimize_blocks_ex: cut_algo = KTN_CUT_SUPPORTING needs KTN_BLOCKS_SUPPORTING");
-        if (e->M != e->M_base || e->iter != 0 || e->reopened) e->reset();
+        // (a warm launch starts from the x of the last one -- clamped by a setter since, perhaps --: the reset leaves it alone)
+        e->reset_keeps_x = (flags & KTN_BLOCKS_WARM) != 0 && e->blocks_warm_ok && e->blocks_launched && e->M == e->M_base;
+        if (e->M != e->M_base || e->iter != 0 || e->reopened) {
+            try { e->reset(); } catch (...) { e->reset_keeps_x = false; throw; }
+        }
+        e->reset_keeps_x = false;
         if (e->esh_mode() && !e->esh_ready) e->esh_prepare();          // x_int: the caller's, or the auxiliary problem of the fused batch
         const int r = e->optimize_blocks_device(cut_capacity > 0 ? cut_capacity : 12, flags);
-        if (r == Engine::kBlocksDone) return e->status;
+        if (r == Engine::kBlocksDone || r == Engine::kBlocksScreened) return e->status;
         if (flags & KTN_BLOCKS_NO_FALLBACK) {
             if (r == Engine::kBlocksUnfit) throw ktn::Error(KTN_E_UNSUPPORTED, "ktn_optimize_blocks_ex: the batch does not qualify for the device-side loop");
             return e->status;                                         // the first instance's status that is not :Optimal
@@ -660,6 +667,20 @@ int ktn_blocks_get_results(ktn_handle h, double* out, int64_t cap, int64_t* coun
         if (out) {
             KTN_REQUIRE(cap >= *count, "ktn_blocks_get_results: buffer too small");
             std::memcpy(out, e->h_blkres.data(), e->h_blkres.size() * sizeof(double));
+        }
+        return KTN_OK;
+    })
+}
+int ktn_blocks_rewarm(ktn_handle h, double* out, int64_t cap, int64_t* count) {
+    KTN_TRY(h, {
+        Engine* e = h->eng;
+        KTN_REQUIRE(e->loaded && count && e->blocks_launched && e->blocks_warm_ok && e->n_blocks > 0,
+                    "ktn_blocks_rewarm: after a device launch of ktn_optimize_blocks[_ex] on the loaded problem (and no ktn_reset or host fallback since)");
+        *count = 8 * e->n_blocks;
+        if (out) {
+            KTN_REQUIRE(cap >= *count, "ktn_blocks_rewarm: buffer too small");
+            e->blocks_rewarm();
+            std::memcpy(out, e->h_rewarm.data(), e->h_rewarm.size() * sizeof(double));
         }
         return KTN_OK;
     })

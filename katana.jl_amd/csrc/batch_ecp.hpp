@@ -23,7 +23,16 @@
 // with sig == 0 or without a finite phi >= 0 below lambda = 1 stores exactly what ESH = 0 stores.  The switch is a template
 // parameter, not a field of EcpBatch: the kernel is sensitive to register allocation (see the note at the sweep), and
 // k_ecp_blocks<0> is the code and the kernel argument that were there before the switch existed.
+//
+// A trailing EcpWarm argument -- k_ecp_blocks<0, EcpWarm>(EcpBatch, EcpWarm), k_ecp_blocks<1, EcpEsh, EcpWarm>(EcpBatch, EcpEsh, EcpWarm);
+// ktn_optimize_blocks_ex with KTN_BLOCKS_WARM, DESIGN.md section 14 "In the device-side loop" -- is the WARM ENTRY: the arenas of the
+// last launch are still there, k_blocks_rewarm (batch_warm.hpp) has screened, clamped and compacted them, and per instance its record
+// says how to start: 1 from the arena's rows, multipliers, lists and x, with the first LP at the tolerance the last solve ended at;
+// 2 an :Infeasible record and nothing else; 0 the initial LP below, as ever.  Like ESH it is decided by the template arguments and
+// not by a field of EcpBatch, for the same reason: the cold instantiations <0> and <1, EcpEsh> keep their names, their kernel
+// arguments and their code.
 #pragma once
+#include <type_traits>
 #include "kernels.hpp"
 #include "pdhg_check.hpp"
 #include "quad_rows.hpp"
@@ -87,7 +96,14 @@ struct EcpEsh {
     double root_tol;                 // esh_root_tol: a search stops at 0 <= phi <= root_tol * (the sweep's f_tol)
     int iters;                       // esh_root_iters
 };
-__device__ __forceinline__ const EcpEsh& ecp_esh_arg(const EcpEsh& e) { return e; }
+// What the warm entry takes beside them: the records of k_blocks_rewarm (batch_warm.hpp)
+struct EcpWarm {
+    const double* rec;               // [nb * 8]: state (0 cold, 1 warm, 2 infeasible), M, NNZ, ...
+};
+template <class... Rest>
+__device__ __forceinline__ const EcpEsh& ecp_esh_arg(const EcpEsh& e, const Rest&...) { return e; }
+__device__ __forceinline__ const EcpWarm& ecp_warm_arg(const EcpWarm& w) { return w; }
+__device__ __forceinline__ const EcpWarm& ecp_warm_arg(const EcpEsh&, const EcpWarm& w) { return w; }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // sparse dot products of the block's outputs (rows or columns) with an LDS vector: out(o, acc) called by lane 0 of each
@@ -171,7 +187,9 @@ static __device__ __forceinline__ void ecp_quad_entries(const EcpBatch& B, int64
 // both into one struct changed the code of <0>: 40 bytes and three more SGPR spills; the empty pack leaves it as it was)
 template <int ESH, class... EshArg>
 __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B, EshArg... esh_arg) {
-    static_assert(sizeof...(EshArg) == (ESH != 0 ? 1 : 0), "k_ecp_blocks<0>(EcpBatch) or k_ecp_blocks<1, EcpEsh>(EcpBatch, EcpEsh)");
+    constexpr bool WARM = (std::is_same_v<EshArg, EcpWarm> || ...);
+    static_assert(sizeof...(EshArg) == (ESH != 0 ? 1 : 0) + (WARM ? 1 : 0),
+                  "k_ecp_blocks<0>(EcpBatch) or k_ecp_blocks<1, EcpEsh>(EcpBatch, EcpEsh), each with a trailing EcpWarm for the warm entry");
     extern __shared__ double sm[];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int64_t c0 = B.blk_col[b];
@@ -213,7 +231,9 @@ __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B, EshArg..
 
     // ================================================================ initial LP: the instance's linear rows =========
     int M = m_lin, NNZ = 0;
-    {
+    int wstate = 0;                    // (WARM) what k_blocks_rewarm decided for this instance
+    if constexpr (WARM) wstate = (int)ecp_warm_arg(esh_arg...).rec[(int64_t)b * 8];
+    if (!WARM || wstate == 0) {
         const int64_t e0 = B.lp_rowptr[lin0];
         NNZ = (int)(B.lp_rowptr[lin0 + m_lin] - e0);
         for (int r = tid; r <= m_lin; r += kEcpThreads) rptr[r] = (int32_t)(B.lp_rowptr[lin0 + r] - e0);
@@ -222,10 +242,29 @@ __global__ __launch_bounds__(kEcpThreads) void k_ecp_blocks(EcpBatch B, EshArg..
         for (int i = tid; i < m_nl; i += kEcpThreads) last_cut[i] = -1;
         for (int j = tid; j < nb; j += kEcpThreads) xg[j] = 0.0;
     }
+    [[maybe_unused]] double warm_maxviol = 1e300;
+    if constexpr (WARM) {
+        if (wstate == 2) {             // the new box is empty or a kept row excludes it: no LP (the arena stays as it is)
+            if (tid == 0) {
+                double* o = B.res + (int64_t)b * 8;
+                const double rows = o[6];
+                o[0] = (double)KTN_STATUS_INFEASIBLE; o[1] = 0.0; o[2] = __builtin_nan(""); o[3] = rows; o[4] = 0.0; o[5] = 1e300; o[6] = rows; o[7] = 0.0;
+            }
+            if constexpr (ESH != 0) { if (tid < 4) ecp_esh_arg(esh_arg...).res[(int64_t)b * 4 + tid] = 0.0; }
+            return;
+        }
+        if (wstate == 1) {             // the arena of the last launch: its rows, yv, last_cut, cut_prev and xg stand
+            M = (int)ecp_warm_arg(esh_arg...).rec[(int64_t)b * 8 + 1];
+            NNZ = rptr[M];
+            warm_maxviol = B.res[(int64_t)b * 8 + 5];      // (read by every lane long before lane 0 writes the new record)
+        }
+    }
     __syncthreads();
     int status = KTN_STATUS_NONE, iter = 0, numcuts = m_lin;
+    if constexpr (WARM) numcuts = M;
     long pdhg_total = 0;
     double last_maxviol = 1e300, objval = 0.0, om_keep = -1.0;
+    if constexpr (WARM) last_maxviol = warm_maxviol;
     bool allsat = false, overflow = false;
     // Objective certificate per instance (Engine::objective_certificate / kernels.hpp "objective certificate", round 4): at the
     // point that meets the reference's stop rule the workgroup adds up  D = sum_i lambda_i * (signed residual of NL row i)  with

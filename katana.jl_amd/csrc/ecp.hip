@@ -4,16 +4,58 @@
 #include "kernels.hpp"
 #include "batch_lp.hpp"
 #include "batch_ecp.hpp"
+#include "batch_warm.hpp"
 
 namespace ktn {
+
+// k_blocks_rewarm over the resident arenas (batch_warm.hpp): screen, clamp, compaction; the records into h_rewarm.  Runs once per
+// state of the data: a second call before the next setter or launch returns with h_rewarm as it is.
+void Engine::blocks_rewarm() {
+    if (blocks_rewarmed) return;
+    const int nb = (int)n_blocks;
+    e_rewarm.resize((size_t)nb * 8, stream);
+    WarmBatch W;
+    W.blk_col = d_blkcol.p; W.blk_lin = d_blklin.p; W.blk_nl = d_blknl.p; W.arena = d_ar.p;
+    W.rptr = e_rptr.p; W.rcol = e_rcol.p; W.rval = e_rval.p; W.lo = e_lo.p; W.hi = e_hi.p; W.y = e_y.p;
+    W.lam = blocks_last_esh ? e_lam.p : nullptr;
+    W.last_cut = e_last.p; W.cut_prev = e_prev.p;
+    W.crow = e_crow.p; W.cval = e_cval.p; W.dr = e_dr.p; W.loh = e_loh.p; W.hih = e_hih.p;
+    W.l = lp_l.p; W.u = lp_u.p; W.x = lp_x.p; W.res = e_res.p; W.out = e_rewarm.p;
+    W.tol0 = prm.lp_tol_floor * prm.f_tol; W.purge_margin = prm.purge_margin;
+    for (hipEvent_t& e : ev_rewarm)                      // the kernel's own begin / end timestamps ("ecp_blocks_rewarm_kernel_s")
+        if (!e) KTN_HIP(hipEventCreate(&e));
+    launch_ev(k_blocks_rewarm, (unsigned)nb, kEcpThreads, 0, stream, ev_rewarm[0], ev_rewarm[1], W);
+    check_launch();
+    h_rewarm = e_rewarm.to_host(stream);
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, ev_rewarm[0], ev_rewarm[1]) != hipSuccess) { (void)hipGetLastError(); ms = 0.f; }
+    stats["ecp_blocks_rewarm_kernel_s"] = (double)ms * 1e-3;
+    double cnt[3] = {0.0, 0.0, 0.0}, dropped = 0.0, clamped = 0.0;
+    for (int bb = 0; bb < nb; ++bb) {
+        const double* r = h_rewarm.data() + (size_t)bb * 8;
+        cnt[(int)r[0]] += 1.0; dropped += r[3]; clamped += r[4];
+        if ((int)r[0] == 1) h_blkres[(size_t)bb * 8 + 6] = r[1];       // (ktn_blocks_get_cuts / _duals read the compacted arena)
+    }
+    stats["ecp_blocks_warm_instances"] = cnt[1]; stats["ecp_blocks_warm_cold_instances"] = cnt[0]; stats["ecp_blocks_warm_infeasible"] = cnt[2];
+    stats["ecp_blocks_warm_dropped_rows"] = dropped; stats["ecp_blocks_warm_clamped_cols"] = clamped;
+    kkt_cached = false;                                  // (rows moved: the report is built again from the re-threaded lists)
+    blocks_rewarmed = true;
+}
 
 // Throughput mode, device-side loop (batch_ecp.hpp).  Returns kBlocksUnfit when the problem does not qualify (nothing launched),
 // kBlocksOpen when an instance could not finish (arena overflow, LP status) -- the caller then runs the ordinary loop, or with
 // KTN_BLOCKS_NO_FALLBACK reports the first such instance's status -- and kBlocksDone when every instance ended :Optimal.
 // KTN_BLOCKS_SUPPORTING with an interior point in hand launches k_ecp_blocks<1> (the root search inside the emit pass), everything
 // else k_ecp_blocks<0>.
+// KTN_BLOCKS_WARM with the arenas of the last device launch still standing (blocks_warm_ok, the same cap_mul): nothing is uploaded
+// or resized, k_blocks_rewarm screens, clamps and compacts every arena, and the instantiation with the trailing EcpWarm starts each
+// instance from what is left (batch_warm.hpp).  Instances the screen ends :Infeasible do not send the batch to the host loop, which
+// could not help them: when they are the only ones not :Optimal the return is kBlocksScreened, status the first of them.  Without
+// such a previous launch the flag changes nothing: the cold launch, and "ecp_blocks_warm_launches" does not move.
 int Engine::optimize_blocks_device(int cap_mul, int flags) {
     const bool keep = (flags & KTN_BLOCKS_NO_FALLBACK) != 0;
+    const bool want_warm = (flags & KTN_BLOCKS_WARM) != 0 && blocks_warm_ok && blocks_launched && cap_mul == blocks_cap_mul &&
+                      (int64_t)h_ar_rows.size() == n_blocks;
     const bool esh = (flags & KTN_BLOCKS_SUPPORTING) != 0 && esh_mode() && xint_found != 0;
     // (rows: separable, tape or QUAD, linear or not; k_ecp_blocks evaluates tape rows with the interpreter of k_tape_eval and QUAD
     //  rows with the two passes of quad_rows.hpp.  A handle whose OBJECTIVE row is KTN_ROW_QUAD -- a hand-fused QuadNLP; nlp.fuse_problems
@@ -84,20 +126,32 @@ int Engine::optimize_blocks_device(int cap_mul, int flags) {
                        (size_t)(std::max(blk_nmax, mmax) + 4) * sizeof(int32_t);
     if (lds > 158 * 1024 || blk_nmax > 65535 || mmax > 65535) return kBlocksUnfit;      // 16-bit local indices in the arenas
     t_start = std::chrono::steady_clock::now();
-    d_ar.upload(ar, stream); d_blklin.upload(blk_lin, stream); d_blknl.upload(blk_nl, stream);
-    e_rptr.resize((size_t)row_tot + nb + 1, stream);
-    e_rcol.resize((size_t)nnz_tot + 1, stream); e_rval.resize((size_t)nnz_tot + 1, stream); e_rsval.resize((size_t)nnz_tot + 1, stream);
-    e_crow.resize((size_t)nnz_tot + 1, stream); e_cval.resize((size_t)nnz_tot + 1, stream); e_csval.resize((size_t)nnz_tot + 1, stream);
-    for (DBuf<double>* v : {&e_lo, &e_hi, &e_y, &e_dr, &e_loh, &e_hih}) v->resize((size_t)row_tot + 1, stream);
-    e_cptr.resize((size_t)n_lp + nb + 1, stream);
-    for (DBuf<double>* v : {&e_dc, &e_ch, &e_lh, &e_uh}) v->resize((size_t)n_lp + 1, stream);
-    e_last.resize((size_t)std::max<int64_t>(m_nl, 1), stream);
-    e_prev.resize((size_t)row_tot + 1, stream); e_ax.resize((size_t)row_tot + 1, stream);
-    e_res.resize((size_t)nb * 8, stream);
-    h_ar_row0.resize((size_t)nb); h_ar_nnz0.resize((size_t)nb); h_ar_rows.resize((size_t)nb);      // (ktn_blocks_get_cuts reads the arenas of this launch)
-    for (int bb = 0; bb < nb; ++bb) { h_ar_row0[(size_t)bb] = ar[(size_t)bb].row0; h_ar_nnz0[(size_t)bb] = ar[(size_t)bb].nnz0; h_ar_rows[(size_t)bb] = ar[(size_t)bb].cap_rows; }
-    h_blklin = blk_lin; h_blknl = blk_nl;
-    blocks_launched = false; blocks_last_esh = esh;
+    // (a supporting launch needs a lambda per kept row: after a Kelley launch there is none, and the launch is the cold one)
+    bool warm = want_warm && !(esh && !blocks_last_esh);
+    for (int bb = 0; warm && bb < nb; ++bb)                 // the geometry the resident arenas were laid out with
+        warm = ar[(size_t)bb].row0 == h_ar_row0[(size_t)bb] && ar[(size_t)bb].nnz0 == h_ar_nnz0[(size_t)bb] && ar[(size_t)bb].cap_rows == h_ar_rows[(size_t)bb];
+    if (!warm) {
+        d_ar.upload(ar, stream); d_blklin.upload(blk_lin, stream); d_blknl.upload(blk_nl, stream);
+        e_rptr.resize((size_t)row_tot + nb + 1, stream);
+        e_rcol.resize((size_t)nnz_tot + 1, stream); e_rval.resize((size_t)nnz_tot + 1, stream); e_rsval.resize((size_t)nnz_tot + 1, stream);
+        e_crow.resize((size_t)nnz_tot + 1, stream); e_cval.resize((size_t)nnz_tot + 1, stream); e_csval.resize((size_t)nnz_tot + 1, stream);
+        for (DBuf<double>* v : {&e_lo, &e_hi, &e_y, &e_dr, &e_loh, &e_hih}) v->resize((size_t)row_tot + 1, stream);
+        e_cptr.resize((size_t)n_lp + nb + 1, stream);
+        for (DBuf<double>* v : {&e_dc, &e_ch, &e_lh, &e_uh}) v->resize((size_t)n_lp + 1, stream);
+        e_last.resize((size_t)std::max<int64_t>(m_nl, 1), stream);
+        e_prev.resize((size_t)row_tot + 1, stream); e_ax.resize((size_t)row_tot + 1, stream);
+        e_res.resize((size_t)nb * 8, stream);
+        h_ar_row0.resize((size_t)nb); h_ar_nnz0.resize((size_t)nb); h_ar_rows.resize((size_t)nb);      // (ktn_blocks_get_cuts reads the arenas of this launch)
+        for (int bb = 0; bb < nb; ++bb) { h_ar_row0[(size_t)bb] = ar[(size_t)bb].row0; h_ar_nnz0[(size_t)bb] = ar[(size_t)bb].nnz0; h_ar_rows[(size_t)bb] = ar[(size_t)bb].cap_rows; }
+        h_blklin = blk_lin; h_blknl = blk_nl;
+    }
+    EcpWarm Wm{nullptr};
+    if (warm) {
+        blocks_rewarm();
+        Wm.rec = e_rewarm.p;
+    }
+    const std::vector<double> rewarm_rec = warm ? h_rewarm : std::vector<double>();
+    blocks_launched = false; blocks_last_esh = esh; blocks_warm_ok = false; blocks_rewarmed = false; blocks_cap_mul = cap_mul;
     EcpEsh E{};
     if (esh) {
         e_lam.resize((size_t)row_tot + 1, stream);
@@ -140,7 +194,16 @@ int Engine::optimize_blocks_device(int cap_mul, int flags) {
     B.near_chunk = prm.lp_near_check; B.ruiz_iters = prm.lp_ruiz_iters; B.nmax = blk_nmax; B.mmax = mmax;
     B.power_passes = dev.ecp_power;
     // the loaded state: M == M_base rows (the linear rows), as after reset()
-    if (esh) {
+    if (warm) {
+        // (the warm instantiations ask for their dynamic LDS at every launch: two more high-water marks would save a call per solve)
+        if (esh) {
+            KTN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ecp_blocks<1, EcpEsh, EcpWarm>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            launch(k_ecp_blocks<1, EcpEsh, EcpWarm>, (unsigned)nb, kEcpThreads, lds, stream, B, E, Wm);
+        } else {
+            KTN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ecp_blocks<0, EcpWarm>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            launch(k_ecp_blocks<0, EcpWarm>, (unsigned)nb, kEcpThreads, lds, stream, B, Wm);
+        }
+    } else if (esh) {
         if (lds > lds_set_ecp_esh) {
             KTN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ecp_blocks<1, EcpEsh>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             lds_set_ecp_esh = lds;
@@ -155,7 +218,7 @@ int Engine::optimize_blocks_device(int cap_mul, int flags) {
     }
     check_launch();
     std::vector<double> res = e_res.to_host(stream);
-    blocks_launched = true;
+    blocks_launched = true; blocks_warm_ok = true;
     h_blkres = res;
     ++kkt_solves; kkt_solved = true; kkt_arena = true; kkt_cached = false;      // (KKT report: multipliers and lists are the arenas' now)
     stats["ecp_blocks_esh_rows"] = 0.0;
@@ -166,12 +229,16 @@ int Engine::optimize_blocks_device(int cap_mul, int flags) {
         stats["esh_rows"] += c[0]; stats["esh_fallback_rows"] += c[1]; stats["esh_newton_steps"] += c[2]; stats["esh_quad_rows"] += c[3];
         stats["ecp_blocks_esh_rows"] = c[0];
     }
-    bool ok = true;
+    bool ok = true, screened_only = warm;                    // (screened_only: every instance that is not :Optimal was ended by the screen)
     int first_open = KTN_STATUS_OPTIMAL;
     double obj = 0.0, it_max = 0.0, cuts = 0.0, pd = 0.0, rows = 0.0;
     for (int bb = 0; bb < nb; ++bb) {
         const double* o = res.data() + (size_t)bb * 8;
-        if ((int)o[0] != KTN_STATUS_OPTIMAL) { if (ok) first_open = (int)o[0]; ok = false; }
+        if ((int)o[0] != KTN_STATUS_OPTIMAL) {
+            if (ok) first_open = (int)o[0];
+            ok = false;
+            if (!(warm && (int)rewarm_rec[(size_t)bb * 8] == 2)) screened_only = false;
+        }
         obj += o[2]; it_max = std::max(it_max, o[1]); cuts += o[3]; pd += o[4]; rows += o[6];
     }
     if (dev.debug_blocks) {
@@ -189,15 +256,17 @@ int Engine::optimize_blocks_device(int cap_mul, int flags) {
         }
     }
     stats["ecp_blocks_launches"] += 1.0;
+    if (warm) stats["ecp_blocks_warm_launches"] += 1.0;
     stats["ecp_blocks_pdhg_sum"] += pd;
     stats["ecp_blocks_rows"] = rows;
     stats["ecp_blocks_tape_rows"] = (double)n_tape_nl;
     stats["ecp_blocks_quad_rows"] = (double)n_quad_nl;
-    if (!ok && !keep) { stats["ecp_blocks_fallbacks"] += 1.0; return kBlocksOpen; }
+    screened_only = screened_only && !ok;
+    if (!ok && !keep && !screened_only) { stats["ecp_blocks_fallbacks"] += 1.0; return kBlocksOpen; }
     status = ok ? KTN_STATUS_OPTIMAL : first_open; lp_status = KTN_STATUS_OPTIMAL;
     iter = (int64_t)it_max; numcuts = (int64_t)cuts; objval = obj + c0; allsat = ok;
     soltime = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
-    return ok ? kBlocksDone : kBlocksOpen;
+    return ok ? kBlocksDone : (screened_only ? kBlocksScreened : kBlocksOpen);
 }
 
 // ktn_blocks_get_cuts: the cut rows of instance `block` in the arenas of the last device launch
@@ -254,6 +323,7 @@ void Engine::boundroutine() {
 
 void Engine::begin() {
     KTN_REQUIRE(loaded, "optimize! before loadproblem!");
+    blocks_drop_warm();               // (x is the host loop's from here on: a later KTN_BLOCKS_WARM launch starts cold)
     t_start = std::chrono::steady_clock::now();
     begun = true;
     lp_status = KTN_STATUS_OPTIMAL;

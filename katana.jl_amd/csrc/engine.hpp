@@ -346,8 +346,21 @@ struct Engine {
     DBuf<double> d_blkomega, d_blkres;
     int blk_nmax = 0, blk_mmax = 0;
     void build_blocks();
-    enum { kBlocksUnfit = 0, kBlocksDone = 1, kBlocksOpen = 2 };      // optimize_blocks_device: not launched / all :Optimal / some instance not
+    // optimize_blocks_device: not launched / all :Optimal / some instance not / the instances that are not were all ended
+    // :Infeasible by the screen of a warm launch (the host loop cannot help them: no fallback)
+    enum { kBlocksUnfit = 0, kBlocksDone = 1, kBlocksOpen = 2, kBlocksScreened = 3 };
     int optimize_blocks_device(int cap_mul, int flags);
+    // Warm re-solve of the resident arenas (KTN_BLOCKS_WARM; batch_warm.hpp, DESIGN.md section 14 "In the device-side loop").
+    // blocks_warm_ok: the arenas, e_res and lp_x are those of the last device launch on the loaded problem (dropped by ktn_reset,
+    // ktn_loadproblem, ktn_set_blocks and a host fallback; kept by the setters).  blocks_rewarmed: h_rewarm holds the records of
+    // k_blocks_rewarm for the data in force (dropped by a setter and by a launch), so ktn_blocks_rewarm is idempotent.
+    bool blocks_warm_ok = false, blocks_rewarmed = false, reset_keeps_x = false;
+    int blocks_cap_mul = 0;
+    std::vector<double> h_rewarm;
+    DBuf<double> e_rewarm;
+    hipEvent_t ev_rewarm[2] = {nullptr, nullptr};
+    void blocks_drop_warm() { blocks_warm_ok = false; blocks_rewarmed = false; }
+    void blocks_rewarm();                         // k_blocks_rewarm over every instance, unless h_rewarm is current
     // the last device launch on the loaded problem, for ktn_blocks_get_results / ktn_blocks_get_cuts
     bool blocks_launched = false, blocks_last_esh = false;
     std::vector<int64_t> h_ar_row0, h_ar_nnz0, h_ar_rows, h_blklin, h_blknl;      // arena offsets and row capacities, offsets of linear rows / NL slots
@@ -455,6 +468,7 @@ struct Engine {
         ipc_release();
         for (auto e : ev_pool) (void)hipEventDestroy(e);
         for (auto e : ev_screen) if (e) (void)hipEventDestroy(e);
+        for (auto e : ev_rewarm) if (e) (void)hipEventDestroy(e);
         if (stream) (void)hipStreamDestroy(stream);
         if (h_chk) (void)hipHostFree(h_chk);
     }

@@ -19,6 +19,7 @@ void Engine::esh_build_aux(const double* l_var, const double* u_var, const doubl
     child = nullptr;
     xint_given = false; esh_ready = false; xint_found = 0;
     blocks_launched = false;                     // (a new problem: no device launch of the batch loop to read back yet)
+    blocks_drop_warm();
     h_xint.clear();
     aux = EshAux();
     h_esh_side.assign((size_t)m_ext, 0);

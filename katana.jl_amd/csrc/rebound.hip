@@ -33,6 +33,7 @@ void Engine::reopen() {
     lp_sols.clear();
     screened_out = false;
     reopened = true;
+    blocks_rewarmed = false;          // (the arenas of a device launch, blocks_launched and x stay: a warm launch screens them again)
     sync();
 }
 

@@ -974,7 +974,8 @@ void Engine::reset() {
     M = M_base; NNZ = NNZ_base; numcuts = numcuts_base;
     lp_rowptr.n = (size_t)M + 1; lp_col.n = (size_t)NNZ; lp_val.n = (size_t)NNZ;
     lp_lo.n = lp_hi.n = lp_y.n = (size_t)M;
-    lp_y.zero(stream); lp_x.zero(stream);
+    lp_y.zero(stream);
+    if (!reset_keeps_x) lp_x.zero(stream);      // (a warm device launch starts from the x of the last one: ktn_optimize_blocks_ex)
     std::vector<int64_t> neg1((size_t)std::max<int64_t>(m_ext, 1), -1);
     d_lastcut.upload(neg1, stream);
     d_age.resize((size_t)std::max<int64_t>(M, 1), stream);

@@ -20,7 +20,7 @@ using JuMP
 import ..KatanaSolver, ..AbstractKatanaSeparator, ..EpigraphNLPEvaluator          # src/solver.jl:6, src/separators.jl:8, src/nlpeval.jl:6
 import ..initialize!, ..precompute!, ..gencut, ..isconstrsat                      # the separator API, src/separators.jl:23-53
 
-export KatanaHipSeparator, supporting_hyperplane_cut, supporting_hyperplane_quad_cut, feasible_point, blocks_feasible_points
+export KatanaHipSeparator, supporting_hyperplane_cut, supporting_hyperplane_quad_cut, feasible_point, blocks_feasible_points, set_blocks!, optimize_blocks!, blocks_rewarm
 export setvarbounds!, lp_row_activity
 
 const LIB = get(ENV, "KATANA_HIP_LIB", joinpath(dirname(@__FILE__), "..", "libkatana_hip.so"))
@@ -398,6 +398,27 @@ function blocks_feasible_points(m::KatanaHipModel)
     check(m, ccall((:ktn_blocks_get_feasible_points, LIB), Cint, (Ptr{Void}, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Int64, Ref{Int64}),
                    m.handle, x, length(x), info, length(info), cnt))
     x[1:m.num_var], reshape(info[1:cnt[]], KTN_FEAS_INFO_LEN, :)
+end
+# Throughput mode (ktn_set_blocks / ktn_optimize_blocks_ex): the loaded problem is a block-diagonal batch and every instance's whole
+# loop runs in its own workgroup.  warm = true (KTN_BLOCKS_WARM) starts every instance from its arena of the last device launch on
+# this handle -- its cuts, multipliers and x, screened against the bounds in force (DESIGN.md section 14 "In the device-side loop").
+const KTN_BLOCKS_SUPPORTING = 1
+const KTN_BLOCKS_NO_FALLBACK = 2
+const KTN_BLOCKS_WARM = 4
+set_blocks!(m::KatanaHipModel, col_offsets) =
+    check(m, ccall((:ktn_set_blocks, LIB), Cint, (Ptr{Void}, Int64, Ptr{Int64}), m.handle, length(col_offsets) - 1, convert(Vector{Int64}, col_offsets)))
+function optimize_blocks!(m::KatanaHipModel; cut_capacity = 0, supporting = false, fallback = true, warm = false)
+    flags = (supporting ? KTN_BLOCKS_SUPPORTING : 0) | (fallback ? 0 : KTN_BLOCKS_NO_FALLBACK) | (warm ? KTN_BLOCKS_WARM : 0)
+    STATUS[check(m, ccall((:ktn_optimize_blocks_ex, LIB), Cint, (Ptr{Void}, Int32, Int32), m.handle, cut_capacity, flags)) + 1]
+end
+# 8 x n_blocks records of k_blocks_rewarm (state 0 cold / 1 warm / 2 infeasible, LP rows, non-zeros, rows dropped, columns clamped,
+# first proving row -- 0-based, -1 if none --, crossed columns, redundant rows); idempotent until the next setter or launch
+function blocks_rewarm(m::KatanaHipModel)
+    cnt = Ref{Int64}(0)
+    check(m, ccall((:ktn_blocks_rewarm, LIB), Cint, (Ptr{Void}, Ptr{Cdouble}, Int64, Ref{Int64}), m.handle, C_NULL, 0, cnt))
+    out = zeros(Float64, max(cnt[], 1))
+    check(m, ccall((:ktn_blocks_rewarm, LIB), Cint, (Ptr{Void}, Ptr{Cdouble}, Int64, Ref{Int64}), m.handle, out, length(out), cnt))
+    reshape(out[1:cnt[]], 8, :)
 end
 # Re-solve from the kept cut pool (include/katana_hip.h; DESIGN.md section 14): new variable bounds or a new linear cost in place.
 # The cuts, their multipliers and the point stay; the next optimize! runs the ordinary loop from them.  Crossed bounds are accepted

@@ -326,17 +326,31 @@ class KatanaNonlinearModel:
         off = np.ascontiguousarray(col_offsets, dtype=np.int64)
         L.check(self._h, self._lib.ktn_set_blocks(self._h, len(off) - 1, _p(off, C.c_int64)))
 
-    def optimize_blocks(self, cut_capacity=0, supporting=False, fallback=True):
+    def optimize_blocks(self, cut_capacity=0, supporting=False, fallback=True, warm=False):
         """optimize! of a block-diagonal batch with every instance's whole loop in its own workgroup (ktn_optimize_blocks).
         supporting: cut_algo "supporting_hyperplane[_quad]" runs inside the device-side loop (KTN_BLOCKS_SUPPORTING; tape rows keep
         Kelley's cut there); without it such a handle is refused.  fallback=False (KTN_BLOCKS_NO_FALLBACK): return after the device
-        launch with the first status that is not "Optimal" instead of running the ordinary loop.  With both keywords at their
-        defaults the call is ktn_optimize_blocks itself, otherwise ktn_optimize_blocks_ex.  last_sweep_lambdas() keeps describing the
-        sweeps of the host-driven loop only; the lambdas of a device launch come from blocks_cuts()."""
-        if not supporting and fallback:
+        launch with the first status that is not "Optimal" instead of running the ordinary loop.  warm=True (KTN_BLOCKS_WARM): every
+        instance starts from its arena of the last device launch -- its cuts, multipliers and x, screened against the bounds in
+        force --; do not reset() in between (that drops the warm state, and the call is then the cold launch).  With all keywords
+        at their defaults the call is ktn_optimize_blocks itself, otherwise ktn_optimize_blocks_ex.  last_sweep_lambdas() keeps
+        describing the sweeps of the host-driven loop only; the lambdas of a device launch come from blocks_cuts()."""
+        if not supporting and fallback and not warm:
             return STATUS_SYMBOLS[L.check(self._h, self._lib.ktn_optimize_blocks(self._h, int(cut_capacity)))]
-        flags = (L.BLOCKS_SUPPORTING if supporting else 0) | (0 if fallback else L.BLOCKS_NO_FALLBACK)
+        flags = (L.BLOCKS_SUPPORTING if supporting else 0) | (0 if fallback else L.BLOCKS_NO_FALLBACK) | (L.BLOCKS_WARM if warm else 0)
         return STATUS_SYMBOLS[L.check(self._h, self._lib.ktn_optimize_blocks_ex(self._h, int(cut_capacity), flags))]
+
+    BLOCKS_REWARM_FIELDS = ("state", "lp_rows", "nnz", "dropped_rows", "clamped_cols", "first_proving_row", "crossed_cols", "redundant_rows")
+
+    def blocks_rewarm(self):
+        """[n_blocks, 8] records of k_blocks_rewarm on the arenas of the last device launch (ktn_blocks_rewarm; columns:
+        BLOCKS_REWARM_FIELDS, state 0 cold / 1 warm / 2 infeasible): the screen against the bounds in force, the clamp of x and the
+        compaction that a warm optimize_blocks() would run first.  Idempotent until the next setter or launch."""
+        n = C.c_int64(0)
+        L.check(self._h, self._lib.ktn_blocks_rewarm(self._h, C.POINTER(C.c_double)(), 0, C.byref(n)))
+        out = np.zeros(max(n.value, 1))
+        L.check(self._h, self._lib.ktn_blocks_rewarm(self._h, _p(out), len(out), C.byref(n)))
+        return out[:n.value].reshape(-1, 8)
 
     BLOCKS_RESULT_FIELDS = ("status", "iters", "objval", "numcuts", "pdhg_iters", "max_viol", "lp_rows", "overflow")
 
