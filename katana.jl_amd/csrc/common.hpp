@@ -12,15 +12,11 @@
 #include <vector>
 
 #include "../../include/katana_hip.h"
+#include "error.hpp"
 
 namespace ktn {
 
-struct Error : public std::runtime_error {
-    int code;
-    Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
-
-#define KTN_HIP(expr)                                                                          \
+#define KTN_HIP(expr)                                                                         \
     do {                                                                                       \
         hipError_t e__ = (expr);                                                               \
         if (e__ != hipSuccess) {                                                               \
@@ -28,11 +24,6 @@ struct Error : public std::runtime_error {
                                std::string(#expr) + ": " + hipGetErrorString(e__) + " (" +    \
                                    __FILE__ + ":" + std::to_string(__LINE__) + ")");          \
         }                                                                                      \
-    } while (0)
-
-#define KTN_REQUIRE(cond, msg)                                   \
-    do {                                                         \
-        if (!(cond)) throw ::ktn::Error(KTN_E_INVALID, (msg));   \
     } while (0)
 
 // KTN_POISON (development switch, DevParams in engine.hpp; DESIGN.md "Reproducibility"): every NEW allocation of DBuf::reserve is

@@ -1,6 +1,8 @@
 // engine.hpp -- struct Engine: the state of one handle and the declarations of its methods.  No kernel is named here; the methods
 // live in
-//   sweep.hip   loadproblem, the separator sweep (precompute! + isconstrsat + gencut + round_coefs + _addcut), the host-evaluator rows
+//   load.hip    loadproblem as a list of stages (the index arithmetic that needs no device: load_host.hpp), tape shape classes,
+//               QUAD rows, reset
+//   sweep.hip   the separator sweep (precompute! + isconstrsat + gencut + round_coefs + _addcut), the host-evaluator rows, the KKT report
 //   pool.hip    the cut pool: LP row storage, CSC mirror, working (epigraph-shifted) form, purging, append / pack / unpack
 //   lp.hip      the LP solves: scaling, tiled copies, PDHG steps and checks, exact small / mid-size LPs, per-block LPs, recession ray
 //   ecp.hip     the cutting-plane loop: begin / step / polish_step / end, objective certificate, device-side batch loop
@@ -125,6 +127,8 @@ struct DevParams {
     }
 };
 
+struct LoadScratch;                 // load.hip
+
 struct Engine {
     ktn_params prm;
     DevParams dev;
@@ -193,8 +197,7 @@ struct Engine {
     DBuf<double> d_tc_c, d_tc_cst;
     DBuf<TapeClassMeta> d_tc_meta;
     DBuf<uint8_t> d_tc_rowflag;                // [m_ext] 1: the row is evaluated by k_tape_classed (k_gj_stats skips it)
-    void build_tape_classes(const std::vector<int64_t>& nodeptr, const std::vector<int32_t>& nop, const std::vector<int32_t>& na,
-                            const std::vector<int32_t>& nb, const std::vector<double>& nc, const std::vector<int32_t>& tape_all);
+    void build_tape_classes(const LoadScratch& S);
     TapeClassDev tape_class_view();
     // KTN_ROW_QUAD rows (quad_rows.hpp; built by build_quad_rows at load): the Q entries in two streams, the QUAD rows' Jacobian
     // entries numbered in row order, and two launch lists -- all QUAD rows (precompute_all), those among the NL rows (sweep)
@@ -204,7 +207,7 @@ struct Engine {
     DBuf<int32_t> d_qcol, d_qrows_all, d_qrows_nl;
     DBuf<double> d_qval, d_qvterm;
     DBuf<int64_t> d_qptr, d_qjidx, d_qslots_all, d_qslots_nl, d_qtbase_all, d_qtbase_nl, d_qent_nl;
-    void build_quad_rows(const ktn_nlp_desc* d);
+    void build_quad_rows(const ktn_nlp_desc* d, const LoadScratch& S);
     void launch_quad(bool nl_only, const double* d_x, double f_tol);
     // sweep state
     DBuf<double> d_g, d_jac, d_bconst, d_maxc, d_xs, d_ray, d_scal;
@@ -569,6 +572,22 @@ struct Engine {
     // ================================================================ loadproblem ===
     void loadproblem(int64_t num_var, int64_t num_constr, const double* l_var, const double* u_var,
                      const double* l_constr, const double* u_constr, int32_t sense_, const ktn_nlp_desc* d);
+    // its stages, in the order they run (load.hip); LoadScratch: what one stage leaves for the next and nobody needs after the load
+    void load_constraint_rows(const ktn_nlp_desc* d, LoadScratch& S);
+    void load_epigraph_row(const ktn_nlp_desc* d, LoadScratch& S);
+    void load_host_rows(const ktn_nlp_desc* d);
+    void load_tape_nodes(const ktn_nlp_desc* d, LoadScratch& S);
+    void load_rows_and_box(const double* l_var, const double* u_var, const double* l_constr, const double* u_constr,
+                           const ktn_nlp_desc* d, LoadScratch& S);
+    void load_upload_nlp(LoadScratch& S);
+    void load_blocked_copy(const LoadScratch& S);
+    void load_long_rows(const LoadScratch& S);
+    void load_batched_copy(const LoadScratch& S);
+    void load_sweep_form(const LoadScratch& S);
+    void load_sweep_buffers();
+    void load_linear_rows(LoadScratch& S);
+    void load_objective(LoadScratch& S);
+    void load_lp(const LoadScratch& S);
     void reset();
 
     // ================================================================ separator =====

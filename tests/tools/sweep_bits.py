@@ -8,9 +8,11 @@ the fused batches of sep_cases.py and fuse_quad_cases.py) at the tests' own size
 gencut of every row, one sweep and the cut emission -- or, for the fused batches, the device-side loop -- under the switches that
 select each kernel form.  Every output a caller can see goes into the .npz: g, the Jacobian, the cut constants, the violated slots,
 maxviol, the status (a non-finite coefficient in a violated row: Error), the appended LP rows (columns, values, bounds), lambda and
-the supporting-hyperplane counters, the per-instance results of a batch; and the load statistics that say which form ran.
+the supporting-hyperplane counters, the per-instance results of a batch; and the load statistics that say which form ran.  Per
+model, before its first sweep, also the LP as loadproblem left it: its rows from 0 with their bounds, the cost vector and c0.
 One process per build (KTN_LIB is read at import); `compare` needs no GPU."""
 import contextlib
+import ctypes
 import os
 import subprocess
 import sys
@@ -50,8 +52,19 @@ def get_g_jac(ktn, model, sep):
     return g[:sep.num_constr], jac[:sep.nnz]
 
 
+def lp_as_loaded(ktn, out, name, model):
+    """the LP of a freshly loaded model: the linear rows, the epigraph cut at the box vertex if there is one, cost and c0"""
+    L = ktn._lib
+    for k, a in zip(("rowptr", "col", "val", "lo", "hi"), model.lp_rows_from(0)):
+        out[name + "/load_lp_" + k] = np.array(a)
+    c, c0 = np.zeros(model.num_var + 1), ctypes.c_double(0.0)        # (one more than num_var: the epigraph variable, when there is one)
+    L.check(model._h, model._lib.ktn_lp_get_objective(model._h, c.ctypes.data_as(L.P(L.c_f64)), len(c), ctypes.byref(c0)))
+    out[name + "/load_lp_c_c0"] = np.concatenate([c, [c0.value]])
+
+
 def precompute_and_sweep(ktn, out, name, model, x, f_tol, stats=()):
-    """precompute! at x, gencut, one sweep with its emission: all of it into out[name/...]"""
+    """the LP as loaded; precompute! at x, gencut, one sweep with its emission: all of it into out[name/...]"""
+    lp_as_loaded(ktn, out, name, model)
     sep = ktn.KatanaHipSeparator(model)
     sep.initialize()
     sep.precompute(x)
@@ -191,10 +204,11 @@ def supporting_hyperplane_cases(ktn, out):
     inst = ktn.instances.make_instance(n=4000, m_nl=400, k=32, family="explog", seed=0)
     model = ktn.NonlinearModel(ktn.KatanaSolver(log_level=0, cut_algo="supporting_hyperplane"))
     model.loadproblem(inst.n, inst.num_constr, inst.l_var, inst.u_var, inst.l_constr, inst.u_constr, inst.sense, ktn.SeparableNLP(inst))
+    name = "esh_first_round"
+    lp_as_loaded(ktn, out, name, model)
     model.optimize_begin()
     m0 = model.lp_num_rows()
     model.ecp_step()
-    name = "esh_first_round"
     out[name + "/x"] = model.getsolution()
     for k, a in zip(("rowptr", "col", "val", "lo", "hi"), model.lp_rows_from(m0)):
         out[name + "/lp_" + k] = np.array(a)
