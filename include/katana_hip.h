@@ -335,6 +335,30 @@ int ktn_set_var_bounds(ktn_handle h, const double* l, const double* u, int64_t n
 int ktn_set_linear_objective(ktn_handle h, const double* c, int64_t n, double c0);
 int ktn_lp_row_activity(ktn_handle h, double* amin, double* amax, int64_t m);
 
+/* ---- re-solve after a change of constraint bounds (DESIGN.md section 14 "Row bounds").  A cut of nonlinear row i taken at a
+ * point with tangent constant b is stored as [lb_i - b, ub_i - b]; the tangent of a convex g_i is valid at every level, so the
+ * cut for new bounds is the same row with its sides moved by ub_i' - ub_i and lb_i' - lb_i.  ktn_set_row_bounds does that to every
+ * cut of the pool in place, along the per-row cut lists, and follows the contract of ktn_set_var_bounds above: coefficients,
+ * multipliers, lists, ages, x and the scaling stay, the run state is re-opened, the same handles are refused.
+ *
+ * ktn_set_row_bounds: m == num_constr of ktn_loadproblem; lb == NULL or ub == NULL keeps that side; a NaN bound is
+ *   KTN_E_INVALID.  A NONLINEAR row may move its finite bound(s) but not gain or lose a side (the finite side defines its convex
+ *   level set): such a request is KTN_E_INVALID and changes nothing.  Linear rows may gain or lose sides freely; their LP rows
+ *   are worked out again from the tangent at the origin and equal those of a fresh load bit for bit.  The epigraph row is never
+ *   touched.  Each moved side of a cut is one rounded addition hi + (ub' - ub), the difference formed once per row; a side whose
+ *   old and new bound are equal (two infinite ones included) is not written, so unchanged bounds leave the pool bit for bit.
+ *   The engine's own interior point is searched again; the caller's is kept as given.  lb_i' > ub_i' is accepted and counted
+ *   (stat "screen_crossed_rows"): the next solve ends :Infeasible before any LP, as for crossed columns, and otherwise starts
+ *   with the screen of ktn_set_var_bounds.  With a device launch of ktn_optimize_blocks[_ex] standing, the resident arenas get
+ *   the same treatment before the call returns (linear rows copied, cut rows shifted), so KTN_BLOCKS_WARM continues from them.
+ *   Stats: "rebase_rows" (cut rows moved, pool and arenas), "rebase_kernel_s" (the kernels' own time), "screen_crossed_rows".
+ * ktn_lp_get_row_owners: owner[M] (M = ktn_lp_num_rows; m < M is KTN_E_INVALID): for every LP row the caller's constraint row
+ *   whose cut list holds it, num_constr for a cut of the epigraph row, -1 for a row in no list (linear rows, engine-made rows,
+ *   rows appended without an id).  KTN_E_UNSUPPORTED while the lists are not tracked (rows appended from the host without
+ *   global lists) or are global (ktn_lp_enable_global_lists). */
+int ktn_set_row_bounds(ktn_handle h, const double* lb, const double* ub, int64_t m);
+int ktn_lp_get_row_owners(ktn_handle h, int64_t* owner, int64_t m);
+
 /* MathProgBase.status / getobjval / getsolution / getsolvetime  src/model.jl:337-343;
  * numiters / numcuts src/model.jl:326,333; setwarmstart! (a no-op) :335 */
 int     ktn_get_status(ktn_handle h);

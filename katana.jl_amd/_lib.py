@@ -76,6 +76,8 @@ PROTOTYPES = {
     "ktn_set_var_bounds": (c_i32, [C.c_void_p, P(c_f64), P(c_f64), c_i64]),
     "ktn_set_linear_objective": (c_i32, [C.c_void_p, P(c_f64), c_i64, c_f64]),
     "ktn_lp_row_activity": (c_i32, [C.c_void_p, P(c_f64), P(c_f64), c_i64]),
+    "ktn_set_row_bounds": (c_i32, [C.c_void_p, P(c_f64), P(c_f64), c_i64]),
+    "ktn_lp_get_row_owners": (c_i32, [C.c_void_p, P(c_i64), c_i64]),
     "ktn_get_status": (c_i32, [C.c_void_p]),
     "ktn_get_objval": (c_f64, [C.c_void_p]),
     "ktn_get_num_var": (c_i64, [C.c_void_p]),

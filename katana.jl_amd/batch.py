@@ -103,6 +103,7 @@ class FusedBatch:
         from .instances import fuse_instances
         self.instances = instances
         self._bounds = None                                         # (set_var_bounds: the fused bounds in force, once they differ from the loaded ones)
+        self._row_bounds = None                                     # (set_row_bounds: the same for the constraint bounds)
         if not _all_instances(instances):                         # Problems / Models, tape and QUAD rows allowed (nlp.fuse_problems)
             probs = [_as_problem(i) for i in instances]
             self.big, self.offs, self._objinfo = fuse_problems(probs, allow_quad=True)
@@ -171,6 +172,35 @@ class FusedBatch:
                 cur[0][o + n_k], cur[1][o + n_k] = -R, R
         self.m.setvarbounds(cur[0], cur[1])
         self._bounds = cur
+        return cur
+
+    def set_row_bounds(self, lb_list, ub_list):
+        """New constraint bounds per instance (ktn_set_row_bounds), each vector over the instance's own rows in its own row order;
+        None (for a side, or for one instance of a side) keeps what is in force.  The vectors are placed at the instance's rows of
+        the fused problem (_row_ranges) and set in place.  The epigraph row that fusion gave a quadratic objective keeps its
+        bounds.  Fusion negates the objective of a "Max" instance, never its rows: the bounds go in as given.  With a device
+        launch standing the resident arenas are updated by the same call, so solve(warm=True) continues from each instance's own
+        cuts; solve() starts from the loaded rows with the new bounds."""
+        import numpy as np
+        cur = [np.array(self.big.l_constr, dtype=np.float64).reshape(-1), np.array(self.big.u_constr, dtype=np.float64).reshape(-1)]
+        if getattr(self, "_row_bounds", None) is not None:
+            cur = [self._row_bounds[0].copy(), self._row_bounds[1].copy()]
+        ranges = self._row_ranges()
+        for side, lst in enumerate((lb_list, ub_list)):
+            if lst is None:
+                continue
+            if len(lst) != len(self.instances):
+                raise ValueError("one bound vector per instance: %d for %d instances" % (len(lst), len(self.instances)))
+            for k, v in enumerate(lst):
+                if v is None:
+                    continue
+                v = np.asarray(v, dtype=np.float64).reshape(-1)
+                idx = ranges[k][0]
+                if len(v) != len(idx):
+                    raise ValueError("instance %d has %d constraints, its bound vector %d entries" % (k, len(idx), len(v)))
+                cur[side][idx] = v
+        self.m.setconstrbounds(cur[0], cur[1])
+        self._row_bounds = cur
         return cur
 
     def set_costs(self, c_list):

@@ -107,12 +107,23 @@ int ktn_optimize(ktn_handle h) {
 
 int ktn_reset(ktn_handle h) { KTN_TRY(h, { KTN_REQUIRE(h->eng->loaded, "reset before loadproblem"); h->eng->blocks_drop_warm(); h->eng->reset(); return KTN_OK; }) }
 
-// ---- re-solve from the kept cut pool (Engine::set_var_bounds / set_linear_objective / row_activity, rebound.hip)
+// ---- re-solve from the kept cut pool (Engine::set_var_bounds / set_linear_objective / set_row_bounds / row_owners / row_activity, rebound.hip)
 int ktn_set_var_bounds(ktn_handle h, const double* l, const double* u, int64_t n) {
     KTN_TRY(h, { h->eng->set_var_bounds(l, u, n); return KTN_OK; })
 }
 int ktn_set_linear_objective(ktn_handle h, const double* c, int64_t n, double c0) {
     KTN_TRY(h, { h->eng->set_linear_objective(c, n, c0); return KTN_OK; })
+}
+int ktn_set_row_bounds(ktn_handle h, const double* lb, const double* ub, int64_t m) {
+    KTN_TRY(h, { h->eng->set_row_bounds(lb, ub, m); return KTN_OK; })
+}
+int ktn_lp_get_row_owners(ktn_handle h, int64_t* owner, int64_t m) {
+    KTN_TRY(h, {
+        Engine* e = h->eng;
+        KTN_REQUIRE(e->loaded && owner && m >= e->M, "ktn_lp_get_row_owners: buffer missing or shorter than ktn_lp_num_rows");
+        e->row_owners(owner);
+        return KTN_OK;
+    })
 }
 int ktn_lp_row_activity(ktn_handle h, double* amin, double* amax, int64_t m) {
     KTN_TRY(h, {

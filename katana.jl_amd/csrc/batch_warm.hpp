@@ -255,4 +255,53 @@ static __global__ __launch_bounds__(kEcpThreads) void k_blocks_rewarm(WarmBatch 
     }
 }
 
+// ---- ktn_set_row_bounds on resident arenas (rebound.hpp "row bounds"; Engine::blocks_rebase).  Per instance, one workgroup:
+//   linear rows   lo / hi of arena rows [0, m_lin) are copied from the handle's lp_lo / lp_hi, which the setter has just worked out again
+//   cut rows      every row of the list of NL slot i moves by the change of that slot's row bounds: hi + (ub' - ub), lo + (lb' - lb),
+//                 the difference formed once per slot, a side whose old and new bound are equal not written (k_rebase_cuts' arithmetic)
+// M is the row count of the instance's launch record; outside [m_lin, cap_rows] (no launch ended there) the cut rows are left alone --
+// k_blocks_rewarm then calls the instance cold.  The walk follows last_cut / cut_prev and ends at a link that does not strictly descend.
+struct RebaseBatch {
+    const int64_t* blk_lin; const int64_t* blk_nl;      // [nb + 1] each, as EcpBatch
+    const EcpArena* arena;
+    const int32_t* nl_rows;                              // the engine's NL row list
+    const double* lp_lo; const double* lp_hi;            // the loaded LP: the linear rows of every instance
+    const double* lb_old; const double* ub_old; const double* lb_new; const double* ub_new;      // per extended row
+    double* lo; double* hi;
+    const int32_t* last_cut; const int32_t* cut_prev;
+    const double* res;                                   // [nb * 8] records of the last launch (slot 6: LP rows)
+    unsigned long long* cnt;                             // += cut rows moved
+};
+
+static __global__ __launch_bounds__(kEcpThreads) void k_blocks_rebase(RebaseBatch W) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int64_t lin0 = W.blk_lin[b];
+    const int m_lin = (int)(W.blk_lin[b + 1] - lin0);
+    const int64_t nl0 = W.blk_nl[b];
+    const int m_nl = (int)(W.blk_nl[b + 1] - nl0);
+    const EcpArena A = W.arena[b];
+    double* lo = W.lo + A.row0; double* hi = W.hi + A.row0;
+    const int32_t* last_cut = W.last_cut + nl0;
+    const int32_t* cut_prev = W.cut_prev + A.row0;
+    for (int r = tid; r < m_lin && r < A.cap_rows; r += kEcpThreads) { lo[r] = W.lp_lo[lin0 + r]; hi[r] = W.lp_hi[lin0 + r]; }
+    const int M = (int)W.res[(int64_t)b * 8 + 6];
+    if (!(M >= m_lin && M <= A.cap_rows)) return;
+    unsigned long long moved = 0;
+    for (int i = tid; i < m_nl; i += kEcpThreads) {
+        const int32_t gr = W.nl_rows[nl0 + i];
+        const double l0 = W.lb_old[gr], l1 = W.lb_new[gr], u0 = W.ub_old[gr], u1 = W.ub_new[gr];
+        const bool mlo = !(l0 == l1), mhi = !(u0 == u1);
+        if (!mlo && !mhi) continue;
+        const double dlo = mlo ? l1 - l0 : 0.0, dhi = mhi ? u1 - u0 : 0.0;
+        for (int r = last_cut[i]; r >= m_lin && r < M;) {
+            if (mlo) lo[r] = lo[r] + dlo;
+            if (mhi) hi[r] = hi[r] + dhi;
+            ++moved;
+            const int nx = cut_prev[r];
+            r = nx < r ? nx : -1;
+        }
+    }
+    if (moved) atomicAdd(W.cnt, moved);
+}
+
 }  // namespace ktn

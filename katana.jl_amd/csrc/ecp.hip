@@ -42,6 +42,20 @@ void Engine::blocks_rewarm() {
     blocks_rewarmed = true;
 }
 
+// ktn_set_row_bounds with a device launch standing: k_blocks_rebase over the resident arenas (batch_warm.hpp), the old row bounds
+// still in d_lb / d_ub, the new ones in d_lb_new / d_ub_new, lp_lo / lp_hi already those of the new linear rows.  *cnt += rows moved.
+void Engine::blocks_rebase(unsigned long long* cnt, hipEvent_t e0, hipEvent_t e1) {
+    RebaseBatch W;
+    W.blk_lin = d_blklin.p; W.blk_nl = d_blknl.p; W.arena = d_ar.p; W.nl_rows = d_nlrows.p;
+    W.lp_lo = lp_lo.p; W.lp_hi = lp_hi.p;
+    W.lb_old = d_lb.p; W.ub_old = d_ub.p; W.lb_new = d_lb_new.p; W.ub_new = d_ub_new.p;
+    W.lo = e_lo.p; W.hi = e_hi.p; W.last_cut = e_last.p; W.cut_prev = e_prev.p;
+    W.res = e_res.p; W.cnt = cnt;
+    launch_ev(k_blocks_rebase, (unsigned)n_blocks, kEcpThreads, 0, stream, e0, e1, W);
+    check_launch();
+    kkt_cached = false;                                  // (the report reads the arenas' row bounds)
+}
+
 // Throughput mode, device-side loop (batch_ecp.hpp).  Returns kBlocksUnfit when the problem does not qualify (nothing launched),
 // kBlocksOpen when an instance could not finish (arena overflow, LP status) -- the caller then runs the ordinary loop, or with
 // KTN_BLOCKS_NO_FALLBACK reports the first such instance's status -- and kBlocksDone when every instance ended :Optimal.

@@ -7,7 +7,7 @@
 //   lp.hip      the LP solves: scaling, tiled copies, PDHG steps and checks, exact small / mid-size LPs, per-block LPs, recession ray
 //   ecp.hip     the cutting-plane loop: begin / step / polish_step / end, objective certificate, device-side batch loop
 //   dist.hip    collectives of the row-sharded LP: RCCL, peer buffers, host callback
-//   rebound.hip the re-solve from the kept pool: bound and cost setters, reopen, the screen of the rows against a new box
+//   rebound.hip the re-solve from the kept pool: bound, cost and row-bound setters, reopen, the screen of the rows against a new box
 //   abi.hip     the C ABI of include/katana_hip.h
 // (until the middle of round 4 all of it was engine.hip, one translation unit of 4 100 lines).
 //
@@ -471,6 +471,7 @@ struct Engine {
         ipc_release();
         for (auto e : ev_pool) (void)hipEventDestroy(e);
         for (auto e : ev_screen) if (e) (void)hipEventDestroy(e);
+        for (auto e : ev_rebase) if (e) (void)hipEventDestroy(e);
         for (auto e : ev_rewarm) if (e) (void)hipEventDestroy(e);
         if (stream) (void)hipStreamDestroy(stream);
         if (h_chk) (void)hipHostFree(h_chk);
@@ -639,6 +640,7 @@ struct Engine {
     struct EshAux {
         int64_t n = 0, m = 0;
         std::vector<double> lv, uv, lc, uc, rconst, p0, p1, targ, op0, op1;
+        std::vector<int64_t> rows;                               // the caller's row of every auxiliary row
         std::vector<int64_t> rowptr, tptr, qptr;                 // qptr [entries + 1]: Q segments of the QUAD rows, empty for the others
         std::vector<int32_t> col, top, ocol, qcol;
         std::vector<double> qval;
@@ -719,6 +721,15 @@ struct Engine {
     void reopen();                    // reset() without the items that make up the pool
     void set_var_bounds(const double* l, const double* u, int64_t n);
     void set_linear_objective(const double* c, int64_t n, double c0_new);
+    // ktn_set_row_bounds: new constraint bounds in place.  Linear rows: their LP rows again from the tangent at the origin; NL rows:
+    // every cut of the row's list shifted by the change (k_rebase_cuts), in the pool and -- with a device launch standing -- in the
+    // resident arenas (k_blocks_rebase).  Every copy of the row bounds follows: h_lb / h_ub, d_lb / d_ub, d_slots, aux.lc / aux.uc.
+    int64_t crossed_rows = 0;         // caller's rows with lb_i > ub_i at the last ktn_set_row_bounds
+    DBuf<double> d_lb_new, d_ub_new;
+    hipEvent_t ev_rebase[4] = {nullptr, nullptr, nullptr, nullptr};     // k_rebase_cuts begin / end, k_blocks_rebase begin / end
+    void set_row_bounds(const double* lb, const double* ub, int64_t m);
+    void blocks_rebase(unsigned long long* cnt, hipEvent_t e0, hipEvent_t e1);     // ecp.hip: k_blocks_rebase, old bounds in d_lb / d_ub, new in d_lb_new / d_ub_new
+    void row_owners(int64_t* owner_out);      // ktn_lp_get_row_owners: M entries
     void row_activity(hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);      // k_row_activity over the current rows and bounds, into d_act_*
     bool screen();                    // true: the box is empty or contradicts a row
 

@@ -90,6 +90,7 @@ void Engine::esh_build_aux(const double* l_var, const double* u_var, const doubl
         A.kind.push_back(quad_lin ? (uint8_t)KTN_ROW_SEP : kind);
         A.lin.push_back(lin ? 1 : 0);
         A.rconst.push_back(d->rconst ? d->rconst[i] : 0.0);
+        A.rows.push_back(i);
         A.lc.push_back(l_constr[i]);
         A.uc.push_back(u_constr[i]);
     }

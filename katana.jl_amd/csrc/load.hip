@@ -416,7 +416,7 @@ void Engine::load_epigraph_row(const ktn_nlp_desc* d, LoadScratch& S) {
     obj_settable = obj_linear && (d->obj_kind == KTN_ROW_SEP || d->obj_kind == KTN_ROW_QUAD);
     for (int64_t e = h_rowptr[(size_t)m0]; e < nnz_ext && d->obj_kind == KTN_ROW_SEP; ++e)
         if (akind[(size_t)e] != KTN_ATOM_LIN) obj_settable = false;
-    screen_pending = false; crossed_cols = 0;
+    screen_pending = false; crossed_cols = 0; crossed_rows = 0;
     for (int64_t i = 0; i < m0; ++i) {                   // atom_kind and p1 are ignored for QUAD rows
         if (h_rowkind[i] != KTN_ROW_QUAD) continue;
         for (int64_t e = h_rowptr[i]; e < h_rowptr[i + 1]; ++e) { akind[(size_t)e] = 0; p1[(size_t)e] = 0.0; }

@@ -1,4 +1,4 @@
-// rebound.hip -- re-solve after a change of variable bounds or of a linear cost, from the kept cut pool:
+// rebound.hip -- re-solve after a change of variable bounds, of constraint bounds or of a linear cost, from the kept cut pool:
 // the host side of rebound.hpp (struct Engine: engine.hpp)
 #include "engine.hpp"
 #include "launch.hpp"
@@ -111,6 +111,111 @@ void Engine::set_linear_objective(const double* c, int64_t n, double c0_new) {
     reopen();
 }
 
+// New constraint bounds in place (rebound.hpp "row bounds").  Nothing is changed before every refusal has been decided.
+void Engine::set_row_bounds(const double* lb, const double* ub, int64_t m) {
+    KTN_REQUIRE(loaded, "ktn_set_row_bounds: after ktn_loadproblem");
+    KTN_REQUIRE(m == m0, "ktn_set_row_bounds: m must be the problem's num_constr");
+    KTN_REQUIRE(status != KTN_STATUS_ERROR, "ktn_set_row_bounds: the handle's status is :Error (ktn_reset or ktn_loadproblem first)");
+    require_own_lp(this, "ktn_set_row_bounds");
+    if (!lists_ok() || glists)
+        throw Error(KTN_E_UNSUPPORTED, "ktn_set_row_bounds: the cuts cannot be attributed to their rows (rows appended from the host, or global cut lists)");
+    for (int64_t i = 0; i < m0; ++i)
+        KTN_REQUIRE(!(lb && lb[i] != lb[i]) && !(ub && ub[i] != ub[i]), "ktn_set_row_bounds: a bound is NaN");
+    std::vector<double> nlb(h_lb), nub(h_ub);            // per extended row; a NULL side keeps what is loaded, the epigraph row its own
+    if (lb) std::copy(lb, lb + m0, nlb.begin());
+    if (ub) std::copy(ub, ub + m0, nub.begin());
+    std::vector<char> is_nl((size_t)std::max<int64_t>(m0, 1), 0);
+    for (int32_t r : h_nlrows) if (r < m0) is_nl[(size_t)r] = 1;
+    // a nonlinear row keeps its pattern of finite sides (an infinite side stays the infinity it is): the finite side defines the
+    // convex level set the cuts were taken for
+    auto same_side = [](double a, double b) { return std::isfinite(a) ? std::isfinite(b) : a == b; };
+    bool lin_changed = false;
+    int64_t crossed = 0;
+    for (int64_t i = 0; i < m0; ++i) {
+        const size_t k = (size_t)i;
+        if (is_nl[k])
+            KTN_REQUIRE(same_side(h_lb[k], nlb[k]) && same_side(h_ub[k], nub[k]),
+                        "ktn_set_row_bounds: a nonlinear row may move its finite bounds but not gain or lose a side");
+        else if (std::memcmp(&h_lb[k], &nlb[k], sizeof(double)) != 0 || std::memcmp(&h_ub[k], &nub[k], sizeof(double)) != 0)
+            lin_changed = true;
+        if (nlb[k] > nub[k]) ++crossed;
+    }
+    crossed_rows = crossed;
+    stats["screen_crossed_rows"] = (double)crossed;
+    d_lb_new.upload(nlb, stream); d_ub_new.upload(nub, stream);
+    // linear rows: the tangent at the origin again, as the load takes it; their LP rows then equal a fresh load's bit for bit
+    if (lin_changed && kkt_n_lin > 0) {
+        d_xs.zero(stream);
+        precompute_all(d_xs.p);
+        launch_n(k_lin_bounds, m0, stream, m0, (const int32_t*)d_kkt_rowmap.p, (const int64_t*)d_rowptr.p, (const double*)d_jac.p, (const double*)d_g.p,
+                 (const double*)d_lb_new.p, (const double*)d_ub_new.p, std::min<int64_t>(M, M_lin), lp_lo.p, lp_hi.p);
+        check_launch();
+    }
+    // cuts: every list row moves with its slot's bounds; the old ones are still in d_lb / d_ub
+    for (hipEvent_t& e : ev_rebase)                      // the kernels' own begin / end timestamps ("rebase_kernel_s")
+        if (!e) KTN_HIP(hipEventCreate(&e));
+    d_act_cnt.resize(4, stream);
+    d_act_cnt.zero(stream);
+    const bool pool_cuts = m_nl > 0 && M > M_base;
+    if (pool_cuts) {
+        launch_ev(k_rebase_cuts, grid_n(m_nl), kBlock, 0, stream, ev_rebase[0], ev_rebase[1], m_nl, (const int32_t*)d_nlrows.p, (const int64_t*)d_lastcut.p,
+                  (const int64_t*)d_cutprev.p, M, (const double*)d_lb.p, (const double*)d_ub.p, (const double*)d_lb_new.p, (const double*)d_ub_new.p,
+                  lp_lo.p, lp_hi.p, d_act_cnt.p);
+        check_launch();
+    }
+    // the resident arenas of a device launch hold their own row bounds (batch_warm.hpp k_blocks_rebase)
+    const bool arenas = blocks_launched && n_blocks > 0 && (int64_t)h_ar_rows.size() == n_blocks;
+    if (arenas) blocks_rebase(d_act_cnt.p + 1, ev_rebase[2], ev_rebase[3]);
+    unsigned long long cnt[2] = {0, 0};
+    KTN_HIP(hipMemcpyAsync(cnt, d_act_cnt.p, sizeof(cnt), hipMemcpyDeviceToHost, stream));
+    sync();
+    float ms = 0.f, ms_pool = 0.f, ms_blk = 0.f;
+    if (pool_cuts && hipEventElapsedTime(&ms_pool, ev_rebase[0], ev_rebase[1]) != hipSuccess) { (void)hipGetLastError(); ms_pool = 0.f; }
+    if (arenas && hipEventElapsedTime(&ms_blk, ev_rebase[2], ev_rebase[3]) != hipSuccess) { (void)hipGetLastError(); ms_blk = 0.f; }
+    ms = ms_pool + ms_blk;
+    stats["rebase_rows"] = (double)(cnt[0] + cnt[1]);
+    stats["rebase_kernel_s"] = (double)ms * 1e-3;
+    // the bounds themselves, and their two other copies
+    h_lb = nlb; h_ub = nub;
+    d_lb.upload(h_lb, stream); d_ub.upload(h_ub, stream);
+    if (blk_on && d_slots.n == (size_t)m_nl) {           // the column-blocked sweep reads them from its slot records
+        std::vector<SepSlot> slots = d_slots.to_host(stream);
+        for (int64_t si = 0; si < m_nl; ++si) {
+            const size_t r = (size_t)h_nlrows[(size_t)si];
+            slots[(size_t)si].lb = h_lb[r]; slots[(size_t)si].ub = h_ub[r];
+        }
+        d_slots.upload(slots, stream);
+        sync();                                          // (the temporary is freed on leaving the scope)
+    }
+    for (size_t k = 0; k < aux.rows.size(); ++k) {       // the supporting-hyperplane auxiliary problem, in its own row numbering
+        aux.lc[k] = h_lb[(size_t)aux.rows[k]]; aux.uc[k] = h_ub[(size_t)aux.rows[k]];
+    }
+    // the engine's own interior point belongs to the old bounds; the caller's stays, and which rows it is interior to is
+    // evaluated again (esh_prepare): a row for which it no longer is stores Kelley's cut
+    delete child;
+    child = nullptr;
+    if (!xint_given) { xint_found = 0; h_xint.clear(); }
+    esh_ready = false;
+    lp_dirty = true;                                     // the working form (wlo / whi) is a copy of lp_lo / lp_hi made when this is set
+    screen_pending = true;                               // a moved row bound can make a row impossible over the unchanged box
+    reopen();
+}
+
+void Engine::row_owners(int64_t* owner_out) {
+    if (!lists_ok() || glists)
+        throw Error(KTN_E_UNSUPPORTED, "ktn_lp_get_row_owners: no per-row cut lists (rows appended from the host, or global cut lists)");
+    if (M == 0) return;
+    DBuf<int64_t> t_owner;
+    t_owner.resize((size_t)M, stream);
+    KTN_HIP(hipMemsetAsync(t_owner.p, 0xFF, (size_t)M * sizeof(int64_t), stream));
+    if (m_nl > 0 && M > M_base) {
+        launch_n(k_row_owners, m_nl, stream, m_nl, (const int32_t*)d_nlrows.p, (const int64_t*)d_lastcut.p, (const int64_t*)d_cutprev.p, M, t_owner.p);
+        check_launch();
+    }
+    t_owner.download(owner_out, (size_t)M, stream);      // (synchronises: the temporary is free to go)
+    sync();
+}
+
 void Engine::row_activity(hipEvent_t e0, hipEvent_t e1) {
     const size_t mm = (size_t)std::max<int64_t>(M, 1);
     d_act_min.resize(mm, stream); d_act_max.resize(mm, stream);
@@ -145,9 +250,10 @@ bool Engine::screen() {
     stats["screen_first_row"] = cnt[0] ? (double)cnt[1] : -1.0;
     stats["screen_redundant_rows"] = (double)cnt[2];
     stats["screen_crossed_cols"] = (double)crossed_cols;
+    stats["screen_crossed_rows"] = (double)crossed_rows;
     stats["screen_kernel_s"] = (double)ms * 1e-3;
     stats["screen_time_s"] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return cnt[0] > 0 || crossed_cols > 0;
+    return cnt[0] > 0 || crossed_cols > 0 || crossed_rows > 0;
 }
 
 }  // namespace ktn

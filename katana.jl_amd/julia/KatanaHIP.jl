@@ -21,7 +21,7 @@ import ..KatanaSolver, ..AbstractKatanaSeparator, ..EpigraphNLPEvaluator        
 import ..initialize!, ..precompute!, ..gencut, ..isconstrsat                      # the separator API, src/separators.jl:23-53
 
 export KatanaHipSeparator, supporting_hyperplane_cut, supporting_hyperplane_quad_cut, feasible_point, blocks_feasible_points, set_blocks!, optimize_blocks!, blocks_rewarm
-export setvarbounds!, lp_row_activity
+export setvarbounds!, lp_row_activity, setconstrbounds!, lp_row_owners
 
 const LIB = get(ENV, "KATANA_HIP_LIB", joinpath(dirname(@__FILE__), "..", "libkatana_hip.so"))
 
@@ -435,6 +435,24 @@ MathProgBase.setvarUB!(m::KatanaHipModel, u) = setvarbounds!(m, nothing, u)
 function MathProgBase.setobj!(m::KatanaHipModel, c)
     length(c) == m.num_var || error("setobj!: one coefficient per variable")
     check(m, ccall((:ktn_set_linear_objective, LIB), Cint, (Ptr{Void}, Ptr{Cdouble}, Int64, Cdouble), m.handle, convert(Vector{Float64}, c), m.num_var, 0.0))
+end
+# New constraint bounds in place (ktn_set_row_bounds; DESIGN.md section 14 "Row bounds"): every cut of a nonlinear row moves with
+# its row's bound, linear rows are worked out again.  A nonlinear row may move its finite bound(s) but not gain or lose a side;
+# lb_i > ub_i is accepted and ends the next solve :Infeasible.  `nothing` keeps a side.
+function setconstrbounds!(m::KatanaHipModel, lb, ub)
+    (lb === nothing || length(lb) == m.num_constr) && (ub === nothing || length(ub) == m.num_constr) || error("setconstrbounds!: one bound per constraint")
+    lv = lb === nothing ? C_NULL : convert(Vector{Float64}, lb)
+    uv = ub === nothing ? C_NULL : convert(Vector{Float64}, ub)
+    check(m, ccall((:ktn_set_row_bounds, LIB), Cint, (Ptr{Void}, Ptr{Cdouble}, Ptr{Cdouble}, Int64), m.handle, lv, uv, m.num_constr))
+end
+MathProgBase.setconstrLB!(m::KatanaHipModel, lb) = setconstrbounds!(m, lb, nothing)
+MathProgBase.setconstrUB!(m::KatanaHipModel, ub) = setconstrbounds!(m, nothing, ub)
+# per LP row the constraint (1-based) whose cut list holds it; num_constr + 1 for a cut of the epigraph row, 0 for a row in no list
+function lp_row_owners(m::KatanaHipModel)
+    rows = ccall((:ktn_lp_num_rows, LIB), Int64, (Ptr{Void},), m.handle)
+    owner = fill(Int64(-1), max(rows, 1))
+    check(m, ccall((:ktn_lp_get_row_owners, LIB), Cint, (Ptr{Void}, Ptr{Int64}, Int64), m.handle, owner, rows))
+    owner[1:rows] .+ 1
 end
 # (amin, amax): the smallest and the largest value of every LP row over the current variable bounds
 function lp_row_activity(m::KatanaHipModel)

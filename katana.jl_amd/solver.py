@@ -185,6 +185,33 @@ class KatanaNonlinearModel:
             raise ValueError("setobj: %d entries for %d variables" % (len(c), self._n0))
         L.check(self._h, self._lib.ktn_set_linear_objective(self._h, _p(c), self._n0, float(c0)))
 
+    def setconstrbounds(self, lb, ub):
+        """New constraint bounds in place (MathProgBase.setconstrLB! / setconstrUB!; None keeps that side): every cut of a
+        nonlinear row moves with its row's bound, linear rows are worked out again, the multipliers and x stay.  A nonlinear row
+        may move its finite bound(s) but not gain or lose a side (E_INVALID, nothing changed).  lb_i > ub_i is accepted and ends
+        the next solve "Infeasible" (stat "screen_crossed_rows")."""
+        lb = None if lb is None else _f64(lb)
+        ub = None if ub is None else _f64(ub)
+        for v in (lb, ub):
+            if v is not None and len(v) != self._m0:
+                raise ValueError("setconstrbounds: %d entries for %d constraints" % (len(v), self._m0))
+        null = C.POINTER(C.c_double)()
+        L.check(self._h, self._lib.ktn_set_row_bounds(self._h, null if lb is None else _p(lb), null if ub is None else _p(ub), self._m0))
+
+    def setconstrLB(self, lb):
+        self.setconstrbounds(lb, None)
+
+    def setconstrUB(self, ub):
+        self.setconstrbounds(None, ub)
+
+    def lp_row_owners(self):
+        """per LP row the constraint row whose cut list holds it; num_constr for a cut of the epigraph row, -1 for a row in no
+        list: linear rows, engine-made rows, rows appended without an id (ktn_lp_get_row_owners)"""
+        m = int(self._lib.ktn_lp_num_rows(self._h))
+        owner = np.full(max(m, 1), -1, dtype=np.int64)
+        L.check(self._h, self._lib.ktn_lp_get_row_owners(self._h, _p(owner, C.c_int64), m))
+        return owner[:m]
+
     def lp_row_activity(self):
         """(amin, amax): the smallest and largest value of every LP row over the current variable bounds."""
         m = int(self._lib.ktn_lp_num_rows(self._h))
@@ -703,6 +730,23 @@ class LinearQuadraticModel(KatanaNonlinearModel):
             q["collb"] = l
         if u is not None:
             q["colub"] = u
+
+    def setconstrbounds(self, lb, ub):
+        q = self._lq
+        if q is None:
+            return super().setconstrbounds(lb, ub)
+        lb = None if lb is None else _f64(lb).copy()
+        ub = None if ub is None else _f64(ub).copy()
+        m = len(q["lb"])                                 # (the rows of loadproblem and those of addquadconstr after them)
+        for v in (lb, ub):
+            if v is not None and len(v) != m:
+                raise ValueError("setconstrbounds: %d entries for %d constraints" % (len(v), m))
+        if not q["dirty"]:
+            super().setconstrbounds(lb, ub)              # (refused: the kept state below stays as it is)
+        if lb is not None:
+            q["lb"] = list(lb)
+        if ub is not None:
+            q["ub"] = list(ub)
 
     def setobj(self, c, c0=0.0):
         q = self._lq

@@ -4,12 +4,15 @@ own cuts, multipliers and x) and COLD (solve() on the same handle: ktn_reset and
   (i)   unchanged data;
   (ii)  every instance's box cut down by one bound that removes its optimum (the child of a branching step): the upper bound of
         its most interior variable a quarter of the way below the optimum;
-  (iii) every instance's costs scaled by 1.25.
+  (iii) every instance's costs scaled by 1.25;
+  (iv)  row bounds (FusedBatch.set_row_bounds; DESIGN.md section 14 "Row bounds"): the upper bound of every nonlinear row loosened
+        by 0.25 in the even instances and tightened by 1/64 in the odd ones; the line below the table gives the time of
+        k_blocks_rebase from device events and the cut rows it moved.
 Median of REPS timed solves after one warm-up.  Every timed warm solve starts from the same state: the arenas of a cold solve
 of the loaded data.  Writes profiles/blocks_warm.txt (or argv[2]); no speed-up is promised, the figure to compare a warm
 solve against is the cold solve of the same handle in the same run.
 
-    python tools/blocks_warm_bench.py [instances = 512] [out = profiles/blocks_warm.txt]"""
+    python tools/blocks_warm_bench.py [instances = 512] [out = profiles/blocks_warm.txt] [cases = all, or a comma list of their names]"""
 import os
 import statistics
 import sys
@@ -53,14 +56,30 @@ def branched():
     return us
 
 
+ub0 = [np.array(i.u_constr, dtype=np.float64) for i in insts]
+
+
+def moved_rows():
+    out = []
+    for k, (inst, u) in enumerate(zip(insts, ub0)):
+        u = u.copy()
+        u[inst.m_lin:] += 0.25 if k % 2 == 0 else -1.0 / 64
+        out.append(u)
+    return out
+
+
 CASES = [("unchanged", lambda: None),
          ("one bound", lambda: fb.set_var_bounds(l0, branched())),
-         ("costs x 1.25", lambda: fb.set_costs([cost(i, 1.25) for i in insts]))]
+         ("costs x 1.25", lambda: fb.set_costs([cost(i, 1.25) for i in insts])),
+         ("row bounds", lambda: fb.set_row_bounds(None, moved_rows()))]
+if len(sys.argv) > 3 and sys.argv[3] != "all":
+    CASES = [c for c in CASES if c[0] in sys.argv[3].split(",")]
 
 
 def restore():
     fb.set_var_bounds(l0, u0)
     fb.set_costs([cost(i, 1.0) for i in insts])
+    fb.set_row_bounds(None, ub0)
 
 
 def timed(**kw):
@@ -82,7 +101,9 @@ for name, apply in CASES:
         restore()
         fb.solve(fallback=False)                              # the state every warm solve starts from
         apply()
+        rebase = (m.stat("rebase_kernel_s"), m.stat("rebase_rows")) if name == "row bounds" else None
         w = timed(warm=True)
+        w["rebase"] = rebase
         w["dropped"], w["kernel"] = m.stat("ecp_blocks_warm_dropped_rows"), m.stat("ecp_blocks_rewarm_kernel_s")
         w["states"] = (m.stat("ecp_blocks_warm_instances"), m.stat("ecp_blocks_warm_cold_instances"), m.stat("ecp_blocks_warm_infeasible"))
         c = timed()
@@ -100,6 +121,10 @@ for name, apply in CASES:
             "%.1e" % diff if tag == "warm" else "-"))
     lines.append("%-13s       states of the warm launch (warm / cold / infeasible): %d / %d / %d; overflows warm %d cold %d" % (
         (name,) + tuple(int(v) for v in warm[-1]["states"]) + (warm[-1]["overflow"], cold[-1]["overflow"])))
+    if name == "row bounds":
+        lines.append("%-13s       k_blocks_rebase: median %.1f us (min %.1f, max %.1f), %d cut rows moved" % (
+            name, 1e6 * statistics.median(x["rebase"][0] for x in warm), 1e6 * min(x["rebase"][0] for x in warm),
+            1e6 * max(x["rebase"][0] for x in warm), int(warm[-1]["rebase"][1])))
 text = "\n".join(lines)
 print(text)
 with open(out_path, "w") as f:

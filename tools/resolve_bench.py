@@ -9,7 +9,12 @@ nothing an earlier repetition or child added (pool_rows_before reports it).  Tim
 that end in a stream synchronisation.  Reported per child and in total: rounds, PDHG iterations and seconds for both, the spread
 (min - max) of the cold runs, and the screen's kernel time at that pool size from device events (stat "screen_kernel_s").
 
-    python tools/resolve_bench.py [--config cfg3] [--children 16] [--reps 7] [--seed 0] [--out profiles/resolve_warm.txt]
+With --rows the children move a CONSTRAINT bound instead (ktn_set_row_bounds; DESIGN.md section 14 "Row bounds"): child i takes the
+nonlinear row with the i-th largest multiplier at the parent's solution and loosens its upper bound by 0.25 (odd i: tightens it by
+1/64); warm is setconstrbounds + solve, cold the re-load with the child's row bounds + solve.  "rebase_kernel_us" is the time of
+k_rebase_cuts on the parent's pool from device events (stat "rebase_kernel_s"), "rebase_rows" the cut rows it moved.
+
+    python tools/resolve_bench.py [--config cfg3] [--children 16] [--reps 7] [--seed 0] [--rows] [--out profiles/resolve_warm.txt]
 KTN_PKG_ROOT=<checkout> imports the package from another (built) checkout."""
 import argparse
 import json
@@ -33,8 +38,8 @@ def emit(out, path):
             f.write(line + "\n")
 
 
-def load(m, inst, l, u):
-    m.loadproblem(inst.n, inst.num_constr, l, u, inst.l_constr, inst.u_constr, inst.sense, ktn.SeparableNLP(inst))
+def load(m, inst, l, u, ub=None):
+    m.loadproblem(inst.n, inst.num_constr, l, u, inst.l_constr, inst.u_constr if ub is None else ub, inst.sense, ktn.SeparableNLP(inst))
 
 
 def timed(f):
@@ -49,6 +54,7 @@ def main():
     ap.add_argument("--children", type=int, default=16)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--rows", action="store_true", help="children move a constraint bound instead of a variable bound")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     inst = ktn.instances.make_config(a.config, seed=a.seed)
@@ -62,12 +68,19 @@ def main():
     emit(dict(config=a.config, seed=a.seed, parent_status=st, parent_rounds=warm.numiters(), parent_pdhg=p0, parent_solve_s=t_parent,
               parent_obj=warm.getobjval(), pool_rows=warm.lp_num_rows(), load_s=t_load, n=int(inst.n), m=int(inst.num_constr)), a.out)
     order = np.argsort(-np.minimum(x - l0, u0 - x))
+    ub0 = np.array(inst.u_constr, dtype=np.float64)
+    if a.rows:                                              # the nonlinear rows by multiplier, largest first
+        d = np.abs(warm.getconstrduals())
+        order = inst.m_lin + np.argsort(-d[inst.m_lin:], kind="stable")
     med = lambda v: float(np.median(v))
     tot = dict(warm_s=0.0, cold_s=0.0, warm_rounds=0, cold_rounds=0, warm_pdhg=0.0, cold_pdhg=0.0)
     for i in range(a.children):
         j = int(order[i])
         l, u = l0.copy(), u0.copy()
-        if i % 2 == 0:
+        ub = ub0.copy()
+        if a.rows:
+            ub[j] += 0.25 if i % 2 == 0 else -1.0 / 64
+        elif i % 2 == 0:
             u[j] = x[j] - 0.25 * (x[j] - l0[j])
         else:
             l[j] = x[j] + 0.25 * (u0[j] - x[j])
@@ -78,19 +91,22 @@ def main():
             warm.optimize()
             rows_before = warm.lp_num_rows()
             pw = warm.stat("pdhg_iters")
-            (sw, tw) = timed(lambda: (warm.setvarbounds(l, u), warm.optimize())[1])
-            rec_w = (tw, warm.numiters(), warm.stat("pdhg_iters") - pw, sw, warm.getobjval(), warm.stat("screen_kernel_s"), warm.lp_num_rows(), rows_before)
+            (sw, tw) = timed(lambda: ((warm.setconstrbounds(None, ub) if a.rows else warm.setvarbounds(l, u)), warm.optimize())[1])
+            rec_w = (tw, warm.numiters(), warm.stat("pdhg_iters") - pw, sw, warm.getobjval(), warm.stat("screen_kernel_s"), warm.lp_num_rows(), rows_before,
+                     warm.stat("rebase_kernel_s"), warm.stat("rebase_rows"))
             pc = cold.stat("pdhg_iters")
-            (sc, tc) = timed(lambda: (load(cold, inst, l, u), cold.optimize())[1])
+            (sc, tc) = timed(lambda: (load(cold, inst, l, u, ub), cold.optimize())[1])
             rec_c = (tc, cold.numiters(), cold.stat("pdhg_iters") - pc, sc, cold.getobjval())
             if rep:
                 W.append(rec_w); C.append(rec_c)
-        out = dict(child=i, var=j, side="upper" if i % 2 == 0 else "lower", warm_status=W[0][3], cold_status=C[0][3],
+        out = dict(child=i, var=j, side=("loosened" if i % 2 == 0 else "tightened") if a.rows else ("upper" if i % 2 == 0 else "lower"), warm_status=W[0][3], cold_status=C[0][3],
                    warm_s=med([w[0] for w in W]), cold_s=med([c[0] for c in C]), cold_s_min=min(c[0] for c in C), cold_s_max=max(c[0] for c in C),
                    warm_s_min=min(w[0] for w in W), warm_s_max=max(w[0] for w in W),
                    warm_rounds=int(med([w[1] for w in W])), cold_rounds=int(med([c[1] for c in C])),
                    warm_pdhg=med([w[2] for w in W]), cold_pdhg=med([c[2] for c in C]), warm_obj=W[-1][4], cold_obj=C[-1][4],
                    screen_kernel_us=1e6 * med([w[5] for w in W]), pool_rows=int(W[-1][6]), pool_rows_before=int(W[-1][7]))
+        if a.rows:
+            out.update(row=j, rebase_kernel_us=1e6 * med([w[8] for w in W]), rebase_rows=int(W[-1][9]))
         for k in tot:
             tot[k] += out[k]
         emit(out, a.out)
